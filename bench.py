@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py — synthesized 1024^2 StyleGAN2 frames/s on N MI355X (BASELINE.json metric), with roofline + CPU baseline.
+"""bench.py — synthesized 1024^2 StyleGAN2 frames/s on N MI355X (BASELINE.json metric); with --full also roofline + CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--batches-per-step Q] [--size 1024] [--bends]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +13,11 @@ the render.py:40-43 epilogue), batches alternating over `--lanes` graphs on thei
 does.  Frames are independent, so ranks shard them with no data-path collective (weak scaling: Q * B frames per rank per step).
 Weights are random-init (seeded numpy streams) of the real 1024^2 architecture; arithmetic is fp32 end to end.
 
-Rank 0 prints ONE JSON line.  `roofline` is the single launch with the largest device time (measured live with HIP events on
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given
+(dump_outputs) and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's
+description.  Everything below is measured or checked only with --full (each part can be left out with its --no-* switch).
+
+`roofline` is the single launch with the largest device time (measured live with HIP events on
 the launch stream): `achieved` / `frac` count the flops the matrix cores EXECUTED (the Winograd forms issue a fraction of the
 direct form's multiplies), the SURVEY-8d direct-conv figure sits under `roofline.algorithmic`; `roofline_time_dominant` is the
 kernel instance with the largest share of the serial forward (all its launches of a batch), `conv_kernel_instances` the same
@@ -21,7 +26,8 @@ up-conv shape that carries 49 % of the path's upfirdn2d bytes (BASELINE.md §3.2
 `side_configs` times BASELINE configs 2 (256^2 generator) and 5 (1024^2 with per-frame Translate + Zoom network bends,
 captured) on this GPU.  `cpu_baseline` times oracle/ (the CPU restatement pinned to the reference by tests/golden) on the
 host cores (BASELINE.md §4 legs).  `frame_check` compares the frames of the last replay of every lane with the eager
-(un-captured) forward of the same frames, bit for bit.
+(un-captured) forward of the same frames, bit for bit.  `frames_per_sec_pcie_inclusive` (one GPU) and `frames_per_sec_synth_only`
+(several) time further regions after the headline one; `rccl` (several ranks) records who took part and what the collectives moved.
 """
 import argparse
 import gc
@@ -400,6 +406,37 @@ class Workload:
         return worst
 
 
+DUMP_PIXELS = 1 << 16       # seeded pixel positions sampled from every dumped frame
+DUMP_SAMPLE_BYTES = 32 << 20  # at most this much for the sampled frames, at most 24 MiB for the whole frame: < 64 MB in all
+
+
+def dump_outputs(wl, out_dir):
+    """What the timed path delivered at the end of its last step, as float32 .npy files under ``out_dir``: the uint8 NHWC frames
+    that the last replay of every lane left in the lane's frame buffer (the last n_lanes batches of the step).
+
+    frames_sample.npy  [frames, pixels, 3]  those frames at DUMP_PIXELS positions drawn once with seed 0 (pixel_index.npy, y * W + x)
+    frame_index.npy    [frames]             index of each frame in this rank's sequence
+    frame_last.npy     [H, W, 3]            the last frame of the last batch, whole
+    """
+    import numpy as np
+
+    wl.sync()
+    done = sorted((f0, k) for k, f0 in enumerate(wl.last) if f0 is not None)
+    frames = torch.cat([wl.lanes[k][1].u8 for _, k in done])  # [frames, H, W, 3] uint8
+    n, h, w, _ = frames.shape
+    n_pix = min(h * w, DUMP_PIXELS, DUMP_SAMPLE_BYTES // (n * 3 * 4))
+    pix = np.sort(np.random.default_rng(0).choice(h * w, size=n_pix, replace=False))
+    sample = frames.view(n, h * w, 3)[:, torch.from_numpy(pix).to(frames.device)]
+    out = {"frames_sample": sample.float().cpu().numpy(), "pixel_index": pix.astype(np.float64),
+           "frame_index": np.concatenate([np.arange(f0, f0 + wl.B) for f0, _ in done]).astype(np.float64)}
+    if h * w * 3 * 4 <= 24 << 20:
+        last_lane = wl.lanes[(wl.count - 1) % wl.n_lanes][1]
+        out["frame_last"] = last_lane.u8[-1].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def time_region(wl, steps, bps, mode, use_dist, world):
     """Time ``steps`` steps of ``bps`` batches.  mode "synth": replay + uint8 epilogue only.  "gathered" (N > 1): every batch's
     frames also travel to rank 0 through sharding.FrameStream (one asynchronous RCCL gather per batch, as render() issues them);
@@ -590,10 +627,15 @@ def main():
                          "as render.synthesize does); 1 = strictly serial batches")
     ap.add_argument("--force-gather", action="store_true",
                     help="debug: run the N > 1 timed region (per-batch FrameStream push + landing wait) on one GPU as well")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the config 2 / config 5 side measurements")
-    ap.add_argument("--no-pcie-side", action="store_true", help="skip the host-inclusive side measurement (copy accounting runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step delivered as float32 DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also run every check and side measurement: frame check, host-inclusive / synth-only "
+                         "regions, rccl record, side configurations, per-layer breakdown and rooflines, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="with --full: skip the per-layer breakdown and the conv rooflines")
+    ap.add_argument("--no-side-configs", action="store_true", help="with --full: skip the config 2 / config 5 side measurements")
+    ap.add_argument("--no-pcie-side", action="store_true", help="with --full: skip the host-inclusive side measurement (copy accounting runs)")
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=VALUE",
                     help="A/B switch of an EXPERIMENTS build (tools/build_exp.sh, pass it with --lib): maua_tuning_set(KEY, VALUE) before "
                          "the graphs are captured; the product library has no such entry")
@@ -616,6 +658,8 @@ def main():
                     help="start the ranks through torch.distributed.run from this process also when --gpus is 1 (--gpus N > 1 without a "
                          "rendezvous in the environment always does)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # MAUA_DIST_BACKEND=gloo (debug): run the N > 1 code path with several ranks SHARING one GPU — RCCL wants one GPU per rank, gloo moves
     # device tensors for the collectives this path uses; the rate measured that way is meaningless, the code path is the real one
@@ -684,22 +728,24 @@ def main():
     for _ in range(args.warmup * bps):
         wl.batch()
     wl.sync()
-    # the headline region: EXACTLY --steps steps.  One GPU: synthesis with the frames left in HBM (the PCIe-inclusive rate
-    # is reported next to it).  Several GPUs: the frames of every batch are gathered to rank 0 inside the timed region.
+    # the headline region: EXACTLY --steps steps.  One GPU: synthesis with the frames left in HBM (--full reports the PCIe-inclusive
+    # rate next to it).  Several GPUs: the frames of every batch are gathered to rank 0 inside the timed region.
     elapsed = time_region(wl, args.steps, bps, "gathered" if (world > 1 or args.force_gather) else "synth", use_dist, world)
-    frame_err = wl.check_frames()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
+    frame_err = wl.check_frames() if args.full else None
     extra = {}
     side = max(1, min(args.steps, 8))
-    if world > 1 or args.force_gather:
+    if args.full and (world > 1 or args.force_gather):
         extra["frames_per_sec_synth_only"] = world * side * bps * B / time_region(wl, side, bps, "synth", use_dist, world)
-    if world == 1 and not args.no_pcie_side:
+    if args.full and world == 1 and not args.no_pcie_side:
         regions = sorted(side * bps * B / time_region(wl, side, bps, "pcie", use_dist, world) for _ in range(3))
         extra["frames_per_sec_pcie_inclusive"] = regions[1]  # median of three regions (they scatter by 5 % run to run on one box)
         extra["frames_per_sec_pcie_inclusive_regions"] = regions
         extra["pcie_inclusive_note"] = (f"median of three regions of {side} steps; every batch moves to a device-side ring slot on its lane's stream and from there to "
                                         "pinned host memory on a copy stream (6 slots), as render() does; null sink (no encoder)")
 
-    rccl = rccl_block(dev, rank, world, backend, wl) if use_dist else None  # (collective: every rank calls it)
+    rccl = rccl_block(dev, rank, world, backend, wl) if use_dist and args.full else None  # (collective: every rank calls it)
     result = None
     if rank == 0:
         frames = world * args.steps * bps * B
@@ -721,23 +767,24 @@ def main():
             "timed_region_s": elapsed,
             "value_definition": ("uint8 frames of every batch gathered to rank 0's HBM (one async RCCL gather per batch, "
                                  "sharding.FrameStream) inside the timed region" if (world > 1 or args.force_gather) else
-                                 "uint8 frames left in HBM (see frames_per_sec_pcie_inclusive for the host-inclusive rate)"),
+                                 "uint8 frames left in HBM (--full: frames_per_sec_pcie_inclusive is the host-inclusive rate)"),
             **extra,
             "conv_tflops_sustained": conv_flops_per_frame(size) * fps / world / 1e12,
-            "frame_check": {"max_abs_grey_level_diff_graph_vs_eager": frame_err,
-                            "what": "uint8 frames of the last replay of every lane vs the eager (un-captured) forward of the same frames"},
             "device": _lib.device_info(),
         }
+        if frame_err is not None:
+            result["frame_check"] = {"max_abs_grey_level_diff_graph_vs_eager": frame_err,
+                                     "what": "uint8 frames of the last replay of every lane vs the eager (un-captured) forward of the same frames"}
         if rccl is not None:
             result["rccl"] = rccl
             if rccl["frames"].get("payload_check") == "FAILED" or not rccl["weights"]["param_checksums_equal_after_broadcast"]:
                 print("bench.py: a collective delivered wrong bytes (see the rccl block)", file=sys.stderr)
                 result["rccl"]["FAILED"] = True
-        if frame_err != 0:
+        if frame_err not in (None, 0):
             print(f"bench.py: captured frames differ from the eager forward by {frame_err} grey levels", file=sys.stderr)
             result["frame_check"]["FAILED"] = True
     # ---- side configurations (rank 0's GPU only, after the headline region; N == 1 runs only)
-    if rank == 0 and world == 1 and not args.no_side_configs and size == 1024 and not args.bends:
+    if args.full and rank == 0 and world == 1 and not args.no_side_configs and size == 1024 and not args.bends:
         sides = {}
         for name, (sz, bends) in {"config5_1024_bends": (1024, True), "config2_256": (256, False)}.items():
             try:
@@ -824,7 +871,7 @@ def main():
         result["side_configs_note"] = ("same machinery as the headline (captured forward, 3 lanes, HBM-resident sequences): BASELINE config 5's "
                                        "workload = modulated Translate at layer id 4 + modulated Zoom at layer id 5 read per frame on the "
                                        "device; config 2's generator = StyleGAN2-256 with every noise scale per-frame")
-    if rank == 0:
+    if args.full and rank == 0:
         if not args.no_breakdown and not args.bends:
             # the isolated launches below are timed in the chip's loaded state: ~0.4 s of the headline workload right in front of them
             # (after the side configurations the device has idled through their set-up)
@@ -997,7 +1044,7 @@ def main():
             result["roofline_upfirdn2d"]["measured_copy_gbs"] = copy_gbs
             result["roofline_upfirdn2d"]["frac_of_measured_copy"] = ach / copy_gbs
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(size)
         print(json.dumps(result))
     if use_dist:

@@ -610,6 +610,10 @@ def stylegan1_fixture(seeding):
     with open(os.path.join(HERE, "stylegan1_meta.json"), "w") as f:
         json.dump(meta, f)
     print("  G_style(1920, 128-px checkpoint): const", meta["const"], "noise", meta["noise"][0], "...", meta["noise"][-1])
+    # the image goes one frame per file: the pair does not compress below the size limit of a committed file
+    image = out.pop("synth.image")
+    for i in range(image.shape[0]):
+        np.savez_compressed(os.path.join(HERE, f"stylegan1_image_{i}.npz"), image=image[i:i + 1])
     np.savez_compressed(os.path.join(HERE, "stylegan1.npz"), **out)
 
 
@@ -624,7 +628,7 @@ def main():
     ap.add_argument("--only-signatures", action="store_true", help="(re)generate signatures.json only")
     ap.add_argument("--only-variants", action="store_true", help="(re)generate generator_variants.npz only")
     ap.add_argument("--only-latent-utils", action="store_true", help="(re)generate latent_utils.npz only")
-    ap.add_argument("--only-stylegan1", action="store_true", help="(re)generate stylegan1.npz / stylegan1_meta.json only")
+    ap.add_argument("--only-stylegan1", action="store_true", help="(re)generate stylegan1.npz / stylegan1_image_*.npz / stylegan1_meta.json only")
     ap.add_argument("--only-plugin", action="store_true", help="(re)generate default_plugin.npz / generate_e2e.npz only")
     args = ap.parse_args()
 

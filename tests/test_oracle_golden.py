@@ -450,6 +450,12 @@ def _sg1_state_dict(fx):
     return sd
 
 
+def _sg1_image(golden):
+    """The reference's G_synthesis image of stylegan1.npz's network, [2, 3, 256, 256]: stored one frame per file
+    (stylegan1_image_<i>.npz) to keep every fixture under the size limit of a committed file."""
+    return np.concatenate([golden(f"stylegan1_image_{i}.npz")["image"] for i in range(2)])
+
+
 def test_stylegan1_oracle_matches_reference_golden(golden):
     """oracle/stylegan1_oracle.py against outputs of the reference's G_synthesis / G_mapping classes (stylegan1.npz), and the
     identity the device path is built on: the reference's fused conv_transpose2d upscale (>= 128 px, models/stylegan1.py:83-93)
@@ -463,7 +469,7 @@ def test_stylegan1_oracle_matches_reference_golden(golden):
     n_blocks = 7
     dl = torch.from_numpy(seeding.seeded_array(s_l, "dlatents", (2, 2 * n_blocks, 512)))
     noise = [torch.from_numpy(seeding.seeded_array(s_n, f"noise_{i}", (2 if i % 2 else 1, 1, 4 * 2 ** i, 4 * 2 ** i))) for i in range(n_blocks)]
-    np.testing.assert_allclose(s1o.synthesis(sd, dl, noise, prefix="").numpy(), fx["synth.image"], atol=2e-4)
+    np.testing.assert_allclose(s1o.synthesis(sd, dl, noise, prefix="").numpy(), _sg1_image(golden), atol=2e-4)
     rng = np.random.default_rng(5)
     x = torch.from_numpy(rng.standard_normal((2, 5, 64, 72)).astype(np.float32))
     w = torch.from_numpy(rng.standard_normal((7, 5, 3, 3)).astype(np.float32))

@@ -6,7 +6,7 @@ mkdir -p $out
 for round in 1 2; do
 for v in "$@"; do
   if [ "$v" = base ]; then lib=""; else lib="--lib tools/bin/libmaua_$v.so"; fi
-  python bench.py --steps 12 --no-cpu-baseline --no-side-configs $lib > $out/bench_${v}_$round.json 2> $out/bench_${v}_$round.err
+  python bench.py --full --steps 12 --no-cpu-baseline --no-side-configs $lib > $out/bench_${v}_$round.json 2> $out/bench_${v}_$round.err
   python - <<PY
 import json
 p=json.load(open("$out/bench_${v}_$round.json"))

@@ -87,8 +87,8 @@ def main():
 
 Commands (tools/profile_round.sh, run through gpurun on one MI355X):
 
-    rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --no-cpu-baseline --no-side-configs --lanes 1   # strictly serial batches
-    rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --no-cpu-baseline --no-side-configs             # default: 3 graph lanes
+    rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --full --no-cpu-baseline --no-side-configs --lanes 1   # strictly serial batches
+    rocprofv3 --kernel-trace --stats -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --full --no-cpu-baseline --no-side-configs             # default: 3 graph lanes
 
 The serial run is the one whose per-kernel averages are comparable with the live HIP-event numbers in the bench JSON
 (profiles/{TAG}_bench_rocprof_lanes1.json: {l1['value']:.0f} frames/s, roofline.launch_ms {l1['roofline']['launch_ms']:.3f} ms for
@@ -116,7 +116,7 @@ up2d_edge_kernel = its two edge lines.  PRE = true: the instance for an input ma
 ## Final kernels of {TAG}, measured inside bench.py
 
 Command (tools/profile_round.sh): `rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY
-SQ_WAVE_CYCLES --kernel-trace -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --lanes 1 --no-cpu-baseline
+SQ_WAVE_CYCLES --kernel-trace -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --full --lanes 1 --no-cpu-baseline
 --no-side-configs --no-breakdown` and a second pass with `--pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32
 SQ_INSTS_VALU SQ_WAIT_ANY` (counters only, with --kernel-trace; no sys/hip/hsa trace domains).  Averages over every dispatch of the template instance in the run (batch 8, 1024^2 generator).
 MFMA busy % = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); clock = (GRBM_GUI_ACTIVE / 8) / duration.
@@ -143,7 +143,7 @@ duration; "non-MFMA VALU per MFMA" = (SQ_INSTS_VALU - MOPS / 4) / (MOPS / 4).
     open(f"profiles/{TAG}_pmc_modconv.md", "w").write(f"# PMC counters of the modulated-conv kernels ({TAG})\n" + "\n".join(lines) + "\n")
 
     tr = [f"# HBM traffic per launch inside bench.py ({TAG}; rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes)", "",
-          "Command: `rocprofv3 --pmc <CTR> --kernel-trace -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --lanes 1 --no-cpu-baseline --no-side-configs --no-breakdown`",
+          "Command: `rocprofv3 --pmc <CTR> --kernel-trace -- python bench.py --steps 1 --warmup 1 --batches-per-step 3 --full --lanes 1 --no-cpu-baseline --no-side-configs --no-breakdown`",
           "(tools/profile_round.sh).  Units: KB per dispatch, averaged over the dispatches of one template instance.  Corrections as calibrated",
           "in r01_pmc_upfirdn2d.md against kernels of known traffic (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports exactly 1/2 of",
           "the bytes read -> x2; WRITE_SIZE is exact.", "",
@@ -178,7 +178,7 @@ duration; "non-MFMA VALU per MFMA" = (SQ_INSTS_VALU - MOPS / 4) / (MOPS / 4).
     bench = last_json(f"{O}/bench_default.json")
     with open(f"profiles/{TAG}_pmc_traffic.json", "w") as f:
         json.dump({"source": "tools/profile_round.sh: rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python bench.py "
-                             "--steps 1 --warmup 1 --batches-per-step 3 --lanes 1 --no-cpu-baseline --no-side-configs --no-breakdown",
+                             "--steps 1 --warmup 1 --batches-per-step 3 --full --lanes 1 --no-cpu-baseline --no-side-configs --no-breakdown",
                    "correction": "FETCH_SIZE x2 (reports 1/2 of the bytes read on gfx950, calibrated on a known-size copy), WRITE_SIZE exact",
                    "batch": bench["config"]["batch"], "size": 1024, "kernels": kernels}, f, indent=1)
     print(f"wrote profiles/{TAG}_*")

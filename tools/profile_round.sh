@@ -9,9 +9,9 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 ( cd "$R" && python -m pytest tests -q -m gpu > "$O/pytest_gpu.log" 2>&1; echo "pytest rc=$?" >> "$O/pytest_gpu.log" )
 ( cd "$R" && python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 )
-( cd "$R" && python bench.py --steps 20 > "$O/bench_default.json" 2> "$O/bench_default.err" )
+( cd "$R" && python bench.py --full --steps 20 > "$O/bench_default.json" 2> "$O/bench_default.err" )
 # short traced / counted runs: 1 warm-up + 1 timed step of 3 batches (every kernel instance of the path is dispatched several times)
-SHORT="--steps 1 --warmup 1 --batches-per-step 3 --no-cpu-baseline --no-side-configs"
+SHORT="--steps 1 --warmup 1 --batches-per-step 3 --full --no-cpu-baseline --no-side-configs"
 rocprofv3 --kernel-trace --stats -d "$O/trace_lanes3" -o bench -- python "$R/bench.py" $SHORT > "$O/bench_trace_lanes3.json" 2> "$O/trace_lanes3.err"
 rocprofv3 --kernel-trace --stats -d "$O/trace_lanes1" -o bench -- python "$R/bench.py" $SHORT --lanes 1 > "$O/bench_trace_lanes1.json" 2> "$O/trace_lanes1.err"
 # copy accounting: the same traced run with 3 and with 12 batches per step and nothing else in the process (no breakdown, no warm-up);

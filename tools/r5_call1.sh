@@ -10,11 +10,11 @@ export TMPDIR=/tmp
 ( timeout 1500 python -m pytest tests/test_world8_gpu.py tests/test_signal_gpu.py tests/test_two_rank_gpu.py "tests/test_render_gpu.py::test_render_rank_shards_on_device_equal_single_rank" "tests/test_render_gpu.py::test_whole_workload_wav_to_frames_vs_oracle" -q -m gpu -s -p no:cacheprovider > "$O/pytest_new.log" 2>&1; echo "pytest rc=$?" >> "$O/pytest_new.log" )
 tail -3 "$O/pytest_new.log"
 COMMON="--no-cpu-baseline --no-breakdown --no-side-configs --no-pcie-side"
-( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 1 --force-gather $COMMON > "$O/bench_rccl_1rank_force_gather.json" 2> "$O/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
+( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 5 --warmup 1 --force-gather $COMMON > "$O/bench_rccl_1rank_force_gather.json" 2> "$O/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
 ( timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 tools/rccl_probe.py > "$O/rccl_probe.log" 2>&1; echo "probe rc=$?" )
-( MAUA_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29515 bench.py --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$O/bench_8ranks_gloo_one_gpu.json" 2> "$O/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
+( MAUA_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29515 bench.py --full --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$O/bench_8ranks_gloo_one_gpu.json" 2> "$O/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
 bash tools/asan_run.sh > "$O/asan_stdout.log" 2>&1; cp -r gpurun_out/asan "$O/asan" 2>/dev/null; rm -rf gpurun_out/asan
-( timeout 600 python bench.py --steps 10 --no-cpu-baseline > "$O/bench_short.json" 2> "$O/bench_short.err"; echo "bench rc=$?" )
+( timeout 600 python bench.py --full --steps 10 --no-cpu-baseline > "$O/bench_short.json" 2> "$O/bench_short.err"; echo "bench rc=$?" )
 head -c 400 "$O/bench_short.json"; echo
 ( timeout 600 python tools/fuse_probe.py --lib tools/bin/libmaua_fuse.so > "$O/fuse_probe.json" 2> "$O/fuse_probe.err"; echo "fuse rc=$?"; cat "$O/fuse_probe.json"; tail -3 "$O/fuse_probe.err" )
 python - <<PY

@@ -9,8 +9,8 @@ O=$R/gpurun_out/prof_final
 X=$R/gpurun_out/r5_extras
 rm -rf "$X"; mkdir -p "$X"
 COMMON="--no-cpu-baseline --no-breakdown --no-side-configs --no-pcie-side"
-( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 10 --warmup 2 --force-gather $COMMON > "$X/bench_rccl_1rank_force_gather.json" 2> "$X/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
-( MAUA_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29515 bench.py --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$X/bench_8ranks_gloo_one_gpu.json" 2> "$X/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
+( timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 10 --warmup 2 --force-gather $COMMON > "$X/bench_rccl_1rank_force_gather.json" 2> "$X/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
+( MAUA_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29515 bench.py --full --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$X/bench_8ranks_gloo_one_gpu.json" 2> "$X/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
 bash tools/asan_run.sh > "$X/asan_stdout.log" 2>&1; cp -r gpurun_out/asan "$X/asan" 2>/dev/null; rm -rf gpurun_out/asan
 ( timeout 300 python tools/fuse_probe.py --lib maua_stylegan2_amd/csrc/libmaua_hip.so --exact --rounds 3 > "$X/fuse_probe_exact.json" 2> "$X/fuse_probe_exact.err"; echo "fuse exact rc=$?" )
 # (the segment-length override only exists in the experiments build)

@@ -11,11 +11,11 @@ export TMPDIR=/tmp
 grep -n "style fold\|passed\|failed\|rc=\|Error\|assert" "$O/pytest_fold.log" | tail -40
 COMMON="--no-cpu-baseline --no-side-configs --no-pcie-side"
 for r in 1 2 3; do
-  ( timeout 600 python bench.py --steps 10 $COMMON --no-breakdown > "$O/bench_fold_on_$r.json" 2> "$O/bench_fold_on_$r.err"; echo "on rc=$?" )
-  ( timeout 600 python bench.py --steps 10 $COMMON --no-breakdown --no-style-fold > "$O/bench_fold_off_$r.json" 2> "$O/bench_fold_off_$r.err"; echo "off rc=$?" )
+  ( timeout 600 python bench.py --full --steps 10 $COMMON --no-breakdown > "$O/bench_fold_on_$r.json" 2> "$O/bench_fold_on_$r.err"; echo "on rc=$?" )
+  ( timeout 600 python bench.py --full --steps 10 $COMMON --no-breakdown --no-style-fold > "$O/bench_fold_off_$r.json" 2> "$O/bench_fold_off_$r.err"; echo "off rc=$?" )
 done
-( timeout 600 python bench.py --steps 10 $COMMON > "$O/bench_layers_on.json" 2> "$O/bench_layers_on.err"; echo "layers on rc=$?" )
-( timeout 600 python bench.py --steps 10 $COMMON --no-style-fold > "$O/bench_layers_off.json" 2> "$O/bench_layers_off.err"; echo "layers off rc=$?" )
+( timeout 600 python bench.py --full --steps 10 $COMMON > "$O/bench_layers_on.json" 2> "$O/bench_layers_on.err"; echo "layers on rc=$?" )
+( timeout 600 python bench.py --full --steps 10 $COMMON --no-style-fold > "$O/bench_layers_off.json" 2> "$O/bench_layers_off.err"; echo "layers off rc=$?" )
 python - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/bench_fold_*.json")):

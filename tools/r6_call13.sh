@@ -11,7 +11,7 @@ rocprofv3 --kernel-trace -d "$O/trace" -o bench -- python "$R/bench.py" --steps 
 python "$R/tools/rocpd_timeline.py" "$O/trace/bench_results.db" 2 > "$O/timeline.md"; rm -rf "$O/trace"
 head -24 "$O/timeline.md" | cut -c1-110; tail -1 "$O/timeline.md"
 cd "$R"
-python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/bench.json" 2> "$O/bench.err" || tail -5 "$O/bench.err"
+python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/bench.json" 2> "$O/bench.err" || tail -5 "$O/bench.err"
 python - <<PY
 import json
 p=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ rm -rf "$O"; mkdir -p "$O"
 cd "$R"
 export TMPDIR=/tmp
 for b in 8 16 24 32; do
-  timeout 600 python bench.py --batch $b --lanes 1 --steps 2 --warmup 1 --batches-per-step 4 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/b$b.json" 2> "$O/b$b.err"; echo "rc=$?"
+  timeout 600 python bench.py --full --batch $b --lanes 1 --steps 2 --warmup 1 --batches-per-step 4 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/b$b.json" 2> "$O/b$b.err"; echo "rc=$?"
   python - <<PY
 import json
 p=json.loads(open("$O/b$b.json").read().strip().splitlines()[-1])

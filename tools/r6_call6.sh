@@ -10,7 +10,7 @@ tail -3 "$O/pytest_layers.log"
 rocprofv3 --kernel-trace -d "$O/trace" -o bench -- python "$R/bench.py" --steps 1 --warmup 1 --batches-per-step 3 --lanes 1 --no-cpu-baseline --no-side-configs --no-breakdown --no-pcie-side > "$O/bench_trace.json" 2> "$O/trace.err"
 python "$R/tools/rocpd_timeline.py" "$O/trace/bench_results.db" 2 > "$O/timeline.md"; rm -rf "$O/trace"
 cat "$O/timeline.md"
-( cd "$R" && python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/bench.json" 2> "$O/bench.err" )
+( cd "$R" && python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-side-configs --no-pcie-side > "$O/bench.json" 2> "$O/bench.err" )
 python - <<PY
 import json
 p=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

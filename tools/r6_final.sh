@@ -9,10 +9,10 @@ cd "$R"
 export TMPDIR=/tmp
 bash tools/asan_run.sh > "$O/asan_stdout.log" 2>&1; cp gpurun_out/asan/summary.txt "$O/asan_summary.txt" 2>/dev/null; cp gpurun_out/asan/host.log "$O/asan_host.log" 2>/dev/null; rm -rf gpurun_out/asan
 head -12 "$O/asan_summary.txt"; grep -c " ok$" "$O/asan_summary.txt"
-( timeout 900 python bench.py --steps 20 --warmup 5 > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench rc=$?" )
+( timeout 900 python bench.py --full --steps 20 --warmup 5 > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench rc=$?" )
 COMMON="--no-cpu-baseline --no-breakdown --no-side-configs --no-pcie-side"
-( timeout 600 python bench.py --gpus 1 --self-launch --force-gather --steps 5 --warmup 1 $COMMON > "$O/bench_rccl_1rank_self_launched.json" 2> "$O/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
-( MAUA_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$O/bench_8ranks_gloo_self_launched.json" 2> "$O/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
+( timeout 600 python bench.py --full --gpus 1 --self-launch --force-gather --steps 5 --warmup 1 $COMMON > "$O/bench_rccl_1rank_self_launched.json" 2> "$O/bench_rccl_1rank.err"; echo "rccl-1 rc=$?" )
+( MAUA_DIST_BACKEND=gloo timeout 900 python bench.py --full --gpus 8 --steps 2 --warmup 1 --lanes 1 $COMMON > "$O/bench_8ranks_gloo_self_launched.json" 2> "$O/bench_8ranks_gloo.err"; echo "gloo-8 rc=$?" )
 ( timeout 600 python tools/e2e_config3.py --repeat 6 > "$O/e2e_config3.txt" 2>&1; echo "e2e rc=$?" )
 grep "E2E run\|preprocessing took\|rendered" "$O/e2e_config3.txt"
 python - <<PY

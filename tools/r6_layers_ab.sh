@@ -7,7 +7,7 @@ mkdir -p "$O"
 cd "$R"; export TMPDIR=/tmp
 for rep in 1 2; do
 for lib in $LIBS; do
-python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-side-configs --no-pcie-side --lib $lib > "$O/bench.json" 2> "$O/bench.err" || tail -5 "$O/bench.err"
+python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-side-configs --no-pcie-side --lib $lib > "$O/bench.json" 2> "$O/bench.err" || tail -5 "$O/bench.err"
 python - <<PY
 import json
 p=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])
