@@ -20,7 +20,7 @@ extern "C" {
 #define MAUA_ENOSYS (-38)
 
 /* ABI version of this header; bumped on any signature change. */
-int maua_abi_version(void);  /* 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
+int maua_abi_version(void);  /* 6: + the structural-segmentation entries (maua_tempogram_f32 ... maua_rec_affinity_f32); 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
 /* Number of compute units / name of device 0 (diagnostics for bench.py). */
 int maua_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
 
@@ -369,6 +369,32 @@ int maua_cqt_mag_f32(const float* y, int64_t n_samples, const float* freqs, cons
 int maua_chroma_cens_f32(const float* ch, float* out, int n_bins, int n_frames, int win_len, void* stream);
 int64_t maua_nn_median_ws_doubles(int n_bins, int n_frames, int k);
 int maua_nn_median_f32(const float* ch, float* out, int n_bins, int n_frames, int k, int width, double* ws, void* stream);
+
+/* Structural segmentation (audioreactive laplacian_segmentation, ABI 6).  Every entry is deterministic run to run.
+ * Tempogram: the onset envelope env[n_frames] padded by win/2 with a linear ramp to 0, framed with hop 1 (n_frames frames), each
+ * frame times a periodic Hann window of win samples, autocorrelated over lags 0 .. win-1 (fp64), divided by its max |.| (unless
+ * that is below FLT_MIN), averaged over frames -> tg[win].  2 <= win <= 1024; ws holds maua_tempogram_ws_doubles() doubles. */
+int64_t maua_tempogram_ws_doubles(int n_frames, int win);
+int maua_tempogram_f32(const float* env, int n_frames, int win, double* ws, float* tg, void* stream);
+/* Beat tracking (librosa.beat's dynamic programme, tightness 100): onset[n_frames] is the normalised envelope; localscore =
+ * onset convolved ('same', zero padding) with exp(-0.5 (j 32 / period)^2), j = -period..period; then, frame by frame,
+ * cumscore[i] = localscore[i] + max over w = -2 period .. -round(period/2) of -100 log(-w/period)^2 (+ cumscore[i + w] when
+ * i + w >= 0), first maximum; backlink[i] = i + w of that maximum, or -1 while no frame has yet reached 0.01 max(localscore).
+ * 2 <= period <= 2000. */
+int maua_beat_track_f64(const double* onset, int n_frames, int period, double* localscore, double* cumscore, int* backlink,
+                        void* stream);
+/* Beat-synchronous aggregation: out[r][s] = np.median (median = 1) or mean (median = 0) of x[r][bounds[s] .. bounds[s+1]) for
+ * x[rows, n_frames]; bounds[n_spans + 1] increasing inside [0, n_frames] (clamped there; an empty span gives NaN).  Spans of any
+ * length. */
+int maua_beat_sync_f32(const float* x, int rows, int n_frames, const int* bounds, int n_spans, int median, float* out, void* stream);
+/* k-nearest-neighbour links of the columns of x[d, s] (d <= 1024, 2 <= s <= 8192): row i links the k columns j with |i - j| >= width
+ * of smallest fp32 Euclidean distance (ties to the lower j); links[i][j] = that distance on a link, -1 elsewhere.  The squares are summed
+ * feature by feature, so the distance of (i, j) and of (j, i) are equal bit for bit. */
+int maua_knn_links_f32(const float* x, int d, int s, int k, int width, float* links, void* stream);
+/* Recurrence affinity from those links (4 <= s <= 8192): rec[i][j] = exp(-dist / bandwidth) where i links j and j links i, 0 elsewhere;
+ * rec_filt = librosa timelag_filter(median_filter, size=(1, 7)) of rec: rec_filt[i][j] = median over s = -3..3 of rec[i - j + j'][j'],
+ * j' = j + s reflected at the edges (d c b a | a b c d), 0 for a row outside [0, s). */
+int maua_rec_affinity_f32(const float* links, int s, float bandwidth, float* rec, float* rec_filt, void* stream);
 
 /* 3-D tileable Perlin noise (audioreactive/latent.py:188-246): grad [r0+1,r1+1,r2+1,3] -> out [n0,n1,n2]. */
 int maua_perlin3d_f32(const float* grad, float* out, int n0, int n1, int n2, int r0, int r1, int r2, void* stream);

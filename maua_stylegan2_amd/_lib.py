@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmaua_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class MauaHipError(RuntimeError):
@@ -113,6 +113,12 @@ _SIGNATURES = {
     "maua_nn_median_ws_doubles": (c_int64, [c_int] * 3),
     "maua_nn_median_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "maua_filterbank_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "maua_tempogram_ws_doubles": (c_int64, [c_int] * 2),
+    "maua_tempogram_f32": (c_int, [_P, c_int, c_int, _P, _P, _P]),
+    "maua_beat_track_f64": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    "maua_beat_sync_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P]),
+    "maua_knn_links_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "maua_rec_affinity_f32": (c_int, [_P, c_int, c_float, _P, _P, _P]),
     "maua_perlin3d_f32": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "maua_affine_reflect_warp_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P]),
     "maua_affine_reflect_warp_mapped_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P, _P]),

@@ -568,7 +568,11 @@ def chroma(audio, sr, n_frames, margin=16, type="cens", notes=12, device=None):
 
 
 def laplacian_segmentation(signal, sr, k=5, plot=False):
-    raise NotImplementedError("laplacian_segmentation is outside the hot path (SURVEY.md §2 row 7: only kelp.py uses it)")
+    """Section start times and labels of a track (Laplacian structural segmentation, reference :159-240); the body is
+    audioreactive/segment.py, whose docstring lists the deliberate differences from the reference."""
+    from .segment import laplacian_segmentation as _segment
+
+    return _segment(signal, sr, k=k, plot=plot)
 
 
 # ------------------------------------------------------------------------------------------------ audio loading
