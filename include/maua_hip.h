@@ -342,6 +342,9 @@ int maua_stft_complex_f32(const float* y, int64_t n_samples, const float* window
                           float* out_im, int n_frames, void* stream);
 int maua_istft_f32(const float* in_re, const float* in_im, const float* window, int n_fft, int hop, int n_frames,
                    float* frames_ws, float* y, int64_t n_samples, void* stream);
+/* Median of a centred window of `size` in {3, 5, 9, 17, 31} taps (MAUA_ENOSYS otherwise) along `axis` of x[rows, cols]: periodic symmetric
+ * reflection (d c b a | a b c d | d c b a), any axis length: scipy.ndimage mode 'reflect', and numpy.pad 'symmetric' where the axis is
+ * shorter than size / 2. */
 int maua_median_filter_f32(const float* x, float* y, int rows, int cols, int size, int axis, void* stream);
 int maua_softmask_apply_f32(const float* re, const float* im, const float* x, const float* x_ref, float margin, float power,
                             int split_zeros, float* out_re, float* out_im, int64_t n, void* stream);
@@ -362,7 +365,8 @@ int maua_cqt_mag_f32(const float* y, int64_t n_samples, const float* freqs, cons
 /* Chroma post-processing for audioreactive/signal.py:102-133 (ch / out are [n_bins <= 32, n_frames], fp32):
  * CENS = per-frame L1 normalisation, 4-level quantisation, Hann smoothing over win_len (odd) frames, L2 normalisation;
  * nn_median = per-frame median over the k frames of highest cosine similarity outside |i-j| < width (the
- * aggregate=np.median, metric="cosine" nearest-neighbour filter at :131).  The fp64 similarity row of a frame lives in LDS
+ * aggregate=np.median, metric="cosine" nearest-neighbour filter at :131; 1 <= k < n_frames; where fewer than k frames are admissible the
+ * excluded ones fill up in index order, every frame at most once).  The fp64 similarity row of a frame lives in LDS
  * while n_frames * 8 + k * (4 + 4 n_bins) bytes fit (~16k frames); longer tracks need a caller-owned workspace `ws` of
  * maua_nn_median_ws_doubles() doubles (0 = not needed, ws may be NULL).  A non-NULL ws of min(n_frames, 1024) * n_frames doubles
  * selects the workspace path at any size (same results, bit for bit). */

@@ -258,8 +258,10 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
     }
 }
 
-// Median of a centred `size`-tap window (size odd, <= 31) along one axis of x[rows, cols]; scipy.ndimage 'reflect'
-// boundary (d c b a | a b c d | d c b a).  Rank counting instead of sorting: branch-free and register resident.
+// Median of a centred `size`-tap window (size odd, <= 31) along one axis of x[rows, cols]; periodic symmetric reflection at
+// the boundary (d c b a | a b c d | d c b a, period 2 * len), any axis length: scipy.ndimage 'reflect' wherever the axis
+// is at least size / 2 long, numpy.pad(mode="symmetric") below that.  Rank counting instead of sorting: branch-free and
+// register resident.
 template <int SIZE>
 __global__ __launch_bounds__(256) void median_filter_kernel(const float* __restrict__ x, float* __restrict__ y, int rows, int cols,
                                                             int axis) {
@@ -496,7 +498,8 @@ __global__ __launch_bounds__(256) void chroma_cens_kernel(const float* __restric
 // Nearest-neighbour median filter (the role of librosa.decompose.nn_filter(S, aggregate=np.median, metric="cosine"),
 // signal.py:131).  One workgroup per frame i: cosine similarity to every frame in fp64 (the neighbour ORDER has to match
 // the float64 oracle), the k best frames outside |i-j| < width by k rounds of block-wide arg-max (ties -> lower index,
-// i.e. a stable descending sort), then a per-feature median over those k frames.
+// i.e. a stable descending sort; with fewer than k admissible frames the excluded ones follow in index order, each frame
+// at most once), then a per-feature median over those k frames.
 // SIMS_IN_LDS: the similarity row of the frame lives in LDS (tracks up to ~16k frames = 6 min at hop 512); otherwise every
 // workgroup owns one row of a caller-provided fp64 workspace [gridDim.x][n_frames] and walks frames i = blockIdx.x,
 // blockIdx.x + gridDim.x, ... — full-length songs keep the reference's semantics instead of skipping the filter.
@@ -553,7 +556,8 @@ __global__ __launch_bounds__(256) void nn_median_kernel(const float* __restrict_
         }
         if (tid == 0) {
             picked[r] = red_i[0];
-            sims[red_i[0]] = -INFINITY;
+            sims[red_i[0]] = NAN;  // taken: never compares greater or equal again (-inf would tie with the EXCLUDED frames, which are
+                                   // picked by index once the admissible ones run out; k < n_frames leaves a candidate in every round)
         }
         __syncthreads();
     }

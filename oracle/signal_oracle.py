@@ -103,13 +103,13 @@ def hann_periodic(n):
     return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
 
 
-def stft_power(y, n_fft=2048, hop=512, power=2.0):
-    """|STFT|**power, centred frames with reflect padding, periodic Hann (librosa.stft defaults).
-    Returns [1 + n_fft/2, n_frames] float64 with n_frames = 1 + len(y)//hop."""
+def stft_power(y, n_fft=2048, hop=512, power=2.0, window=None, n_frames=None):
+    """|STFT|**power, centred frames with reflect padding, periodic Hann (librosa.stft defaults) or ``window`` [n_fft].
+    Returns [1 + n_fft/2, n_frames] float64 with n_frames = 1 + len(y)//hop unless fewer are asked for."""
     y = np.asarray(y, dtype=np.float64)
     ypad = np.pad(y, n_fft // 2, mode="reflect")
-    n_frames = 1 + (len(ypad) - n_fft) // hop
-    win = hann_periodic(n_fft)
+    n_frames = 1 + (len(ypad) - n_fft) // hop if n_frames is None else n_frames
+    win = hann_periodic(n_fft) if window is None else np.asarray(window, dtype=np.float64)
     frames = np.stack([ypad[t * hop: t * hop + n_fft] * win for t in range(n_frames)], axis=1)
     spec = np.fft.rfft(frames, axis=0)
     mag2 = spec.real ** 2 + spec.imag ** 2
@@ -245,21 +245,22 @@ def chroma_stft(y, sr, n_fft=2048, hop=512, tuning=None):
     return raw / np.where(peak > np.finfo(np.float64).tiny, peak, 1.0)
 
 
-def stft_complex(y, n_fft=2048, hop=512):
+def stft_complex(y, n_fft=2048, hop=512, window=None, n_frames=None):
     y = np.asarray(y, dtype=np.float64)
     ypad = np.pad(y, n_fft // 2, mode="reflect")
-    n_frames = 1 + (len(ypad) - n_fft) // hop
-    win = hann_periodic(n_fft)
+    n_frames = 1 + (len(ypad) - n_fft) // hop if n_frames is None else n_frames
+    win = hann_periodic(n_fft) if window is None else np.asarray(window, dtype=np.float64)
     frames = np.stack([ypad[t * hop: t * hop + n_fft] * win for t in range(n_frames)], axis=1)
     return np.fft.rfft(frames, axis=0)
 
 
-def istft(spec, length, n_fft=2048, hop=512):
-    """Window-sum-square normalised overlap-add, centre padding removed (librosa.istft)."""
+def istft(spec, length, n_fft=2048, hop=512, window=None):
+    """Window-sum-square normalised overlap-add, centre padding removed (librosa.istft); samples that no frame reaches
+    (``length`` beyond the frames' cover, gaps when hop > n_fft) are 0."""
     n_frames = spec.shape[1]
-    win = hann_periodic(n_fft)
+    win = hann_periodic(n_fft) if window is None else np.asarray(window, dtype=np.float64)
     frames = np.fft.irfft(spec, n=n_fft, axis=0) * win[:, None]
-    total = n_fft + hop * (n_frames - 1)
+    total = max(n_fft + hop * (n_frames - 1), n_fft // 2 + length)
     y = np.zeros(total)
     wss = np.zeros(total)
     for t in range(n_frames):
@@ -476,14 +477,15 @@ def cens_from_chroma(ch, win_len=41):
     return sm / np.where(l2 > np.finfo(np.float32).tiny, l2, 1.0)
 
 
-def nn_filter_median(ch, width=1):
+def nn_filter_median(ch, width=1, k=None):
     """Nearest-neighbour median filter of a [F, T] feature sequence (the role of librosa.decompose.nn_filter(S,
     aggregate=np.median, metric="cosine") in signal.py:131): for every frame, the k = 2*ceil(sqrt(T - 2*width + 1)) frames
     of highest cosine similarity (frames closer than ``width`` excluded; ties broken toward the lower index) are
     aggregated by the per-feature median.  **parity unpinned.**"""
     ch = np.asarray(ch, dtype=np.float64)
     f, t = ch.shape
-    k = int(min(t - 1, 2 * np.ceil(np.sqrt(max(t - 2 * width + 1, 1)))))
+    if k is None:
+        k = int(min(t - 1, 2 * np.ceil(np.sqrt(max(t - 2 * width + 1, 1)))))
     norms = np.sqrt((ch ** 2).sum(axis=0))
     inv = 1.0 / np.where(norms > np.finfo(np.float32).tiny, norms, 1.0)
     unit = ch * inv

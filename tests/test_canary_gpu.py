@@ -18,59 +18,10 @@ import pytest
 import torch
 
 from maua_stylegan2_amd import _lib, seeding
+from redzone import Guard
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-
-RED = 4096
-CANARY_BITS = 0x7FC0BEEF  # a quiet NaN with a payload nothing computes
-
-
-class Guard:
-    """Windows of exact size between red zones, all in one registry so that one call checks every buffer of a launch."""
-
-    def __init__(self, dev):
-        self.dev = dev
-        self.items = []
-
-    def _alloc(self, n, dtype):
-        assert dtype in (torch.float32, torch.uint8)
-        if dtype == torch.uint8:
-            n_f = (n + 3) // 4
-        else:
-            n_f = n
-        raw = torch.full((RED + n_f + RED,), CANARY_BITS, dtype=torch.int32, device=self.dev)
-        return raw, n_f
-
-    def inp(self, t, name):
-        """A copy of ``t`` (any shape, fp32) in a guarded window."""
-        t = t.to(self.dev, torch.float32).contiguous()
-        raw, n_f = self._alloc(t.numel(), torch.float32)
-        view = raw[RED: RED + n_f].view(torch.float32)
-        view.copy_(t.reshape(-1))
-        self.items.append((name, raw, n_f, False))
-        return view.view(t.shape)
-
-    def out(self, shape, name, dtype=torch.float32):
-        """An output / workspace window, pre-filled with the canary."""
-        n = int(np.prod(shape))
-        raw, n_f = self._alloc(n, dtype)
-        self.items.append((name, raw, n_f, True))
-        if dtype == torch.uint8:
-            return raw[RED: RED + n_f].view(torch.uint8)[:n].view(shape)
-        return raw[RED: RED + n_f].view(torch.float32).view(shape)
-
-    def check(self, written=()):
-        """Red zones intact everywhere; the outputs named in ``written`` hold no canary and only finite values."""
-        torch.cuda.synchronize(self.dev)
-        for name, raw, n_f, is_out in self.items:
-            lo, hi = raw[:RED], raw[RED + n_f:]
-            assert bool((lo == CANARY_BITS).all()), f"{name}: write BELOW the buffer ({int((lo != CANARY_BITS).sum())} dwords)"
-            assert bool((hi == CANARY_BITS).all()), f"{name}: write BEYOND the buffer ({int((hi != CANARY_BITS).sum())} dwords)"
-            if is_out and name in written:
-                body = raw[RED: RED + n_f]
-                assert not bool((body == CANARY_BITS).any()), f"{name}: {int((body == CANARY_BITS).sum())} elements never written"
-                assert bool(torch.isfinite(body.view(torch.float32)).all()), f"{name}: non-finite output (an operand was read outside its buffer?)"
 
 
 def _layer(cin, cout, up, seed, dev):
