@@ -20,7 +20,7 @@ extern "C" {
 #define MAUA_ENOSYS (-38)
 
 /* ABI version of this header; bumped on any signature change. */
-int maua_abi_version(void);  /* 6: + the structural-segmentation entries (maua_tempogram_f32 ... maua_rec_affinity_f32); 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
+int maua_abi_version(void);  /* 7: + maua_randn_frames_f32 (counter-based noise); 6: + the structural-segmentation entries (maua_tempogram_f32 ... maua_rec_affinity_f32); 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
 /* Number of compute units / name of device 0 (diagnostics for bench.py). */
 int maua_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
 
@@ -76,6 +76,33 @@ typedef struct {
 } maua_frame_source_t;
 /* src->frame0 = frame0, asynchronously on `stream` (a 4-byte hipMemsetD32Async: no host buffer has to outlive the call). */
 int maua_frame_source_seek(maua_frame_source_t* src, int frame0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ counter-based noise (ABI 7)
+ * Seeded N(0,1) noise maps for `randomize_noise` (models/stylegan2.py:262-265, render.py:180), generated on the device: the map of
+ * (seed, absolute frame f, slot s) is a pure function, so it is the same for every batch size, lane count and shard of a job, and it
+ * can be produced per replay inside a captured forward instead of living in HBM as a [n_frames, 1, h, w] sequence.  Element e:
+ *   x[0..3] = Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with
+ *             key = (seed low word, seed high word) and counter = (e / 4, f, s, 0);
+ *   u(x)    = ((x >> 9) + 0.5) * 2^-23      — 24 significant bits: exact in fp32, never 0 or 1, so |z| <= sqrt(48 ln 2) = 5.768;
+ *   Box-Muller: element 4i = r cos(2 pi u(x[1])), 4i+1 = r sin(2 pi u(x[1])) with r = sqrt(-2 ln u(x[0])); 4i+2, 4i+3 the same from
+ *             (x[2], x[3]).  A map whose hw is not a multiple of 4 drops the surplus values.
+ * One launch fills the [batch, hw] maps of all `n_slots` table entries (the table lives in DEVICE memory; an entry with dst == NULL or
+ * hw < 1 is skipped); frame of sample b:
+ *   src == NULL: frame0 + b;
+ *   src != NULL: frame0 + src->frame0 + b, read on the device, so that one captured launch serves every replay.  `frame0` is then the
+ *             absolute frame at which the sequences behind `src` start: 0, unless the caller holds one shard of a job's frames.
+ *             The same launch points the frame source at the generated maps, for every entry with slot in 0 .. MAUA_MAX_NOISE_SLOTS-1:
+ *               src->noise[slot] = dst - src->frame0 * hw,  src->noise_stride[slot] = hw
+ *             (the layers, later on the same stream, read noise[slot] + (src->frame0 + b) * noise_stride[slot] = dst + b * hw; the
+ *             biased pointer itself is never dereferenced).
+ * MAUA_EINVAL: table == NULL, n_slots outside 1 .. MAUA_MAX_NOISE_SLOTS, batch < 1, frame0 < 0. */
+typedef struct {
+    float* dst;     /* [batch, hw] */
+    int32_t hw;     /* floats per map */
+    int32_t slot;   /* third counter word; with src also the noise slot of the frame source */
+} maua_randn_slot_t;
+int maua_randn_frames_f32(const maua_randn_slot_t* table, int n_slots, int batch, uint64_t seed, int frame0, maua_frame_source_t* src,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------ generator layers
  * THE STYLE FOLD (ABI 4).  ModulatedConv2d multiplies its input by the per-sample styles before the shared-weight contraction

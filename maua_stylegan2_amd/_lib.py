@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmaua_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class MauaHipError(RuntimeError):
@@ -51,6 +51,12 @@ class FrameSource(ctypes.Structure):
     ]
 
 
+class RandnSlot(ctypes.Structure):
+    """maua_randn_slot_t (include/maua_hip.h): one generated noise map sequence of a maua_randn_frames_f32 launch."""
+
+    _fields_ = [("dst", c_void_p), ("hw", ctypes.c_int32), ("slot", ctypes.c_int32)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "maua_abi_version": (c_int, []),
@@ -62,6 +68,7 @@ _SIGNATURES = {
     "maua_upfirdn2d_f16": (c_int, [_P, _P, _P] + [c_int] * 14 + [_P]),
     "maua_upfirdn2d_f64": (c_int, [_P, _P, _P] + [c_int] * 14 + [_P]),
     "maua_frame_source_seek": (c_int, [_P, c_int, _P]),
+    "maua_randn_frames_f32": (c_int, [_P, c_int, c_int, ctypes.c_uint64, c_int, _P, _P]),
     "maua_blur_noise_act_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, c_int64, _P, _P, _P, c_int, _P, c_int, _P]),
     "maua_upconv_blur_ok": (c_int, [c_int] * 4),
     "maua_upconv_blur_ws_floats": (c_int64, [c_int] * 5),

@@ -323,6 +323,23 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         stem = lambda path: str(path).split("/")[-1].split(".")[0].lower()  # noqa: E731
         output_file = f"{output_dir}/{stem(audio_file)}_{stem(ckpt)}_{uuid.uuid4().hex[:8]}.mp4"
     t0 = time.time()
+    if grouped and hasattr(generator, "random_noise"):
+        # randomize_noise: every rank generates the maps of its frames from the job's one broadcast seed (Generator.random_noise)
+        generator.noise_seed = seed + 3
+    try:
+        written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
+                          output_file, randomize_noise, ffmpeg_preset, shard)
+    finally:
+        if grouped and hasattr(generator, "random_noise"):
+            generator.noise_seed = None  # the generator is cached across jobs
+    dt = max(time.time() - t0, 1e-9)
+    print(f"\nrendered {written} frames in {dt:.2f}s ({written / dt:.1f} frames/s)")
+    print(f"total time taken: {(time.time() - started) / 60:.2f} minutes")
+    return output_file
+
+
+def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
+            randomize_noise, ffmpeg_preset, shard):
     if shard is None:
         written = render.render(generator=generator, latents=latents, noise=noise, audio_file=audio_file, offset=offset,
                                 duration=duration, batch_size=batch, truncation=truncation, bends=bends, rewrites=rewrites,
@@ -331,10 +348,7 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     else:  # one process per GPU: the per-frame inputs were scattered, this rank holds frames [lo, hi) only
         written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
                                       truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard)
-    dt = max(time.time() - t0, 1e-9)
-    print(f"\nrendered {written} frames in {dt:.2f}s ({written / dt:.1f} frames/s)")
-    print(f"total time taken: {(time.time() - started) / 60:.2f} minutes")
-    return output_file
+    return written
 
 
 def load_plugin(audioreactive_file):

@@ -746,6 +746,11 @@ class Generator(nn.Module):
     tap_float_image = False
     # the style fold (include/maua_hip.h THE STYLE FOLD; A/B switch): producers store their map multiplied by the consumer's styles
     style_fold = True
+    # seed of the counter-based noise of a randomised render (render.synthesize, ``random_noise``); None: one draw from torch's CPU
+    # generator per render.  ``noise_frame_offset``: absolute index of frame 0 of the sequences a render is given (a rank that holds one
+    # shard of a job's frames: render.render_shard sets it), so that frame n of the job gets the same maps on whichever rank.
+    noise_seed = None
+    noise_frame_offset = 0
 
     def _build(self, size, style_dim, n_mlp, channel_multiplier, blur_kernel, lr_mlp, constant_input, min_rgb_size):
         self.size = size
@@ -1113,20 +1118,58 @@ class Generator(nn.Module):
         m.last_path = "const"
         return out
 
+    # ------------------------------------------------------------------ counter-based noise
+    def _randn_table(self, slots, maps):
+        """Device table of maua_randn_slot_t (include/maua_hip.h) for ``maps[k]`` = the [batch, 1, h, w] destination of slot ``slots[k]``."""
+        host = (_lib.RandnSlot * len(slots))()
+        for entry, i, t in zip(host, slots, maps):
+            entry.dst, entry.hw, entry.slot = t.data_ptr(), int(t.shape[-2]) * int(t.shape[-1]), int(i)
+        return th.frombuffer(bytearray(bytes(host)), dtype=th.uint8).to(self.input.input.device)
+
+    def _noise_slots(self, slots):
+        slots = list(range(self.num_layers)) if slots is None else [int(i) for i in slots]
+        if not slots or len(set(slots)) != len(slots) or min(slots) < 0 or max(slots) >= min(self.num_layers, _lib.MAX_NOISE_SLOTS):
+            raise RuntimeError(f"noise slots {slots} are not distinct indices below {min(self.num_layers, _lib.MAX_NOISE_SLOTS)}")
+        return slots
+
+    def random_noise(self, frame0, batch, seed, slots=None):
+        """Seeded N(0,1) noise maps of frames [frame0, frame0 + batch) for ``slots`` (default: every noise layer): a list of
+        [batch, 1, h, w] device tensors, one launch of maua_randn_frames_f32.  The map of (seed, frame, slot) is a pure function
+        (Philox4x32-10 + Box-Muller, include/maua_hip.h): the same whatever batch it is produced in, and the same a captured forward
+        with ``random_slots`` generates for itself."""
+        dev = self.input.input.device
+        if dev.type != "cuda":
+            raise RuntimeError("Generator must live on a HIP device (.cuda()); the MI355X path has no CPU fallback")
+        slots = self._noise_slots(slots)
+        frame0, batch, seed = int(frame0), int(batch), int(seed)
+        if frame0 < 0 or batch < 1 or frame0 + batch > 2 ** 31 or not 0 <= seed < 2 ** 64:
+            raise RuntimeError(f"random_noise: frames [{frame0}, {frame0 + batch}) / seed {seed} out of range")
+        with th.cuda.device(dev):
+            maps = [th.empty((batch, 1) + tuple(getattr(self.noises, f"noise_{i}").shape[-2:]), dtype=th.float32, device=dev) for i in slots]
+            table = self._randn_table(slots, maps)
+            _lib.check(_lib.load().maua_randn_frames_f32(table.data_ptr(), len(slots), batch, seed, frame0, None, _lib.stream_ptr(dev)),
+                       "maua_randn_frames_f32")
+            table.record_stream(th.cuda.current_stream(dev))
+        return maps
+
     # ------------------------------------------------------------------ hipGraph
     def weights_key(self):
         """Identity of everything a captured graph has baked in as pointers: parameters and buffers (a swapped or in-place
         modified tensor invalidates the packed weights, style tables and therefore the graph)."""
         return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
 
-    def capture_graph(self, batch, lane=0, frames_u8=False, bends=()):
+    def capture_graph(self, batch, lane=0, frames_u8=False, bends=(), random_slots=(), noise_seed=0, noise_frame_offset=0):
         """Capture one forward of ``batch`` frames into a hipGraph and return its ``GraphLane``.  The captured kernels read
         their per-frame inputs (latents, truncation, noise maps, bend parameters) THROUGH a frame source in device memory
         (include/maua_hip.h): ``lane.bind(latents, noise, truncation)`` points it at sequences resident in HBM — any render,
         any mix of per-frame maps and checkpoint noise buffers — and ``lane.replay(frame0)`` moves only the frame index, so a
         graph is captured once per (batch, lane, bend set) and outlives the render (the reference re-uploads every slice per
         batch, render.py:140-149).  ``bends``: [{"layer", "transform"}] whose transforms implement ``run_static`` (audioreactive
-        /bend.py).  Lanes share the weights but no activation buffer: they may be replayed concurrently on different streams."""
+        /bend.py).  Lanes share the weights but no activation buffer: they may be replayed concurrently on different streams.
+        ``random_slots``: noise slots whose maps the captured forward GENERATES per replay (``randomize_noise``): it then starts with one
+        maua_randn_frames_f32 launch that fills lane-private [batch, 1, h, w] buffers with the maps of (``noise_seed``, frame
+        ``noise_frame_offset`` + frame0 + b, slot) — what ``random_noise`` returns for those frames — and points the frame source at them;
+        ``bind`` takes None for these slots.  Seed and offset are kernel arguments: part of the graph."""
         dev = self.input.input.device
         if th.cuda.current_stream(dev).cuda_stream == 0:
             raise RuntimeError("capture_graph must run on a non-default stream (with torch.cuda.stream(s): ...): HIP cannot "
@@ -1139,19 +1182,33 @@ class Generator(nn.Module):
         self._captured = True
         try:
             with th.cuda.device(dev):
-                source = FrameSource(self, batch, lane)
+                random_slots = tuple(self._noise_slots(random_slots)) if len(random_slots) else ()
+                generated = {i: self._buf(batch, f"g.randn_{i}", (batch, 1) + tuple(getattr(self.noises, f"noise_{i}").shape[-2:]))
+                             for i in random_slots}
+                source = FrameSource(self, batch, lane, generated)
+                randn_table = self._randn_table(random_slots, [generated[i] for i in random_slots]) if random_slots else None
                 u8 = None
                 if frames_u8:
                     hw = getattr(self.noises, f"noise_{self.num_layers - 1}").shape[-2:]
                     u8 = self._buf(batch, "g.frames_u8", (batch, int(hw[0]), int(hw[1]), 3), dtype=th.uint8)
                 tl = self._buf(0, "g.trunc_latent", (self.style_dim,))
-                run = lambda: self._forward_device(None, None, None, tl, bends, frames_u8=u8, src=source.ptr, batch=batch)  # noqa: E731
+
+                def run():
+                    if randn_table is not None:  # first launch of the forward: the layers below read the maps through the frame source
+                        _lib.check(_lib.load().maua_randn_frames_f32(randn_table.data_ptr(), len(random_slots), batch, int(noise_seed),
+                                                                     int(noise_frame_offset), source.ptr, _lib.stream_ptr(dev)),
+                                   "maua_randn_frames_f32")
+                    return self._forward_device(None, None, None, tl, bends, frames_u8=u8, src=source.ptr, batch=batch)
+
                 run()  # warm-up: allocates every static buffer, packs the weights
                 th.cuda.synchronize(dev)
                 graph = _lib.HipGraph()
                 with graph:
                     image, _, _ = run()
-            return GraphLane(self, graph, source, image, u8, tl, batch, lane, self.weights_key())
+            lane_ = GraphLane(self, graph, source, image, u8, tl, batch, lane, self.weights_key())
+            lane_.random_slots, lane_.noise_seed, lane_.noise_frame_offset = random_slots, int(noise_seed), int(noise_frame_offset)
+            lane_._randn_table = randn_table  # the captured launch reads it on every replay
+            return lane_
         finally:
             self._lane = 0
 
@@ -1160,9 +1217,12 @@ class FrameSource:
     """Host handle of a maua_frame_source_t in device memory (include/maua_hip.h): the pointers of the HBM-resident per-frame
     sequences a captured forward reads, plus the frame it starts at."""
 
-    def __init__(self, generator, batch, lane):
+    def __init__(self, generator, batch, lane, generated=None):
         self.generator = generator
         self.batch = batch
+        # slot -> lane-private [batch, 1, h, w] buffer the captured forward fills itself (capture_graph's random_slots); its first launch
+        # rewrites the slot's pointer / stride on every replay, so what ``bind`` leaves there is never read: one valid map, stride 0
+        self.generated = dict(generated or {})
         dev = generator.input.input.device
         self.dev = generator._buf(batch, "g.frame_source", (ctypes.sizeof(_lib.FrameSource),), dtype=th.uint8)
         self.ptr = self.dev.data_ptr()
@@ -1200,6 +1260,12 @@ class FrameSource:
         if len(noise) != g.num_layers or g.num_layers > _lib.MAX_NOISE_SLOTS:
             raise RuntimeError(f"{len(noise)} noise entries for {g.num_layers} layers")
         for i, nz in enumerate(noise):
+            if i in self.generated:
+                if nz is not None:
+                    raise RuntimeError(f"noise[{i}] is generated by this lane (random_slots): bind it as None")
+                host.noise[i] = self.generated[i].data_ptr()
+                host.noise_stride[i] = 0
+                continue
             if nz is None:
                 nz = getattr(g.noises, f"noise_{i}")
             nz = _lib.require_cuda(nz.to(dev), f"noise[{i}]")
@@ -1237,6 +1303,7 @@ class GraphLane:
         self.image, self.u8, self.batch, self.lane = image, u8, batch, lane
         self._trunc_latent = trunc_latent
         self.weights_key = weights_key
+        self.random_slots, self.noise_seed, self.noise_frame_offset = (), 0, 0
 
     def bind(self, latents, noise, truncation=None):
         """Point the lane at the sequences of a render (see FrameSource.bind).  ``truncation`` [n_frames] switches the

@@ -265,28 +265,40 @@ def _lane_stream(dev, k):
     return stream
 
 
-def graph_lanes(generator, batch_size, n_lanes, bends=()):
+UNSEEDED_GRAPH_MIN_FRAMES = 2048  # randomised renders without generator.noise_seed below this length keep the eager path (synthesize)
+
+
+def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None):
     """``n_lanes`` captured forwards (GraphLane) of ``batch_size`` frames with uint8 frame output, each on its own stream.
     Without bends they are cached on the generator and reused by every later render (a captured forward reads its inputs
     through a frame source, so nothing about a particular render is baked in); a changed weight drops the cache.  With bends the
-    transforms' static operands are part of the graph: captured per call."""
+    transforms' static operands are part of the graph: captured per call.  ``random`` = (slots, seed, frame offset): lanes that generate
+    the noise maps of ``slots`` themselves (``Generator.capture_graph``'s random_slots); cached per slot set next to the static lanes, and
+    captured again when the seed or the offset — kernel arguments of the captured noise launch — differ from the cached lane's."""
     dev = device_of(generator)
+    slots, seed, offset = random if random else ((), 0, 0)
+    slots = tuple(slots)
     key = generator.weights_key()
     cache = generator.__dict__.setdefault("_graph_lanes", {})
     lanes = []
     tap = bool(getattr(generator, "tap_float_image", False))  # (parity tests: such lanes also write the fp32 image — other kernels arguments)
     for k in range(n_lanes):
         stream = _lane_stream(dev, k)
-        lane = None if bends else cache.get((batch_size, k, tap))
-        if lane is not None and lane.weights_key != key:
+        cache_key = (batch_size, k, tap) + ((slots,) if slots else ())
+        lane = None if bends else cache.get(cache_key)
+        if lane is not None and (lane.weights_key != key or (slots and (lane.noise_seed, lane.noise_frame_offset) != (seed, offset))):
             lane = None
         if lane is None:
             stream.wait_stream(th.cuda.current_stream(dev))
             with th.cuda.stream(stream):
-                lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends)
+                if slots:
+                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, random_slots=slots, noise_seed=seed,
+                                                   noise_frame_offset=offset)
+                else:
+                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends)
             stream.synchronize()
             if not bends:
-                cache[(batch_size, k, tap)] = lane
+                cache[cache_key] = lane
         lanes.append((stream, lane))
     return lanes
 
@@ -364,7 +376,23 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
             raise KeyError(f"get_rewrites: generator has no parameter {name!r}")
         rewrites[name] = [rewrite, modulation.to(dev, th.float32).contiguous()]
         original_weights[name] = param_dict[name].detach().clone()
-    capturable = use_graph and not rewrites and not randomize_noise and hasattr(generator, "capture_graph")
+    # randomize_noise (reference models/stylegan2.py:262-265: fresh N(0,1) maps for the slots whose entry in `noise` is None): the map of
+    # (seed, frame, slot) is a pure function (Generator.random_noise), generated inside the captured forward by the graph lanes and by one
+    # launch per batch on the eager path, so every frame gets the same maps whichever path, batch size, lane or shard produces it.
+    # Generators without `random_noise` (StyleGAN1) keep torch's generator on the eager path.
+    random = None
+    if randomize_noise and hasattr(generator, "random_noise"):
+        slots = tuple(i for i, nz in enumerate(noise) if nz is None)
+        seed = getattr(generator, "noise_seed", None)
+        if seed is None:  # one draw per render from torch's CPU generator: torch.manual_seed makes a job repeatable
+            seed = int(th.randint(0, 2 ** 63 - 1, (1,), dtype=th.int64).item())
+        if slots:
+            random = (slots, int(seed), int(getattr(generator, "noise_frame_offset", 0)))
+    capturable = use_graph and not rewrites and hasattr(generator, "capture_graph") and (not randomize_noise or hasattr(generator, "random_noise"))
+    if random is not None and getattr(generator, "noise_seed", None) is None and hi - lo < UNSEEDED_GRAPH_MIN_FRAMES:
+        # the seed is an argument of the captured noise launch: a fresh seed per render means capturing the lanes again (~25 ms measured,
+        # profiles/randnoise.md), more than the eager path costs such a render (~0.1 ms per batch).  Same maps, same frames either way.
+        capturable = False
     seq_bends = []
     if capturable and bends:
         seq_bends, capturable = _sequence_bends(bends, n_total) if getattr(generator, "capturable_bends", True) else (None, False)
@@ -372,7 +400,7 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
     caller_stream = th.cuda.current_stream(dev)
     lane_state = []  # (stream, GraphLane or None)
     if capturable and hi - lo >= batch_size:
-        lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends)
+        lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random)
         n_lanes = len(lane_state)
         for stream, lane in lane_state:
             lane.bind(latents, noise, trunc_t)  # once per render: the pointers of the HBM-resident sequences
@@ -397,6 +425,9 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
                     k += 1
                     continue
                 noise_batch = [None if nz is None else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in noise]  # [1, ...] = one map for every frame
+                if random is not None:  # the same maps a graph lane generates for these frames
+                    for i, nz in zip(random[0], generator.random_noise(random[2] + n, b, random[1], random[0])):
+                        noise_batch[i] = nz
                 bend_batch = []
                 for bend in bends:
                     if "modulation" in bend:
@@ -463,6 +494,10 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     else:
         lo, hi, n_frames = _shard
         frame_range = (0, hi - lo)
+    # the sequences of a scattered shard start at the job's frame `lo`: seeded noise is a function of the absolute frame
+    shifted = _shard is not None and hasattr(generator, "random_noise")
+    if shifted:
+        generator.noise_frame_offset = lo
     dev = device_of(generator)
     sink = None
     if rank == 0:
@@ -595,6 +630,8 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
             worker.close()
     finally:  # the encoder process / output file must not outlive a failed render
         parked.__exit__(None, None, None)
+        if shifted:
+            generator.noise_frame_offset = 0
         if worker is not None:
             try:
                 worker.close()  # (also: every ring slot has been written before the rings are handed to the next render)
