@@ -16,6 +16,7 @@ its first call and can be captured into a hipGraph (``capture_graph``).  There i
 """
 import ctypes
 import math
+from types import SimpleNamespace
 
 import torch as th
 from torch import nn
@@ -113,6 +114,27 @@ def _style_table(entries, device):
     return raw.to(device)
 
 
+def _round_up(n, multiple):
+    return (n + multiple - 1) // multiple * multiple
+
+
+def _noise_stride(noise):
+    """Batch stride (floats) of a [B or 1, 1, oh, ow] noise map as the kernels take it: 0 = one map shared by the batch (or no map)."""
+    return 0 if noise is None or noise.shape[0] == 1 else noise.shape[-1] * noise.shape[-2]
+
+
+def _checked_noise(noise, batch, oh, ow, src):
+    """(noise map or None, its batch stride) for a layer that stores [batch, *, oh, ow]; ``noise`` is ignored with a frame source ``src``."""
+    if src is not None or noise is None:
+        return None, 0
+    noise = _lib.require_cuda(noise, "noise")
+    # the kernels read oh*ow floats per sample (batch samples unless the map is shared): a wrongly sized map would be
+    # a silent out-of-bounds read where the reference raises a broadcast error (models/stylegan2.py:266)
+    if noise.dim() != 4 or noise.shape[1] != 1 or tuple(noise.shape[-2:]) != (oh, ow) or noise.shape[0] not in (1, batch):
+        raise RuntimeError(f"noise {tuple(noise.shape)} does not match feature map [{batch}, 1, {oh}, {ow}] (batch must be 1 or {batch})")
+    return noise, _noise_stride(noise)  # (require_cuda made it contiguous)
+
+
 class ModulatedConv2d(nn.Module):
     """reference :164-254.  ``forward(inputs, style)`` keeps the reference contract; the generator calls
     ``run(...)`` with styles / demod factors already computed for all layers."""
@@ -154,7 +176,7 @@ class ModulatedConv2d(nn.Module):
         if self._packed is None or self._packed[0] != key:
             wd = _lib.require_cuda(w.detach(), "weight")
             k2 = self.kernel_size ** 2
-            cpad = (self.out_channel + 31) // 32 * 32
+            cpad = _round_up(self.out_channel, 32)
             wp = th.empty((k2, self.in_channel, cpad), dtype=th.float32, device=w.device) if k2 == 9 else None
             wsq = th.empty((self.out_channel, self.in_channel), dtype=th.float32, device=w.device)
             with th.cuda.device(w.device):
@@ -244,55 +266,40 @@ class ModulatedConv2d(nn.Module):
             self.__dict__["_blur_sep"] = cached = (key, ok)
         return cached[1]
 
+    # packed_wino: mode -> (pack entry, shape of the packed buffer for a layer ``m``, dtype).  Modes 2 / 3 above 32 channels: columns
+    # padded to 64 and interleaved [lane][m-tile] (see pack_weight_wino_kernel), else padded to 32.
+    _WINO_PACKS = {
+        2: ("maua_pack_weight_wino_f32", lambda m: (12, m.in_channel, _round_up(m.out_channel, 64 if m.out_channel > 32 else 32)), th.float32),
+        3: ("maua_pack_weight_wino43_f32", lambda m: (18, m.in_channel, _round_up(m.out_channel, 64 if m.out_channel > 32 else 32)), th.float32),
+        4: ("maua_pack_weight_upwino_f32", lambda m: (12, m.in_channel, _round_up(m.out_channel, 32)), th.float32),
+        5: ("maua_pack_weight_wino2d_f32", lambda m: (24 * m.in_channel * m.out_channel,), th.float32),
+        6: ("maua_pack_weight_up2d_f32", lambda m: (_lib.load().maua_pack_weight_up2d_floats(m.out_channel, m.in_channel),), th.float32),
+        7: ("maua_pack_weight_sbf16_f32", lambda m: (_lib.load().maua_pack_weight_sbf16_bytes(m.out_channel, m.in_channel),), th.uint8),
+    }
+
     def packed_wino(self, mode=2):
-        """Winograd-domain weight [(ky*F+xi), Cin, Cout_pad], F = 4 for mode 2 (maua_pack_weight_wino_f32) and mode 4
-        (maua_pack_weight_upwino_f32), 6 for mode 3 (maua_pack_weight_wino43_f32); cached like ``packed()``."""
+        """Weight in the form the kernel of ``mode`` reads (``_WINO_PACKS``): Winograd-domain [(ky*F+xi), Cin, Cout_pad] with F = 4 for
+        modes 2 and 4, 6 for mode 3; the layouts of csrc/modconv_w2d.hip (5), modconv_up2d.hip (6), modconv_sbf16.hip (7 / 8).  Cached like
+        ``packed()``."""
         self.packed()  # refreshes / invalidates on weight change
         if self._packed_wino is None:
             self._packed_wino = {}
-        if mode == 6 and mode not in self._packed_wino:
-            w = self.weight
-            wd = _lib.require_cuda(w.detach(), "weight")
-            wq = th.empty(_lib.load().maua_pack_weight_up2d_floats(self.out_channel, self.in_channel), dtype=th.float32,
-                          device=w.device)
-            with th.cuda.device(w.device):
-                _lib.check(_lib.load().maua_pack_weight_up2d_f32(wd.data_ptr(), wq.data_ptr(), self.out_channel,
-                                                                 self.in_channel, _lib.stream_ptr(w.device)),
-                           "maua_pack_weight_up2d_f32")
-            self._packed_wino[mode] = wq
         if mode == 8:
             mode = 7  # (one packed weight serves the plain and the transposed form)
-        if mode == 7 and mode not in self._packed_wino:
-            w = self.weight
-            wd = _lib.require_cuda(w.detach(), "weight")
-            wq = th.empty(_lib.load().maua_pack_weight_sbf16_bytes(self.out_channel, self.in_channel), dtype=th.uint8, device=w.device)
-            with th.cuda.device(w.device):
-                _lib.check(_lib.load().maua_pack_weight_sbf16_f32(wd.data_ptr(), wq.data_ptr(), self.out_channel, self.in_channel,
-                                                                  _lib.stream_ptr(w.device)), "maua_pack_weight_sbf16_f32")
-            self._packed_wino[mode] = wq
-        if mode == 5 and mode not in self._packed_wino:
-            w = self.weight
-            wd = _lib.require_cuda(w.detach(), "weight")
-            wq = th.empty(24 * self.in_channel * self.out_channel, dtype=th.float32, device=w.device)
-            with th.cuda.device(w.device):
-                _lib.check(_lib.load().maua_pack_weight_wino2d_f32(wd.data_ptr(), wq.data_ptr(), self.out_channel,
-                                                                   self.in_channel, _lib.stream_ptr(w.device)),
-                           "maua_pack_weight_wino2d_f32")
-            self._packed_wino[mode] = wq
         if mode not in self._packed_wino:
+            fn, shape, dtype = self._WINO_PACKS[mode]
             w = self.weight
             wd = _lib.require_cuda(w.detach(), "weight")
-            # modes 2 / 3 above 32 channels: columns padded to 64 and interleaved [lane][m-tile] (see pack_weight_wino_kernel)
-            pad = 64 if (mode in (2, 3) and self.out_channel > 32) else 32
-            cpad = (self.out_channel + pad - 1) // pad * pad
-            wq = th.empty((18 if mode == 3 else 12, self.in_channel, cpad), dtype=th.float32, device=w.device)
-            fn = {2: "maua_pack_weight_wino_f32", 3: "maua_pack_weight_wino43_f32", 4: "maua_pack_weight_upwino_f32"}[mode]
+            wq = th.empty(shape(self), dtype=dtype, device=w.device)
             with th.cuda.device(w.device):
-                rc = getattr(_lib.load(), fn)(wd.data_ptr(), wq.data_ptr(), self.out_channel, self.in_channel,
-                                              _lib.stream_ptr(w.device))
+                rc = getattr(_lib.load(), fn)(wd.data_ptr(), wq.data_ptr(), self.out_channel, self.in_channel, _lib.stream_ptr(w.device))
             _lib.check(rc, fn)
             self._packed_wino[mode] = wq
         return self._packed_wino[mode]
+
+    def weight_for(self, mode):
+        """The packed weight the kernel of ``mode`` reads: tap-major for the direct and polyphase kernels (0, 1), ``packed_wino`` above."""
+        return self.packed_wino(mode) if mode >= 2 else self.packed()[0]
 
     def table_entry(self, lat_idx, s_off, d_off):
         wp, wsq = self.packed()
@@ -300,47 +307,35 @@ class ModulatedConv2d(nn.Module):
                     cin=self.in_channel, cout=self.out_channel, lat_idx=lat_idx, s_off=s_off, d_off=d_off,
                     wscale=self.scale)
 
-    def run(self, x, s, s_off, d, out, ws, fuse_act=False, noise=None, noise_w=None, bias=None, src=None, slot=0, prescaled=False):
+    def run(self, x, s, s_off, d, out, ws, fuse_act=False, noise=None, noise_w=None, bias=None, src=None, slot=0, prescaled=False, mode=None):
         """3x3 only. x [B,Cin,H,W]; s [B,S] (this layer's slice at s_off); d [B,Cout] or None.
         Writes ``out`` ([B,Cout,H,W] or [B,Cout,2H+1,2W+1] when upsample).  ``src`` (device pointer of a frame source,
         include/maua_hip.h): the noise map comes from its slot ``slot`` instead of ``noise``.  ``prescaled``: x arrives multiplied by
-        this layer's styles (the style fold, include/maua_hip.h; modes 5 and 6 only)."""
+        this layer's styles (the style fold, include/maua_hip.h; modes 5 and 6 only).  ``mode``: ``conv_mode(H, W)``, if the caller has it."""
         lib = _lib.load()
         b, cin, h, w = x.shape
-        mode = self.conv_mode(h, w)
-        wp = self.packed_wino(mode) if mode >= 2 else self.packed()[0]
-        nstride = 0 if noise is None or noise.shape[0] == 1 else noise.shape[-1] * noise.shape[-2]
+        if mode is None:
+            mode = self.conv_mode(h, w)
         rc = lib.maua_modconv3x3_f32(
-            x.data_ptr(), wp.data_ptr(), None if prescaled else s.data_ptr() + 4 * s_off, s.shape[1], _lib.ptr(d), out.data_ptr(), b, cin,
-            self.out_channel, h, w, mode, float(self.scale), int(fuse_act), _lib.ptr(noise), nstride,
+            x.data_ptr(), self.weight_for(mode).data_ptr(), None if prescaled else s.data_ptr() + 4 * s_off, s.shape[1], _lib.ptr(d),
+            out.data_ptr(), b, cin, self.out_channel, h, w, mode, float(self.scale), int(fuse_act), _lib.ptr(noise), _noise_stride(noise),
             _lib.ptr(noise_w), _lib.ptr(bias), _lib.ptr(ws), src if fuse_act else None, slot, _lib.stream_ptr(x.device),
         )
         _lib.check(rc, "maua_modconv3x3_f32")
         return out
 
     def forward(self, inputs, style):
-        x = _lib.require_cuda(inputs, "inputs")
-        style = _lib.require_cuda(style, "style")
+        x, s, d = _layer_styles(self, inputs, style)
         b, cin, h, w = x.shape
         dev = x.device
         lib = _lib.load()
         with th.cuda.device(dev):
-            s = th.empty((b, cin), dtype=th.float32, device=dev)
-            d = th.empty((b, self.out_channel), dtype=th.float32, device=dev) if self.demodulate else None
-            table = _style_table([self.table_entry(0, 0, 0)], dev)
-            lat = style.reshape(b, 1, -1)
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.maua_style_affine_f32(lat.data_ptr(), b, 1, lat.shape[-1], None, None, table.data_ptr(), 1,
-                                                 cin, s.data_ptr(), cin, None, st), "maua_style_affine_f32")
-            if d is not None:
-                _lib.check(lib.maua_demod_f32(table.data_ptr(), 1, self.out_channel, s.data_ptr(), cin, d.data_ptr(), b,
-                                              st), "maua_demod_f32")
             if self.kernel_size == 1:
                 if self.out_channel != 3 or self.demodulate:
                     raise NotImplementedError("1x1 modulated conv is only built for ToRGB (3 channels, no demodulation)")
                 out = th.empty((b, 3, h, w), dtype=th.float32, device=dev)
                 _lib.check(lib.maua_torgb_f32(x.data_ptr(), self.weight.data_ptr(), s.data_ptr(), cin, None, None, None,
-                                              out.data_ptr(), b, cin, h, w, float(self.scale), st), "maua_torgb_f32")
+                                              out.data_ptr(), b, cin, h, w, float(self.scale), _lib.stream_ptr(dev)), "maua_torgb_f32")
                 return out
             oh, ow = (2 * h + 1, 2 * w + 1) if self.upsample else (h, w)
             out = th.empty((b, self.out_channel, oh, ow), dtype=th.float32, device=dev)
@@ -350,6 +345,26 @@ class ModulatedConv2d(nn.Module):
             if self.upsample:
                 out = self.blur(out)
         return out
+
+
+def _layer_styles(conv, inputs, style):
+    """(checked inputs, s [batch, Cin], d [batch, Cout] or None when ``conv`` does not demodulate) of ONE ModulatedConv2d for ``style``
+    [batch, style_dim]: the one-entry form of the generator's style table, for the standalone ``forward`` of the layer classes."""
+    lib = _lib.load()
+    x, style = _lib.require_cuda(inputs, "inputs"), _lib.require_cuda(style, "style")
+    batch, dev = x.shape[0], x.device
+    cin, cout = conv.in_channel, conv.out_channel
+    s = th.empty((batch, cin), dtype=th.float32, device=dev)
+    d = th.empty((batch, cout), dtype=th.float32, device=dev) if conv.demodulate else None
+    with th.cuda.device(dev):
+        table = _style_table([conv.table_entry(0, 0, 0)], dev)
+        lat = style.reshape(batch, 1, -1)
+        st = _lib.stream_ptr(dev)
+        _lib.check(lib.maua_style_affine_f32(lat.data_ptr(), batch, 1, lat.shape[-1], None, None, table.data_ptr(), 1, cin, s.data_ptr(), cin,
+                                             None, st), "maua_style_affine_f32")
+        if d is not None:
+            _lib.check(lib.maua_demod_f32(table.data_ptr(), 1, cout, s.data_ptr(), cin, d.data_ptr(), batch, st), "maua_demod_f32")
+    return x, s, d
 
 
 class NoiseInjection(nn.Module):
@@ -477,184 +492,186 @@ class StyledConv(nn.Module):
         fold, include/maua_hip.h: the 2-D Winograd kernels, mode 5, and the F(2,2)^2 transposed kernel, mode 6, fused with its blur or not)."""
         return self.conv.conv_mode(h, w) in (5, 6)
 
+    # what the last call of ``run`` did: its path ("torgb", "rgb_partial", "lowres", "plain" on a plain layer, "fused", "lowres", "pair" on an
+    # up-sampling one, "const" for conv1 through Generator._run_const_conv) and whether the map it stored carries the consumer's styles
+    last_path = None
+    posted = False
+
+    def _took(self, path, out, posted=False, rgb=None, u8_done=True):
+        """The one place where a call reports what it did: every exit of ``run`` (and of Generator._run_const_conv) returns through here.
+        ``rgb``: the offer that was taken; ``u8_done`` False: its image is in rgb["out"] as fp32 planes (a last layer still needs the frame epilogue)."""
+        self.last_path, self.posted = path, posted
+        if rgb is not None:
+            rgb["done"] = True
+            if not u8_done:
+                rgb["u8_done"] = False
+        return out
+
+    @staticmethod
+    def _rgb_operands(rgb, s):
+        """(ToRGB weight, its styles inside ``s``, its weight scale) as the ToRGB-fused kernels take them; NULLs without an offer."""
+        if rgb is None:
+            return None, None, 0.0
+        t = rgb["module"]
+        return t.conv.weight.data_ptr(), s.data_ptr() + 4 * rgb["s_off"], float(t.conv.scale)
+
     def run(self, x, s, s_off, d, noise, bufs, tag, rgb=None, src=None, slot=0, prescaled=False, post_off=None):
         """Fused forward on precomputed styles. ``bufs(name, shape)`` hands out static device buffers.
         The style fold (include/maua_hip.h): ``prescaled`` = x arrives multiplied by this layer's styles (the producer applied them);
         ``post_off`` = offset inside ``s`` of the styles of the layer that consumes this layer's output: where this layer's path can, it
         stores its map multiplied by them and sets ``self.posted`` (the consumer is then run with ``prescaled``).
-        ``rgb`` (plain layers only): dict(module=ToRGB, s_off, skip, out, store) — fold the following ToRGB into the conv
-        epilogue when the layer qualifies; on success ``rgb["done"]`` is set and ``rgb["out"]`` holds the image.
-        ``src`` / ``slot``: the noise map is read through the frame source (``noise`` is then ignored and may be None)."""
+        ``src`` / ``slot``: the noise map is read through the frame source (``noise`` is then ignored and may be None).
+        ``rgb`` (plain layers only) offers the following ToRGB for folding into this layer's launches.  Keys in: ``module`` (the ToRGB),
+        ``s_off`` (its styles inside ``s``), ``skip`` (the image of the resolution below, or None), ``out`` ([B, 3, H, W] image buffer),
+        ``store`` (False: the feature map itself is not needed — single-launch path only), ``u8`` ([B, H, W, 3] uint8 frames that the
+        single-launch path writes instead of ``out``) and ``tap`` (write ``out`` as well as ``u8``).  Keys out: ``done`` = the image was
+        produced here (the caller runs no ToRGB pass), ``u8_done`` = False when it is in ``out`` as fp32 planes although ``u8`` was offered.
+        The call reports its path in ``self.last_path``; the paths are tried in the order below, each launches or declines."""
         lib = _lib.load()
         conv = self.conv
         b, cin, h, w = x.shape
-        self.posted = False
-        s_ptr = None if prescaled else s.data_ptr() + 4 * s_off
-        post_ptr = None if post_off is None else s.data_ptr() + 4 * post_off
-        n_ws = lib.maua_modconv_ws_floats(b, cin, conv.out_channel, h, w, conv.conv_mode(h, w))
-        # one split-K workspace PER LAYER: a shared name would be re-allocated whenever the size changes, and a captured
-        # hipGraph keeps writing through the pointer of the buffer that was freed
-        low_mode = conv.conv_mode(h, w)
-        low = (self.lowres_fusion and not prescaled and low_mode in ((1,) if conv.upsample else (0, 2, 3))
-               and lib.maua_lowres_ok(cin, conv.out_channel, h, w, low_mode))
-        # (up-sampling layers: 6 = the F(2,2)^2 kernel on 16-wide inputs where the shape allows it, else 1 = the polyphase kernel)
-        low_up = 6 if (low and conv.upsample and self.lowres_up2d and lib.maua_lowres_ok(cin, conv.out_channel, h, w, 6)) else 1
-        ws = bufs(tag + ".ws", (n_ws,)) if (n_ws and not low) else None
-        if src is not None:
-            noise = None
-        if noise is not None:
-            noise = _lib.require_cuda(noise, "noise")
-            # the kernels read oh*ow floats per sample (b samples unless the map is shared): a wrongly sized map would be
-            # a silent out-of-bounds read where the reference raises a broadcast error (models/stylegan2.py:266)
-            oh, ow = (2 * h, 2 * w) if conv.upsample else (h, w)
-            if noise.dim() != 4 or noise.shape[1] != 1 or tuple(noise.shape[-2:]) != (oh, ow) or noise.shape[0] not in (1, b):
-                raise RuntimeError(f"noise {tuple(noise.shape)} does not match feature map [{b}, 1, {oh}, {ow}] "
-                                   f"(batch must be 1 or {b})")
-            noise = noise.contiguous()
-        if not conv.upsample:
-            out = bufs(tag, (b, conv.out_channel, h, w))
-            if rgb is not None and conv.out_channel <= 64 and n_ws == 0:
-                t = rgb["module"]
-                skip = rgb["skip"]
-                fusable = skip is None or (tuple(t.upsample.kernel.shape) == (4, 4) and t.upsample.factor == 2
-                                           and skip.shape[2] * 2 == h and skip.shape[3] * 2 == w)
-                if fusable:
-                    mode = conv.conv_mode(h, w)
-                    wp = conv.packed_wino(mode) if mode >= 2 else conv.packed()[0]
-                    nstride = 0 if noise is None or noise.shape[0] == 1 else noise.shape[-1] * noise.shape[-2]
-                    post = post_ptr if mode == 5 else None
-                    rc = lib.maua_styledconv_torgb_f32(
-                        x.data_ptr(), wp.data_ptr(), s_ptr, s.shape[1], _lib.ptr(d), out.data_ptr(), b,
-                        cin, conv.out_channel, h, w, mode, float(conv.scale), _lib.ptr(noise), nstride,
-                        self.noise.weight.data_ptr(), self.activate.bias.data_ptr(), t.conv.weight.data_ptr(),
-                        s.data_ptr() + 4 * rgb["s_off"], float(t.conv.scale), t.bias.data_ptr(), _lib.ptr(skip),
-                        _lib.ptr(t.upsample.kernel) if skip is not None else None,
-                        rgb["out"].data_ptr() if (rgb.get("u8") is None or rgb.get("tap")) else None,
-                        int(rgb.get("store", True)), _lib.ptr(rgb.get("u8")), src, slot, post, _lib.stream_ptr(x.device))
-                    if rc == 0:
-                        rgb["done"] = True
-                        self.posted = post is not None
-                        return out
-                    if rc != -38:  # MAUA_ENOSYS = layer shape not fusable -> two launches below
-                        _lib.check(rc, "maua_styledconv_torgb_f32")
-            elif rgb is not None and self.partial_rgb_fusion and n_ws == 0 and conv.conv_mode(h, w) == 5:
-                # wider layers on the 2-D Winograd kernel: every output-channel tile leaves its share of the ToRGB sum (3 planes);
-                # the ToRGB pass then adds 3 * m_tiles planes (+ bias, + up-sampled skip) instead of reading all `cout` feature planes
-                t = rgb["module"]
-                skip = rgb["skip"]
-                m_tiles = lib.maua_modconv_w2d_mtiles(cin, conv.out_channel, h, w)
-                fusable = m_tiles > 1 and (skip is None or (tuple(t.upsample.kernel.shape) == (4, 4) and t.upsample.factor == 2
-                                                            and skip.shape[2] * 2 == h and skip.shape[3] * 2 == w))
-                if fusable:
-                    part = bufs(tag + ".rgb_partial", (b, 3 * m_tiles, h, w))
-                    nstride = 0 if noise is None or noise.shape[0] == 1 else noise.shape[-1] * noise.shape[-2]
-                    _lib.check(lib.maua_styledconv_torgb_partial_f32(
-                        x.data_ptr(), conv.packed_wino(5).data_ptr(), s_ptr, s.shape[1], _lib.ptr(d),
-                        out.data_ptr(), b, cin, conv.out_channel, h, w, 5, float(conv.scale), _lib.ptr(noise), nstride,
-                        self.noise.weight.data_ptr(), self.activate.bias.data_ptr(), t.conv.weight.data_ptr(),
-                        s.data_ptr() + 4 * rgb["s_off"], float(t.conv.scale), part.data_ptr(), src, slot, post_ptr,
-                        _lib.stream_ptr(x.device)), "maua_styledconv_torgb_partial_f32")
-                    self.posted = post_ptr is not None
-                    _lib.check(lib.maua_torgb_f32(part.data_ptr(), None, None, 0, t.bias.data_ptr(),
-                                                  _lib.ptr(skip), _lib.ptr(t.upsample.kernel) if skip is not None else None,
-                                                  rgb["out"].data_ptr(), b, 3 * m_tiles, h, w, 1.0, _lib.stream_ptr(x.device)),
-                               "maua_torgb_f32")  # (w = s = NULL: the plane sum + bias + up-sampled skip)
-                    rgb["done"] = True
-                    rgb["u8_done"] = False  # the image is in rgb["out"] as fp32 planes: a last layer still needs the frame epilogue
-                    return out
-            if low and rgb is not None and self.partial_rgb_fusion and (w % 4 == 0) and post_ptr is None:
-                t = rgb["module"]
-                skip = rgb["skip"]
-                if skip is None or (tuple(t.upsample.kernel.shape) == (4, 4) and t.upsample.factor == 2
-                                    and skip.shape[2] * 2 == h and skip.shape[3] * 2 == w):
-                    groups = conv.out_channel // 32
-                    lws = bufs(tag + ".lws", (lib.maua_lowres_ws_floats(b, cin, conv.out_channel, h, w, low_mode),))
-                    part = bufs(tag + ".rgb_partial", (b, 3 * groups, h, w))
-                    nstride = 0 if noise is None or noise.shape[0] == 1 else noise.shape[-1] * noise.shape[-2]
-                    wpk = conv.packed_wino(low_mode) if low_mode >= 2 else conv.packed()[0]
-                    _lib.check(lib.maua_styledconv_rgbpart_lowres_f32(
-                        x.data_ptr(), wpk.data_ptr(), s_ptr, s.shape[1], _lib.ptr(d), out.data_ptr(), lws.data_ptr(),
-                        _lib.ptr(noise), nstride, self.noise.weight.data_ptr(), self.activate.bias.data_ptr(), t.conv.weight.data_ptr(),
-                        s.data_ptr() + 4 * rgb["s_off"], float(t.conv.scale), part.data_ptr(), src, slot, b, cin, conv.out_channel, h, w,
-                        low_mode, float(conv.scale), _lib.stream_ptr(x.device)), "maua_styledconv_rgbpart_lowres_f32")
-                    _lib.check(lib.maua_torgb_f32(part.data_ptr(), None, None, 0, t.bias.data_ptr(), _lib.ptr(skip),
-                                                  _lib.ptr(t.upsample.kernel) if skip is not None else None, rgb["out"].data_ptr(), b,
-                                                  3 * groups, h, w, 1.0, _lib.stream_ptr(x.device)), "maua_torgb_f32")
-                    rgb["done"] = True
-                    rgb["u8_done"] = False
-                    self.last_path = "lowres"
-                    return out
-            if ws is None and n_ws:
-                ws = bufs(tag + ".ws", (n_ws,))
-            self.last_path = "plain"
-            return conv.run(x, s, s_off, d, out, ws, fuse_act=True, noise=noise, noise_w=self.noise.weight,
-                            bias=self.activate.bias, src=src, slot=slot, prescaled=prescaled)
+        up = 2 if conv.upsample else 1
+        mode = conv.conv_mode(h, w)
+        noise, nstride = _checked_noise(noise, b, up * h, up * w, src)
+        c = SimpleNamespace(x=x, s=s, s_off=s_off, d=d, bufs=bufs, tag=tag, rgb=rgb, src=src, slot=slot, prescaled=prescaled, noise=noise,
+                            dims=(b, cin, conv.out_channel, h, w), mode=mode, st=_lib.stream_ptr(x.device))
+        # one split-K workspace PER LAYER (tag + ".ws", for the paths that run the convolution on its own): a shared name would be
+        # re-allocated whenever the size changes, and a captured hipGraph keeps writing through the pointer of the buffer that was freed
+        c.n_ws = lib.maua_modconv_ws_floats(*c.dims, mode)
+        c.low = (self.lowres_fusion and not prescaled and mode in ((1,) if conv.upsample else (0, 2, 3))
+                 and lib.maua_lowres_ok(*c.dims[1:], mode))
+        # (input, packed weight of ``mode``, styles or NULL when the input carries them, their row stride, demodulation) as every fused entry
+        # takes them; a function, so that the path that launches packs the weight (the one-time pack launch keeps its place in the stream)
+        c.head = lambda mode=mode: (x.data_ptr(), conv.weight_for(mode).data_ptr(), None if prescaled else s.data_ptr() + 4 * s_off,  # noqa: E731
+                                    s.shape[1], _lib.ptr(d))
+        c.post_ptr = None if post_off is None else s.data_ptr() + 4 * post_off
+        c.tail = (_lib.ptr(noise), nstride, self.noise.weight.data_ptr(), self.activate.bias.data_ptr())  # noise + bias + activation
+        if conv.upsample:
+            paths = (self._up_fused, self._up_lowres, self._up_pair)
+        else:
+            c.out = bufs(tag, (b, conv.out_channel, h, w))
+            c.rgb_ok = rgb is not None and rgb["module"].skip_fusable(rgb["skip"], h, w)  # the offer can be taken in-launch
+            c.rgb_w = self._rgb_operands(rgb, s)
+            paths = (self._torgb, self._rgb_partial, self._lowres_rgb, self._plain)
+        for path in paths:
+            out = path(c)
+            if out is not None:
+                return out
+
+    def _torgb(self, c):
+        """Layers of at most 64 channels: ToRGB (+ on the last layer the uint8 frame epilogue) in the convolution's epilogue, one launch."""
+        conv, rgb = self.conv, c.rgb
+        if not (c.rgb_ok and conv.out_channel <= 64 and c.n_ws == 0):
+            return None
+        t = rgb["module"]
+        post = c.post_ptr if c.mode == 5 else None
+        rc = _lib.load().maua_styledconv_torgb_f32(
+            *c.head(), c.out.data_ptr(), *c.dims, c.mode, float(conv.scale), *c.tail, *c.rgb_w, t.bias.data_ptr(), *t.skip_operands(rgb["skip"]),
+            rgb["out"].data_ptr() if (rgb.get("u8") is None or rgb.get("tap")) else None,
+            int(rgb.get("store", True)), _lib.ptr(rgb.get("u8")), c.src, c.slot, post, c.st)
+        if rc == -38:  # MAUA_ENOSYS = layer shape not fusable (the library's tile plan decides) -> the paths below
+            return None
+        _lib.check(rc, "maua_styledconv_torgb_f32")
+        return self._took("torgb", c.out, post is not None, rgb)
+
+    def _rgb_partial(self, c):
+        """Wider layers on the 2-D Winograd kernel: every output-channel tile leaves its share of the ToRGB sum (3 planes); the ToRGB pass
+        then adds 3 * m_tiles planes (+ bias, + up-sampled skip) instead of reading all ``cout`` feature planes."""
+        conv, rgb = self.conv, c.rgb
+        # (up to 64 channels the single-launch path above is the only ToRGB fusion that is tried)
+        b, cin, cout, h, w = c.dims
+        if not (c.rgb_ok and cout > 64 and self.partial_rgb_fusion and c.n_ws == 0 and c.mode == 5):
+            return None
+        m_tiles = _lib.load().maua_modconv_w2d_mtiles(cin, cout, h, w)
+        if m_tiles <= 1:
+            return None
+        part = c.bufs(c.tag + ".rgb_partial", (b, 3 * m_tiles, h, w))
+        _lib.check(_lib.load().maua_styledconv_torgb_partial_f32(
+            *c.head(), c.out.data_ptr(), *c.dims, 5, float(conv.scale), *c.tail, *c.rgb_w, part.data_ptr(), c.src, c.slot, c.post_ptr, c.st),
+            "maua_styledconv_torgb_partial_f32")
+        rgb["module"].run(part, None, 0, rgb["skip"], rgb["out"])
+        return self._took("rgb_partial", c.out, c.post_ptr is not None, rgb, u8_done=False)
+
+    def _lowres_rgb(self, c):
+        """Low-resolution entry of a plain layer: convolution -> split-K slabs, ONE launch for slab sum + tail + per-group partial ToRGB
+        sums (maua_styledconv_rgbpart_lowres_f32), then the plane sum."""
+        conv, rgb = self.conv, c.rgb
+        b, cin, cout, h, w = c.dims
+        if not (c.low and c.rgb_ok and self.partial_rgb_fusion and w % 4 == 0 and c.post_ptr is None):
+            return None
+        lib = _lib.load()
+        lws = c.bufs(c.tag + ".lws", (lib.maua_lowres_ws_floats(*c.dims, c.mode),))
+        part = c.bufs(c.tag + ".rgb_partial", (b, 3 * (cout // 32), h, w))
+        _lib.check(lib.maua_styledconv_rgbpart_lowres_f32(
+            *c.head(), c.out.data_ptr(), lws.data_ptr(), *c.tail, *c.rgb_w, part.data_ptr(), c.src, c.slot, *c.dims, c.mode, float(conv.scale),
+            c.st), "maua_styledconv_rgbpart_lowres_f32")
+        rgb["module"].run(part, None, 0, rgb["skip"], rgb["out"])
+        return self._took("lowres", c.out, rgb=rgb, u8_done=False)
+
+    def _plain(self, c):
+        """Convolution with noise + bias + activation in its epilogue; an offered ToRGB is left to the caller."""
+        ws = c.bufs(c.tag + ".ws", (c.n_ws,)) if c.n_ws else None
+        self.conv.run(c.x, c.s, c.s_off, c.d, c.out, ws, fuse_act=True, noise=c.noise, noise_w=self.noise.weight,
+                      bias=self.activate.bias, src=c.src, slot=c.slot, prescaled=c.prescaled, mode=c.mode)
+        return self._took("plain", c.out)
+
+    def _up_fused(self, c):
+        """The whole layer in one pass over the transposed convolution's accumulators: no raw (2H+1) x (2W+1) map (csrc/modconv_up2d.hip)."""
+        conv, lib = self.conv, _lib.load()
+        b, cin, cout, h, w = c.dims
+        if not (self.fused_blur_min_width <= w and c.mode == 6 and tuple(conv.blur.pad) == (1, 1) and conv.blur_is_separable()
+                and lib.maua_upconv_blur_ok(cin, cout, h, w)):
+            return None
+        out = c.bufs(c.tag, (b, cout, 2 * h, 2 * w))
+        n_seam = lib.maua_upconv_blur_ws_floats(*c.dims)
+        seam = c.bufs(c.tag + ".seam", (n_seam,)) if n_seam else None
+        _lib.check(lib.maua_upconv_blur_f32(
+            *c.head(), out.data_ptr(), _lib.ptr(seam), conv.blur.kernel.data_ptr(), *c.tail, c.src, c.slot, *c.dims, float(conv.scale),
+            c.post_ptr, c.st), "maua_upconv_blur_f32")
+        return self._took("fused", out, c.post_ptr is not None)
+
+    def _up_lowres(self, c):
+        """Low-resolution entry of an up-sampling layer: transposed convolution -> split-K slabs, then ONE launch: slab sum, demodulation,
+        blur, noise, bias, leaky ReLU (+ the style fold's scale)."""
+        conv, lib = self.conv, _lib.load()
+        b, cin, cout, h, w = c.dims
+        k = conv.blur.kernel
+        if not (c.low and tuple(k.shape) == (4, 4) and tuple(conv.blur.pad) == (1, 1)):
+            return None
+        # (6 = the F(2,2)^2 kernel on 16-wide inputs where the shape allows it, else 1 = the polyphase kernel, which is ``c.mode`` here)
+        low_up = 6 if (self.lowres_up2d and lib.maua_lowres_ok(cin, cout, h, w, 6)) else 1
+        out = c.bufs(c.tag, (b, cout, 2 * h, 2 * w))
+        lws = c.bufs(c.tag + ".lws", (lib.maua_lowres_ws_floats(*c.dims, low_up),))
+        _lib.check(lib.maua_upconv_blur_lowres_f32(
+            *c.head(low_up), out.data_ptr(), lws.data_ptr(), k.data_ptr(), *c.tail, c.src, c.slot, *c.dims, low_up,
+            float(conv.scale), c.post_ptr, c.st), "maua_upconv_blur_lowres_f32")
+        return self._took("lowres", out, c.post_ptr is not None)
+
+    def _up_pair(self, c):
+        """Transposed convolution into a raw (2H+1) x (2W+1) map, then blur + noise + bias + activation (+ the style fold's scale)."""
+        conv = self.conv
+        b, cin, cout, h, w = c.dims
         k = conv.blur.kernel
         pad0, pad1 = conv.blur.pad
-        if (self.fused_blur_min_width <= w and conv.conv_mode(h, w) == 6 and (pad0, pad1) == (1, 1) and conv.blur_is_separable()
-                and lib.maua_upconv_blur_ok(cin, conv.out_channel, h, w)):
-            # the whole layer in one pass over the transposed convolution's accumulators: no raw (2H+1) x (2W+1) map (csrc/modconv_up2d.hip)
-            self.last_path = "fused"
-            out = bufs(tag, (b, conv.out_channel, 2 * h, 2 * w))
-            n_seam = lib.maua_upconv_blur_ws_floats(b, cin, conv.out_channel, h, w)
-            seam = bufs(tag + ".seam", (n_seam,)) if n_seam else None
-            nstride = 0 if noise is None or noise.shape[0] == 1 else 4 * h * w
-            _lib.check(lib.maua_upconv_blur_f32(
-                x.data_ptr(), conv.packed_wino(6).data_ptr(), s_ptr, s.shape[1], _lib.ptr(d), out.data_ptr(),
-                _lib.ptr(seam), k.data_ptr(), _lib.ptr(noise), nstride, self.noise.weight.data_ptr(), self.activate.bias.data_ptr(),
-                src, slot, b, cin, conv.out_channel, h, w, float(conv.scale), post_ptr, _lib.stream_ptr(x.device)), "maua_upconv_blur_f32")
-            self.posted = post_ptr is not None
-            return out
-        if low and tuple(k.shape) == (4, 4) and (pad0, pad1) == (1, 1):
-            # transposed convolution -> split-K slabs, then ONE launch: slab sum, demodulation, blur, noise, bias, leaky ReLU (+ the style fold's scale)
-            self.last_path = "lowres"
-            out = bufs(tag, (b, conv.out_channel, 2 * h, 2 * w))
-            lws = bufs(tag + ".lws", (lib.maua_lowres_ws_floats(b, cin, conv.out_channel, h, w, low_up),))
-            nstride = 0 if noise is None or noise.shape[0] == 1 else 4 * h * w
-            wpk = conv.packed_wino(6) if low_up == 6 else conv.packed()[0]
-            _lib.check(lib.maua_upconv_blur_lowres_f32(
-                x.data_ptr(), wpk.data_ptr(), s_ptr, s.shape[1], _lib.ptr(d), out.data_ptr(), lws.data_ptr(), k.data_ptr(),
-                _lib.ptr(noise), nstride, self.noise.weight.data_ptr(), self.activate.bias.data_ptr(), src, slot, b, cin, conv.out_channel,
-                h, w, low_up, float(conv.scale), post_ptr, _lib.stream_ptr(x.device)), "maua_upconv_blur_lowres_f32")
-            self.posted = post_ptr is not None
-            return out
-        if ws is None and n_ws:
-            ws = bufs(tag + ".ws", (n_ws,))
-        self.last_path = "pair"
-        raw = bufs(tag + ".raw", (b, conv.out_channel, 2 * h + 1, 2 * w + 1))
-        conv.run(x, s, s_off, d, raw, ws, prescaled=prescaled)
+        ws = c.bufs(c.tag + ".ws", (c.n_ws,)) if c.n_ws else None
+        raw = c.bufs(c.tag + ".raw", (b, cout, 2 * h + 1, 2 * w + 1))
+        conv.run(c.x, c.s, c.s_off, c.d, raw, ws, prescaled=c.prescaled, mode=c.mode)
         oh, ow = raw.shape[2] + pad0 + pad1 - k.shape[0] + 1, raw.shape[3] + pad0 + pad1 - k.shape[1] + 1
-        out = bufs(tag, (b, conv.out_channel, oh, ow))
-        nstride = 0 if noise is None or noise.shape[0] == 1 else oh * ow
-        rc = lib.maua_blur_noise_act_f32(raw.data_ptr(), k.data_ptr(), out.data_ptr(), b, conv.out_channel, raw.shape[2],
-                                         raw.shape[3], k.shape[0], k.shape[1], pad0, pad1, None, _lib.ptr(noise), nstride,
-                                         self.noise.weight.data_ptr(), self.activate.bias.data_ptr(), src, slot,
-                                         post_ptr, s.shape[1], _lib.stream_ptr(x.device))
+        out = c.bufs(c.tag, (b, cout, oh, ow))
+        rc = _lib.load().maua_blur_noise_act_f32(raw.data_ptr(), k.data_ptr(), out.data_ptr(), b, cout, raw.shape[2], raw.shape[3],
+                                                 k.shape[0], k.shape[1], pad0, pad1, None, *c.tail, c.src, c.slot, c.post_ptr,
+                                                 c.s.shape[1], c.st)
         _lib.check(rc, "maua_blur_noise_act_f32")
-        self.posted = post_ptr is not None
-        return out
+        return self._took("pair", out, c.post_ptr is not None)
 
     def forward(self, inputs, style, noise=None, transform_dict_list=[]):
-        x = _lib.require_cuda(inputs, "inputs")
-        style = _lib.require_cuda(style, "style")
-        b, cin = x.shape[:2]
-        dev = x.device
-        lib = _lib.load()
+        x, s, d = _layer_styles(self.conv, inputs, style)
+        b, dev = x.shape[0], x.device
         with th.cuda.device(dev):
-            s = th.empty((b, cin), dtype=th.float32, device=dev)
-            d = th.empty((b, self.conv.out_channel), dtype=th.float32, device=dev)
-            table = _style_table([self.conv.table_entry(0, 0, 0)], dev)
-            lat = style.reshape(b, 1, -1)
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.maua_style_affine_f32(lat.data_ptr(), b, 1, lat.shape[-1], None, None, table.data_ptr(), 1,
-                                                 cin, s.data_ptr(), cin, None, st), "maua_style_affine_f32")
-            _lib.check(lib.maua_demod_f32(table.data_ptr(), 1, self.conv.out_channel, s.data_ptr(), cin, d.data_ptr(), b,
-                                          st), "maua_demod_f32")
             if noise is None:
                 up = 2 if self.conv.upsample else 1
                 noise = th.randn(b, 1, x.shape[2] * up, x.shape[3] * up, device=dev)
-            out = self.run(x, s, 0, d if self.conv.demodulate else None, noise,
-                           lambda name, shape: th.empty(shape, dtype=th.float32, device=dev), "out")
+            out = self.run(x, s, 0, d, noise, lambda name, shape: th.empty(shape, dtype=th.float32, device=dev), "out")
         return self.manipulation(out, transform_dict_list)
 
 
@@ -668,34 +685,36 @@ class ToRGB(nn.Module):
         self.conv = ModulatedConv2d(in_channel, 3, 1, style_dim, demodulate=False)
         self.bias = nn.Parameter(th.zeros(1, 3, 1, 1))
 
+    def _upsample_is_4tap(self):
+        return tuple(self.upsample.kernel.shape) == (4, 4) and self.upsample.factor == 2
+
+    def skip_fusable(self, skip, h, w):
+        """True when the kernels can up-sample ``skip`` inside the launch that adds it to an h x w image: no skip at all, or the 4-tap /
+        factor-2 Upsample on an image of half the size."""
+        return skip is None or (self._upsample_is_4tap() and skip.shape[2] * 2 == h and skip.shape[3] * 2 == w)
+
+    def skip_operands(self, skip):
+        """(skip image, taps of its Upsample) as the kernels take them: NULLs without a skip image."""
+        return (None, None) if skip is None else (skip.data_ptr(), self.upsample.kernel.data_ptr())
+
     def run(self, x, s, s_off, skip, out):
-        lib = _lib.load()
+        """``s`` None: the plane-sum form of maua_torgb_f32 (w = s = NULL) — ``x`` [B, 3 n, H, W] holds partial ToRGB sums that a convolution
+        left, ``out`` = the sum of its 3-plane groups + bias + up-sampled ``skip``."""
         b, cin, h, w = x.shape
-        k4 = None
-        if skip is not None:
-            k4 = self.upsample.kernel
-            if tuple(k4.shape) != (4, 4) or self.upsample.factor != 2:
+        if not self.skip_fusable(skip, h, w):
+            if not self._upsample_is_4tap():
                 raise NotImplementedError("fused ToRGB skip path is built for the 4-tap / factor-2 Upsample")
-            if skip.shape[2] * 2 != h or skip.shape[3] * 2 != w:
-                raise RuntimeError(f"skip {tuple(skip.shape)} is not half of {h}x{w}")
-        rc = lib.maua_torgb_f32(x.data_ptr(), self.conv.weight.data_ptr(), s.data_ptr() + 4 * s_off, s.shape[1],
-                                self.bias.data_ptr(), _lib.ptr(skip), _lib.ptr(k4), out.data_ptr(), b, cin, h, w,
-                                float(self.conv.scale), _lib.stream_ptr(x.device))
+            raise RuntimeError(f"skip {tuple(skip.shape)} is not half of {h}x{w}")
+        weight = (None, None, 0) if s is None else (self.conv.weight.data_ptr(), s.data_ptr() + 4 * s_off, s.shape[1])
+        rc = _lib.load().maua_torgb_f32(x.data_ptr(), *weight, self.bias.data_ptr(), *self.skip_operands(skip), out.data_ptr(), b, cin, h, w,
+                                        1.0 if s is None else float(self.conv.scale), _lib.stream_ptr(x.device))
         _lib.check(rc, "maua_torgb_f32")
         return out
 
     def forward(self, inputs, style, skip=None):
-        x = _lib.require_cuda(inputs, "inputs")
-        style = _lib.require_cuda(style, "style")
-        b, cin, h, w = x.shape
-        dev = x.device
-        lib = _lib.load()
+        x, s, _ = _layer_styles(self.conv, inputs, style)
+        (b, _, h, w), dev = x.shape, x.device
         with th.cuda.device(dev):
-            s = th.empty((b, cin), dtype=th.float32, device=dev)
-            table = _style_table([self.conv.table_entry(0, 0, 0)], dev)
-            lat = style.reshape(b, 1, -1)
-            _lib.check(lib.maua_style_affine_f32(lat.data_ptr(), b, 1, lat.shape[-1], None, None, table.data_ptr(), 1,
-                                                 cin, s.data_ptr(), cin, None, _lib.stream_ptr(dev)), "maua_style_affine_f32")
             out = th.empty((b, 3, h, w), dtype=th.float32, device=dev)
             if skip is not None:
                 skip = _lib.require_cuda(skip, "skip")
@@ -746,6 +765,8 @@ class Generator(nn.Module):
     tap_float_image = False
     # the style fold (include/maua_hip.h THE STYLE FOLD; A/B switch): producers store their map multiplied by the consumer's styles
     style_fold = True
+    # every ToRGB as a pass of its own instead of folded into the preceding layer's launches (A/B switch)
+    disable_rgb_fusion = False
     # seed of the counter-based noise of a randomised render (render.synthesize, ``random_noise``); None: one draw from torch's CPU
     # generator per render.  ``noise_frame_offset``: absolute index of frame 0 of the sequences a render is given (a rank that holds one
     # shard of a job's frames: render.render_shard sets it), so that frame n of the job gets the same maps on whichever rank.
@@ -994,9 +1015,12 @@ class Generator(nn.Module):
         # activation maps handed out (the ToRGB of a plain layer is computed in its own epilogue from the un-scaled value).
         fold = self.style_fold and not want_acts
 
+        def bent(layer_id):
+            return any(bd["layer"] == layer_id for bd in bends)
+
         def post_for(layer_id, consumer, h, w, consumer_entry):
             """s offset of ``consumer``'s styles if the producer with ``layer_id`` may store its map pre-multiplied by them, else None."""
-            if not fold or any(bd["layer"] == layer_id for bd in bends) or not consumer.accepts_prescaled(h, w):
+            if not fold or bent(layer_id) or not consumer.accepts_prescaled(h, w):
                 return None
             return consumer_entry["s_off"]
 
@@ -1004,7 +1028,7 @@ class Generator(nn.Module):
         # conv1 on a ConstantInput nobody bends: y = T s with T = W * const precomputed (csrc/constconv.hip) — no [B, C, 4, 4] copy of the
         # constant, no convolution
         c1 = self.conv1.conv
-        const_conv = (isinstance(self.input, ConstantInput) and self.conv1.lowres_fusion and not any(bd["layer"] == 0 for bd in bends)
+        const_conv = (isinstance(self.input, ConstantInput) and self.conv1.lowres_fusion and not bent(0)
                       and tuple(self.input.input.shape[2:]) == (4, 4) and c1.kernel_size == 3 and not c1.upsample
                       and lib.maua_const_conv_ok(c1.in_channel, c1.out_channel, 4, 4))
         x = None
@@ -1016,66 +1040,59 @@ class Generator(nn.Module):
             x.copy_(self.input.input.expand(batch, -1, -1, -1))
         if x is not None:
             x = self.const_manipulation.run(x, bends, bufs, "const", src)
-        li = 0
         # min_rgb_size (reference :553,567): resolutions below it contribute no ToRGB, the skip chain starts later
         current_size = 4
         image = None
-        fuse1 = None
-        hw0 = tuple(self.input.input.shape[2:]) if x is None else tuple(x.shape[2:])
-        if (self.min_rgb_size <= current_size and not any(bd["layer"] == 1 for bd in bends)
-                and not getattr(self, "disable_rgb_fusion", False)):
-            fuse1 = dict(module=self.to_rgb1, s_off=ent[li + 1]["s_off"], skip=None, out=bufs("rgb1", (batch, 3) + hw0), store=True)
-        if const_conv:
-            out = self._run_const_conv(s, ent[li]["s_off"], demod_of(ent[li]), noise_for(0, 4, 4), bufs, fuse1, src, batch)
-        else:
-            out = self.conv1.run(x, s, ent[li]["s_off"], demod_of(ent[li]), noise_for(0, x.shape[2], x.shape[3]), bufs, "conv1",
-                                 rgb=fuse1, src=src, slot=0)  # (conv1 never posts: its consumer is a polyphase layer without a pre-scaled instance)
         posted = False  # whether `out` carries the next convolution's styles already
-        out = self.conv1.manipulation.run(out, bends, bufs, "conv1", src)
-        acts.append(out)
-        li += 1
-        if fuse1 is not None and fuse1.get("done"):
-            image = fuse1["out"]
-        elif self.min_rgb_size <= current_size:
-            image = self.to_rgb1.run(out, s, ent[li]["s_off"], None, bufs("rgb1", (batch, 3) + tuple(out.shape[2:])))
-        li += 1
-        for n in range(self.log_size - 2):
-            up, plain, rgb = self.convs[2 * n], self.convs[2 * n + 1], self.to_rgbs[n]
-            out = up.run(out, s, ent[li]["s_off"], demod_of(ent[li]), noise_for(2 * n + 1, out.shape[2] * 2, out.shape[3] * 2),
-                         bufs, f"convs.{2 * n}", src=src, slot=2 * n + 1, prescaled=posted,
-                         post_off=post_for(2 * n + 2, plain, out.shape[2] * 2, out.shape[3] * 2, ent[li + 1]))
-            posted = up.posted
-            out = up.manipulation.run(out, bends, bufs, f"convs.{2 * n}", src)
-            acts.append(out)
-            li += 1
-            current_size *= 2
+
+        def plain_layer(conv, tag, slot, layer_id, x, e, to_rgb, e_rgb, rgb_name, is_last=False, post_off=None):
+            """conv1 (``x`` None: on the constant input) or the plain layer of a resolution, its bends, and the resolution's ToRGB onto
+            ``image``: offered to the layer's own launches, else a pass of its own.  Returns the layer's map."""
+            nonlocal image, posted
+            h, w = (4, 4) if x is None else x.shape[2:]
+            rgb_buf = bufs(rgb_name, (batch, 3, h, w))
+            wants_rgb = self.min_rgb_size <= current_size
             # fold ToRGB into the conv epilogue where the layer qualifies (<= 64 channels) and nothing needs the feature
             # map in between (a bend on this layer id would); the last layer then never writes its feature map at all
-            layer_id = 2 * n + 3
-            bent = any(bd["layer"] == layer_id for bd in bends)
-            rgb_buf = bufs(f"rgbs.{n}", (batch, 3, out.shape[2], out.shape[3]))
             fuse = None
-            wants_rgb = self.min_rgb_size <= current_size
-            is_last = n == self.log_size - 3
-            if wants_rgb and not bent and not getattr(self, "disable_rgb_fusion", False):
-                fuse = dict(module=rgb, s_off=ent[li + 1]["s_off"], skip=image, out=rgb_buf,
+            if wants_rgb and not bent(layer_id) and not self.disable_rgb_fusion:
+                fuse = dict(module=to_rgb, s_off=e_rgb["s_off"], skip=image, out=rgb_buf,
                             store=(not is_last) or want_acts, u8=frames_u8 if is_last else None, tap=self.tap_float_image)
-            nxt = self.convs[2 * n + 2] if not is_last else None
-            out = plain.run(out, s, ent[li]["s_off"], demod_of(ent[li]), noise_for(2 * n + 2, out.shape[2], out.shape[3]),
-                            bufs, f"convs.{2 * n + 1}", rgb=fuse, src=src, slot=2 * n + 2, prescaled=posted,
-                            post_off=None if nxt is None else post_for(layer_id, nxt, out.shape[2], out.shape[3], ent[li + 2]))
-            posted = plain.posted
-            out = plain.manipulation.run(out, bends, bufs, f"convs.{2 * n + 1}", src)
+            if x is None:
+                out = self._run_const_conv(s, e["s_off"], demod_of(e), noise_for(slot, h, w), bufs, fuse, src, batch)
+            else:
+                out = conv.run(x, s, e["s_off"], demod_of(e), noise_for(slot, h, w), bufs, tag, rgb=fuse, src=src, slot=slot,
+                               prescaled=posted, post_off=post_off)
+            posted = conv.posted
+            out = conv.manipulation.run(out, bends, bufs, tag, src)
             acts.append(out)
-            li += 1
             if fuse is not None and fuse.get("done"):
                 image = rgb_buf
                 if is_last and frames_u8 is not None and fuse.get("u8_done", True) and not self.tap_float_image:
                     image = None  # left the device path as uint8 frames
             elif wants_rgb:
                 assert not posted  # (a separate ToRGB pass reads the un-scaled map: plain.run only posts from the ToRGB-fused paths)
-                image = rgb.run(out, s, ent[li]["s_off"], image, rgb_buf)
-            li += 1
+                image = to_rgb.run(out, s, e_rgb["s_off"], image, rgb_buf)
+            return out
+
+        # (conv1 never posts: its consumer is a polyphase layer without a pre-scaled instance)
+        out = plain_layer(self.conv1, "conv1", 0, 1, x, ent[0], self.to_rgb1, ent[1], "rgb1")
+        for n in range(self.log_size - 2):
+            up, plain = self.convs[2 * n], self.convs[2 * n + 1]
+            is_last = n == self.log_size - 3
+            # this resolution's entries of the style table (conv1 and to_rgb1 come first); e_next: the next resolution's up-sampling layer
+            e_up, e_plain, e_rgb = ent[3 * n + 2: 3 * n + 5]
+            e_next = None if is_last else ent[3 * n + 5]
+            h, w = out.shape[2] * 2, out.shape[3] * 2
+            out = up.run(out, s, e_up["s_off"], demod_of(e_up), noise_for(2 * n + 1, h, w), bufs, f"convs.{2 * n}", src=src,
+                         slot=2 * n + 1, prescaled=posted, post_off=post_for(2 * n + 2, plain, h, w, e_plain))
+            posted = up.posted
+            out = up.manipulation.run(out, bends, bufs, f"convs.{2 * n}", src)
+            acts.append(out)
+            current_size *= 2
+            post_off = None if is_last else post_for(2 * n + 3, self.convs[2 * n + 2], h, w, e_next)
+            out = plain_layer(plain, f"convs.{2 * n + 1}", 2 * n + 2, 2 * n + 3, out, e_plain, self.to_rgbs[n], e_rgb, f"rgbs.{n}",
+                              is_last, post_off)
         if frames_u8 is not None and image is not None:  # last layer not fusable (bend on it, > 64 channels, ...)
             _lib.check(lib.maua_frames_to_u8(image.data_ptr(), frames_u8.data_ptr(), batch, image.shape[2], image.shape[3], st),
                        "maua_frames_to_u8")
@@ -1086,37 +1103,19 @@ class Generator(nn.Module):
 
     def _run_const_conv(self, s, s_off, d, noise, bufs, rgb, src, batch):
         """conv1 + noise + bias + activation (+ the partial ToRGB sums of to_rgb1 and their plane sum) on the constant input: one launch of
-        maua_const_styledconv_f32 (+ one of maua_torgb_f32's plane-sum form)."""
-        lib = _lib.load()
+        maua_const_styledconv_f32 (+ one of maua_torgb_f32's plane-sum form).  One more path of ``StyledConv.run``, reported on conv1."""
         m, c1 = self.conv1, self.conv1.conv
-        dev = self.input.input.device
         cin, cout = c1.in_channel, c1.out_channel
         out = bufs("conv1", (batch, cout, 4, 4))
-        if src is not None:
-            noise = None
-        if noise is not None:
-            noise = _lib.require_cuda(noise, "noise")
-            if noise.dim() != 4 or noise.shape[1] != 1 or tuple(noise.shape[-2:]) != (4, 4) or noise.shape[0] not in (1, batch):
-                raise RuntimeError(f"noise {tuple(noise.shape)} does not match feature map [{batch}, 1, 4, 4] (batch must be 1 or {batch})")
-            noise = noise.contiguous()
-        nstride = 0 if noise is None or noise.shape[0] == 1 else 16
-        part, t = None, None
-        if rgb is not None:
-            t = rgb["module"]
-            part = bufs("conv1.rgb_partial", (batch, 3 * (cout // 32), 4, 4))
-        st = _lib.stream_ptr(dev)
-        _lib.check(lib.maua_const_styledconv_f32(
+        noise, nstride = _checked_noise(noise, batch, 4, 4, src)
+        part = None if rgb is None else bufs("conv1.rgb_partial", (batch, 3 * (cout // 32), 4, 4))
+        _lib.check(_lib.load().maua_const_styledconv_f32(
             self._const_conv_operand().data_ptr(), s.data_ptr() + 4 * s_off, s.shape[1], _lib.ptr(d), out.data_ptr(), _lib.ptr(noise), nstride,
-            m.noise.weight.data_ptr(), m.activate.bias.data_ptr(), None if t is None else t.conv.weight.data_ptr(),
-            None if t is None else s.data_ptr() + 4 * rgb["s_off"], 0.0 if t is None else float(t.conv.scale), _lib.ptr(part), src, 0, batch,
-            cin, cout, 4, 4, float(c1.scale), st), "maua_const_styledconv_f32")
+            m.noise.weight.data_ptr(), m.activate.bias.data_ptr(), *m._rgb_operands(rgb, s), _lib.ptr(part), src, 0, batch,
+            cin, cout, 4, 4, float(c1.scale), _lib.stream_ptr(self.input.input.device)), "maua_const_styledconv_f32")
         if rgb is not None:
-            _lib.check(lib.maua_torgb_f32(part.data_ptr(), None, None, 0, t.bias.data_ptr(), None, None, rgb["out"].data_ptr(), batch,
-                                          3 * (cout // 32), 4, 4, 1.0, st), "maua_torgb_f32")
-            rgb["done"] = True
-        m.posted = False
-        m.last_path = "const"
-        return out
+            rgb["module"].run(part, None, 0, None, rgb["out"])
+        return m._took("const", out, rgb=rgb)
 
     # ------------------------------------------------------------------ counter-based noise
     def _randn_table(self, slots, maps):
@@ -1223,7 +1222,6 @@ class FrameSource:
         # slot -> lane-private [batch, 1, h, w] buffer the captured forward fills itself (capture_graph's random_slots); its first launch
         # rewrites the slot's pointer / stride on every replay, so what ``bind`` leaves there is never read: one valid map, stride 0
         self.generated = dict(generated or {})
-        dev = generator.input.input.device
         self.dev = generator._buf(batch, "g.frame_source", (ctypes.sizeof(_lib.FrameSource),), dtype=th.uint8)
         self.ptr = self.dev.data_ptr()
         self._keep = None
@@ -1232,7 +1230,6 @@ class FrameSource:
         zeros.zero_()
         self.noise_hw = [tuple(getattr(generator.noises, f"noise_{i}").shape[-2:]) for i in range(generator.num_layers)]
         self.bind(zeros, [None] * generator.num_layers, None, _n_frames=batch)
-        del dev
 
     def bind(self, latents, noise, trunc, _n_frames=None):
         """latents [n_frames, n_latent, style_dim]; noise: per slot None (the checkpoint's buffer for every frame), a
@@ -1273,7 +1270,7 @@ class FrameSource:
                 raise RuntimeError(f"noise[{i}] {tuple(nz.shape)} does not match [{n_frames} or 1, 1, {self.noise_hw[i][0]}, "
                                    f"{self.noise_hw[i][1]}]")
             host.noise[i] = nz.data_ptr()
-            host.noise_stride[i] = 0 if nz.shape[0] == 1 else nz.shape[-1] * nz.shape[-2]
+            host.noise_stride[i] = _noise_stride(nz)
             keep.append(nz)
         self.n_frames = n_frames
         self._keep = keep

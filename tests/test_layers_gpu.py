@@ -900,6 +900,8 @@ def test_style_fold_chain_equals_unfolded_chain_and_oracle(gpu, c0, c1, c2, h, w
         bb = B.run(a, styles, entries[1]["s_off"], dm(entries[1]), g["nzB"], bufs, "B", rgb=fuse, prescaled=fold,
                    post_off=entries[3]["s_off"] if fold else None)
         assert fuse.get("done") and B.posted == fold
+        # (mode 5, n_ws == 0: up to 64 channels ToRGB rides in the convolution's launch, wider layers leave per-tile partial sums)
+        assert B.last_path == ("torgb" if c1 <= 64 else "rgb_partial")
         c = C.run(bb, styles, entries[3]["s_off"], dm(entries[3]), g["nzC"], bufs, "C", prescaled=fold)
         assert not C.posted
         torch.cuda.synchronize()
