@@ -20,7 +20,7 @@ extern "C" {
 #define MAUA_ENOSYS (-38)
 
 /* ABI version of this header; bumped on any signature change. */
-int maua_abi_version(void);  /* 7: + maua_randn_frames_f32 (counter-based noise); 6: + the structural-segmentation entries (maua_tempogram_f32 ... maua_rec_affinity_f32); 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
+int maua_abi_version(void);  /* 8: + maua_bend_point_f32, maua_bend_morph_f32 (point and morphological network bends); 7: + maua_randn_frames_f32 (counter-based noise); 6: + the structural-segmentation entries (maua_tempogram_f32 ... maua_rec_affinity_f32); 5: + the low-resolution entries (maua_*_lowres_*), maua_const_styledconv_f32, maua_torgb_f32's plane-sum form; 4: the style fold (post_s arguments, s == NULL; round 6); 3: + maua_upconv_blur_f32 (round 5); 2: frame source (maua_frame_source_t) arguments; no tuning entry */
 /* Number of compute units / name of device 0 (diagnostics for bench.py). */
 int maua_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
 
@@ -442,6 +442,28 @@ int maua_affine_reflect_warp_f32(const float* x, const float* m, float* y, int b
 int maua_affine_reflect_warp_mapped_f32(const float* x, const float* m, float* y, int batch, int channels, int h, int w,
                                         int pad_l, int pad_r, int pad_t, int pad_b, const float* add_noise,
                                         const int* xmap, const int* ymap, const maua_frame_source_t* src, void* stream);
+
+/* Point and morphological network bends (ABI 8; csrc/bend_ops.hip) — the transforms of Broad, Leymarie and Grierson, "Network Bending:
+ * Expressive Manipulation of Deep Generative Models" (2020) that are not affine warps, each on a chosen subset of a layer's channels
+ * (audioreactive/bend.py: Ablate, Invert, ScalarMultiply, BinaryThreshold, Erode, Dilate).  x, y [batch, channels, ...] fp32;
+ * chan_mask[channels] (uint8, device): channel c is transformed where chan_mask[c] != 0 and copied through unchanged elsewhere; NULL = every
+ * channel.  Per-frame parameter tables (`param` / `radius`, device, `rows` entries) work as the map sequence of
+ * maua_affine_reflect_warp_mapped_f32: rows == 1: every sample uses row 0; src != NULL: sample b uses row src->frame0 + b, read on the
+ * device (one captured launch serves every replay; the caller guarantees the table covers it); src == NULL: sample b uses row b, rows ==
+ * batch.  batch <= 64, channels <= 65535, planes below 2 GiB; MAUA_EINVAL on null or non-positive arguments or an unknown op.
+ *
+ * Point ops on planes of hw elements:  op 0 ablate: 0;  1 invert: 1 - x;  2 scalar multiply: x * p;  3 binary threshold: x > p ? 1 : 0
+ * (a NaN compares false).  param may be NULL for ops 0 and 1.  y == x is allowed. */
+int maua_bend_point_f32(const float* x, float* y, int batch, int channels, int64_t hw, int op, const float* param, int param_rows,
+                        const uint8_t* chan_mask, const maua_frame_source_t* src, void* stream);
+/* Morphological ops:  op 0 erode / 1 dilate = minimum / maximum over the (2r + 1) x (2r + 1) window centred on the pixel, window positions
+ * outside the map ignored: -max_pool2d(-x, 2r + 1, 1, r) / max_pool2d(x, 2r + 1, 1, r), bit for bit (-0 and +0 tie).  r = radius[row]
+ * clamped on the device to 0 .. MAUA_BEND_MAX_RADIUS; r = 0 is the identity.  A NaN stays inside the windows that contain it.  Any
+ * h, w >= 1.  The window is separable: one launch takes the extremum along rows, then along columns, on an LDS tile with a halo of
+ * MAUA_BEND_MAX_RADIUS.  y == x is refused (MAUA_EINVAL). */
+#define MAUA_BEND_MAX_RADIUS 16
+int maua_bend_morph_f32(const float* x, float* y, int batch, int channels, int h, int w, int op, const int32_t* radius, int radius_rows,
+                        const uint8_t* chan_mask, const maua_frame_source_t* src, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ hipGraph runtime
  * Capture everything launched on `stream` between begin/end into a hipGraph and replay it (per-frame generator

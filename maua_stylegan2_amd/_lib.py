@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmaua_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class MauaHipError(RuntimeError):
@@ -129,6 +129,8 @@ _SIGNATURES = {
     "maua_perlin3d_f32": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
     "maua_affine_reflect_warp_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P]),
     "maua_affine_reflect_warp_mapped_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P, _P]),
+    "maua_bend_point_f32": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, _P, c_int, _P, _P, _P]),
+    "maua_bend_morph_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
     "maua_graph_begin_capture": (c_int, [_P]),
     "maua_graph_end_capture": (c_int, [_P, POINTER(c_void_p)]),
     "maua_graph_launch": (c_int, [_P, _P]),

@@ -142,6 +142,120 @@ class AffineReflectWarp(th.nn.Module):
         return self._launch(x, out, m, nz, xmap, ymap, src if per_frame else None)
 
 
+_POINT_OPS = {"ablate": 0, "invert": 1, "multiply": 2, "threshold": 3}  # `op` of maua_bend_point_f32
+_MORPH_OPS = {"erode": 0, "dilate": 1}                                   # `op` of maua_bend_morph_f32
+_MAX_RADIUS = 16                                                         # MAUA_BEND_MAX_RADIUS
+
+
+class _ChannelBend(th.nn.Module):
+    """What the point and the morphological bends share: a per-frame parameter table of ``rows`` entries (``table`` [rows], or None
+    for an op without parameter) and a channel subset, uploaded once per (device, channel count) and reused, so that a captured
+    forward allocates nothing."""
+
+    def __init__(self, table, channels, n_channels=None):
+        super().__init__()
+        self.table = table
+        self.channels = None if channels is None else th.as_tensor(channels, dtype=th.int64).reshape(-1).cpu()
+        self._dev = {}  # (device, channels of the map) -> table and channel mask on the device; entries are never evicted: a captured
+                        # graph keeps reading them, also when one static instance sits on layers of different widths
+        if n_channels is not None:
+            self._channel_mask(int(n_channels))
+
+    @property
+    def sequence_rows(self):
+        return 1 if self.table is None else int(self.table.shape[0])
+
+    def _channel_mask(self, c):
+        if self.channels is None:
+            return None
+        if self.channels.numel() and (int(self.channels.min()) < 0 or int(self.channels.max()) >= c):
+            raise RuntimeError(f"bend channels must lie in 0 .. {c - 1} (the feature map has {c} channels)")
+        mask = th.zeros(c, dtype=th.uint8)
+        mask[self.channels] = 1
+        return mask
+
+    def _operands(self, x, per_frame):
+        """(table, mask) on x's device.  ``per_frame``: the table is the sequence of the whole render, indexed through the frame
+        source; otherwise it holds one row, or one row per sample of ``x``."""
+        b, c = x.shape[:2]
+        if b > 64:
+            raise RuntimeError(f"bends serve batches of up to 64 frames (got {b})")
+        if not per_frame and self.sequence_rows not in (1, b):
+            raise RuntimeError(f"expected 1 or {b} bend parameter rows, got {self.sequence_rows}")
+        if c > 65535:
+            raise RuntimeError(f"bends serve feature maps of up to 65535 channels (got {c})")
+        key = (str(x.device), c)
+        if key not in self._dev:
+            table = None if self.table is None else self.table.to(x.device).contiguous()
+            mask = self._channel_mask(c)
+            self._dev[key] = (table, None if mask is None else mask.to(x.device))
+        return self._dev[key]
+
+    def forward(self, x):
+        x = _lib.require_cuda(x, "x")
+        return self._launch(x, th.empty_like(x), *self._operands(x, per_frame=False), None)
+
+    def run_static(self, x, out, src):
+        """Inside a captured forward: the table holds one row per frame of the render (or a single static row) and sample b uses
+        row frame0 + b, read on the device through the frame source ``src``."""
+        per_frame = self.sequence_rows != 1
+        return self._launch(x, out, *self._operands(x, per_frame=per_frame), src if per_frame else None)
+
+
+class PointBend(_ChannelBend):
+    """y = op(x, p) on the channels ``channels`` (index list / LongTensor, None = all), the others copied through; ``op`` one of
+    _POINT_OPS, ``params`` [rows] (None for ablate / invert).  ``n_channels`` validates the channel list at construction instead of
+    at first use."""
+
+    def __init__(self, op, params, channels, n_channels=None):
+        if op not in _POINT_OPS:
+            raise ValueError(f"unknown point bend {op!r} ({' | '.join(_POINT_OPS)})")
+        if params is None and _POINT_OPS[op] >= 2:
+            raise ValueError(f"point bend {op!r} needs a parameter")
+        if params is not None:
+            params = th.as_tensor(params)
+            if params.dim() != 1 or params.shape[0] < 1:
+                raise ValueError(f"bend modulation must be a [n_frames] sequence (got shape {tuple(params.shape)})")
+            params = params.float()
+        super().__init__(params, channels, n_channels)
+        self.op = _POINT_OPS[op]
+
+    def _launch(self, x, y, params, mask, src):
+        b, c = x.shape[:2]
+        with th.cuda.device(x.device):
+            _lib.check(_lib.load().maua_bend_point_f32(x.data_ptr(), y.data_ptr(), b, c, x[0, 0].numel(), self.op, _lib.ptr(params),
+                                                       self.sequence_rows, _lib.ptr(mask), src, _lib.stream_ptr(x.device)),
+                       "maua_bend_point_f32")
+        return y
+
+
+class MorphBend(_ChannelBend):
+    """Erosion / dilation (``op`` one of _MORPH_OPS) with a (2r + 1)^2 window, r = ``radii`` [rows] (integers in 0 .. _MAX_RADIUS,
+    checked here on the host), on the channels ``channels``."""
+
+    def __init__(self, op, radii, channels, n_channels=None):
+        if op not in _MORPH_OPS:
+            raise ValueError(f"unknown morphological bend {op!r} ({' | '.join(_MORPH_OPS)})")
+        radii = th.as_tensor(radii).float()
+        if radii.dim() != 1 or radii.shape[0] < 1:
+            raise ValueError(f"bend modulation must be a [n_frames] sequence (got shape {tuple(radii.shape)})")
+        lo, hi = float(radii.min()), float(radii.max())
+        if not (lo >= 0 and hi <= _MAX_RADIUS):  # (also refuses a NaN)
+            raise ValueError(f"morphological bend radii must lie in 0 .. {_MAX_RADIUS} (got {lo:g} .. {hi:g})")
+        if not bool((radii == th.round(radii)).all()):
+            raise ValueError("morphological bend radii must be whole numbers (Erode / Dilate round their modulation)")
+        super().__init__(radii.to(th.int32), channels, n_channels)
+        self.op = _MORPH_OPS[op]
+
+    def _launch(self, x, y, radii, mask, src):
+        b, c, h, w = x.shape
+        with th.cuda.device(x.device):
+            _lib.check(_lib.load().maua_bend_morph_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, self.op, radii.data_ptr(),
+                                                       self.sequence_rows, _lib.ptr(mask), src, _lib.stream_ptr(x.device)),
+                       "maua_bend_morph_f32")
+        return y
+
+
 def _inverse_maps_translate(t):
     """dst = src + t  ->  src = dst - t (pixels)."""
     t = t.reshape(-1, 2).float()
@@ -205,3 +319,47 @@ class Rotate(NetworkBend):
         pads = (padding,) * 4
         sequential_fn = lambda b: AffineReflectWarp(_inverse_maps_rotate(b, w + 2 * padding, h + 2 * padding), pads)  # noqa: E731
         super().__init__(sequential_fn, modulation)
+
+
+class Ablate(NetworkBend):
+    """Zero the channels ``channels``: always (no modulation), or on the frames whose modulation is above 0.5 (a gate: the other
+    frames pass through; realised as a multiplication by 0 or 1)."""
+
+    def __init__(self, modulation=None, channels=None):
+        if modulation is None:
+            super().__init__(lambda _: PointBend("ablate", None, channels), None)
+        else:
+            super().__init__(lambda m: PointBend("multiply", (th.as_tensor(m) <= 0.5).float(), channels), modulation)
+
+
+class Invert(NetworkBend):
+    """x -> 1 - x on the channels ``channels``."""
+
+    def __init__(self, channels=None):
+        super().__init__(lambda _: PointBend("invert", None, channels), None)
+
+
+class ScalarMultiply(NetworkBend):
+    def __init__(self, modulation, channels=None):
+        super().__init__(lambda m: PointBend("multiply", m, channels), modulation)
+
+
+class BinaryThreshold(NetworkBend):
+    """x -> 1 where x exceeds the frame's modulation, else 0."""
+
+    def __init__(self, modulation, channels=None):
+        super().__init__(lambda m: PointBend("threshold", m, channels), modulation)
+
+
+class Erode(NetworkBend):
+    """Minimum over a square window of radius round(modulation) pixels (0 .. 16) around every pixel."""
+
+    def __init__(self, modulation, channels=None):
+        super().__init__(lambda m: MorphBend("erode", th.round(th.as_tensor(m).float()), channels), modulation)
+
+
+class Dilate(NetworkBend):
+    """Maximum over a square window of radius round(modulation) pixels (0 .. 16) around every pixel."""
+
+    def __init__(self, modulation, channels=None):
+        super().__init__(lambda m: MorphBend("dilate", th.round(th.as_tensor(m).float()), channels), modulation)
