@@ -464,6 +464,17 @@ int maua_bend_point_f32(const float* x, float* y, int batch, int channels, int64
 #define MAUA_BEND_MAX_RADIUS 16
 int maua_bend_morph_f32(const float* x, float* y, int batch, int channels, int h, int w, int op, const int32_t* radius, int radius_rows,
                         const uint8_t* chan_mask, const maua_frame_source_t* src, void* stream);
+/* Padding bend (additive to ABI 8; audioreactive/bend.py: Pad): y [batch, channels, h + pad_t + pad_b, w + pad_l + pad_r] =
+ * torch.nn.functional.pad(x, (pad_l, pad_r, pad_t, pad_b), mode, value) + noise — the layer-0 transform that widens the 4 x 4 constant to
+ * the 4 x 8 (8 x 4) one of a 1920 (1080) render.  mode 0 constant (filled with `value`), 1 replicate, 2 reflect (every pad < its axis),
+ * 3 circular (every pad <= its axis); the four pads are independent and >= 0.  noise: NULL, or a static plane [noise_channels, padded h,
+ * padded w] with noise_channels 1 (shared by the channels) or `channels`, added with one fp32 add: the result is bit-defined, a NaN or
+ * an infinity of x or `value` is carried through.  Nothing is per frame, so there is no frame source: a captured launch is static.
+ * 16-byte stores where the padded width is a multiple of 4 and y (and noise) are 16-byte aligned, element by element otherwise.
+ * batch <= 64, channels <= 65535, planes below 2 GiB; y == x is refused.  MAUA_EINVAL on null or non-positive arguments, a negative pad, an
+ * unknown mode, a reflect / circular pad beyond its limit, or a noise_channels other than 1 / channels. */
+int maua_bend_pad_f32(const float* x, float* y, int batch, int channels, int h, int w, int pad_l, int pad_r, int pad_t, int pad_b,
+                      int mode, float value, const float* noise, int noise_channels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ hipGraph runtime
  * Capture everything launched on `stream` between begin/end into a hipGraph and replay it (per-frame generator

@@ -256,6 +256,81 @@ class MorphBend(_ChannelBend):
         return y
 
 
+_PAD_MODES = {"constant": 0, "replicate": 1, "reflect": 2, "circular": 3}  # `mode` of maua_bend_pad_f32
+
+
+class Pad(th.nn.Module):
+    """y = torch.nn.functional.pad(x, padding, mode, value) (+ noise) in one launch of maua_bend_pad_f32: the capturable form of the
+    examples' layer-0 transform ``Sequential(ReplicationPad2d((2, 2, 0, 0)), AddNoise(noise))`` that widens the 4 x 4 constant for a
+    2:1 render.  ``padding`` = (left, right, top, bottom), each >= 0; ``noise``: a static plane of the PADDED size, [H, W], [1 or C, H, W]
+    or [1, 1 or C, H, W].  Nothing is per frame.  A static bend that changes the map's shape says so through ``static_shape``: the
+    captured forward sizes the output buffer with it (ManipulationLayer.run)."""
+
+    capturable = True
+    sequence_rows = None
+
+    def __init__(self, padding, mode="replicate", value=0.0, noise=None):
+        super().__init__()
+        padding = tuple(padding)
+        if len(padding) != 4 or any(int(p) != p for p in padding):
+            raise ValueError(f"padding must be four whole numbers (left, right, top, bottom), got {padding}")
+        padding = tuple(int(p) for p in padding)
+        if min(padding) < 0:
+            raise ValueError(f"pads must not be negative (got {padding}): cropping is not a padding bend")
+        if mode not in _PAD_MODES:
+            raise ValueError(f"unknown padding mode {mode!r} ({' | '.join(_PAD_MODES)})")
+        if noise is not None:
+            noise = th.as_tensor(noise)
+            if noise.dim() not in (2, 3, 4) or (noise.dim() == 4 and noise.shape[0] != 1):
+                raise ValueError(f"bend noise must be one static plane [H, W], [C, H, W] or [1, C, H, W] (got shape {tuple(noise.shape)})")
+            noise = noise.reshape((-1,) + tuple(noise.shape[-2:])).float()
+        self.padding, self.mode, self.value, self.noise = padding, mode, float(value), noise
+        self._dev = {}  # device -> the noise plane there; entries are never evicted: a captured graph keeps reading them
+
+    def static_shape(self, shape):
+        """Shape of the padded map for an input of ``shape`` [B, C, h, w]; refuses what the kernel refuses."""
+        b, c, h, w = (int(v) for v in shape)
+        left, right, top, bottom = self.padding
+        if self.mode == "reflect" and (max(left, right) >= w or max(top, bottom) >= h):
+            raise RuntimeError(f"reflect pads {self.padding} must be smaller than the map ({h} x {w})")
+        if self.mode == "circular" and (max(left, right) > w or max(top, bottom) > h):
+            raise RuntimeError(f"circular pads {self.padding} must not exceed the map ({h} x {w})")
+        return (b, c, h + top + bottom, w + left + right)
+
+    def _noise_plane(self, x, shape):
+        if self.noise is None:
+            return None
+        if tuple(self.noise.shape[1:]) != tuple(shape[2:]) or self.noise.shape[0] not in (1, shape[1]):
+            raise RuntimeError(f"bend noise {tuple(self.noise.shape)} does not match the padded map {tuple(shape)}: "
+                               f"expected [1 or {shape[1]}, {shape[2]}, {shape[3]}]")
+        key = str(x.device)
+        if key not in self._dev:
+            self._dev[key] = self.noise.to(x.device).contiguous()
+        return self._dev[key]
+
+    def _launch(self, x, y):
+        b, c, h, w = x.shape
+        if b > 64 or c > 65535:
+            raise RuntimeError(f"bends serve batches of up to 64 frames and maps of up to 65535 channels (got {b} x {c})")
+        nz = self._noise_plane(x, y.shape)
+        with th.cuda.device(x.device):
+            _lib.check(_lib.load().maua_bend_pad_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, *self.padding, _PAD_MODES[self.mode],
+                                                     self.value, _lib.ptr(nz), 0 if nz is None else nz.shape[0],
+                                                     _lib.stream_ptr(x.device)), "maua_bend_pad_f32")
+        return y
+
+    def forward(self, x):
+        x = _lib.require_cuda(x, "x")
+        return self._launch(x, th.empty(self.static_shape(x.shape), dtype=x.dtype, device=x.device))
+
+    def run_static(self, x, out, src):
+        """Inside a captured forward: writes into the static buffer ``out`` of ``static_shape(x.shape)``; ``src`` is unused (nothing is
+        per frame) and nothing is allocated once the noise plane lives on the device (the warm-up forward before the capture)."""
+        if tuple(out.shape) != self.static_shape(x.shape):
+            raise RuntimeError(f"padding bend: output buffer {tuple(out.shape)} for a padded map {self.static_shape(x.shape)}")
+        return self._launch(x, out)
+
+
 def _inverse_maps_translate(t):
     """dst = src + t  ->  src = dst - t (pixels)."""
     t = t.reshape(-1, 2).float()

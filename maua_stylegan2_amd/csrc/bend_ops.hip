@@ -4,6 +4,9 @@
 // profiles/bend_ops.md), 16 bytes per lane where the planes allow it (w, resp. h * w, a multiple
 // of 4 and 16-byte aligned pointers; element by element otherwise).  Per-frame parameters are read on the device through the frame
 // source like the warp's inverse maps (csrc/signal.hip), so one captured launch serves every replay.
+//
+// maua_bend_pad_f32: the padding bend (torch.nn.functional.pad in its four modes, plus a static noise plane) that turns the 4 x 4 constant
+// into the 4 x 8 one of a 2:1 render.  A pure gather: one thread per 4 consecutive output elements, source indices computed per element.
 #include "common.h"
 
 namespace {
@@ -165,6 +168,60 @@ __global__ __launch_bounds__(256) void bend_morph_kernel(const float* __restrict
 
 bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
+// Source index along an axis of length n for the padded position i (relative to the source: -pad_before .. n - 1 + pad_after), by the
+// rules of torch.nn.functional.pad; -1: the constant fill.  The entry guarantees pad < n (reflect) and pad <= n (circular), so one fold
+// or one wrap lands inside [0, n).
+__device__ __forceinline__ int pad_source(int mode, int i, int n) {
+    if (i >= 0 && i < n) return i;
+    switch (mode) {
+        case 0: return -1;
+        case 1: return i < 0 ? 0 : n - 1;
+        case 2: return i < 0 ? -i : 2 * (n - 1) - i;
+        default: return i < 0 ? i + n : i - n;
+    }
+}
+
+// grid (ceil(planes * quads / blockDim)); a thread owns 4 consecutive elements (a quad) of one padded plane of oh x ow elements, `quads`
+// = ceil(oh ow / 4) of them per plane.  VEC (ow % 4 == 0, y and noise 16-byte aligned): the quad lies in one row and leaves as one 16-byte
+// store; otherwise element by element, across row ends.  The noise is added with one fp32 add, nothing else is computed on a value.
+template <bool VEC>
+__global__ __launch_bounds__(256) void bend_pad_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t planes, int channels,
+                                                       int h, int w, int oh, int ow, int pad_l, int pad_t, int mode, float value,
+                                                       const float* __restrict__ noise, int noise_channels, int quads) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= planes * quads) return;
+    const int64_t plane = q / quads;  // b * channels + c
+    const int e = (int)(q - plane * quads) * 4;
+    const int ohw = oh * ow;
+    const float* xp = x + (size_t)plane * ((size_t)h * w);
+    float* yp = y + (size_t)plane * (size_t)ohw;
+    const float* np = !noise ? nullptr : noise + (noise_channels == 1 ? (size_t)0 : (size_t)(plane % channels) * (size_t)ohw);
+    int i = e / ow, j = e - i * ow;
+    const int n = ohw - e < 4 ? ohw - e : 4;  // (VEC: always 4)
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = 0.f;
+        if (k < n) {
+            const int sy = pad_source(mode, i - pad_t, h), sx = pad_source(mode, j - pad_l, w);
+            v[k] = sy < 0 || sx < 0 ? value : xp[(size_t)sy * w + sx];
+            if (++j == ow) j = 0, ++i;
+        }
+    }
+    if (VEC) {
+        float4 out = make_float4(v[0], v[1], v[2], v[3]);
+        if (np) {
+            const float4 z = *reinterpret_cast<const float4*>(np + e);
+            out = make_float4(out.x + z.x, out.y + z.y, out.z + z.z, out.w + z.w);
+        }
+        *reinterpret_cast<float4*>(yp + e) = out;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) yp[e + k] = np ? v[k] + np[e + k] : v[k];
+    }
+}
+
 }  // namespace
 
 extern "C" int maua_bend_point_f32(const float* x, float* y, int batch, int channels, int64_t hw, int op, const float* param,
@@ -200,6 +257,31 @@ extern "C" int maua_bend_morph_f32(const float* x, float* y, int batch, int chan
     else
         hipLaunchKernelGGL(bend_morph_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, y, channels, h, w, tiles_x, op, radius,
                            radius_rows, chan_mask, src);
+    MAUA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int maua_bend_pad_f32(const float* x, float* y, int batch, int channels, int h, int w, int pad_l, int pad_r, int pad_t, int pad_b,
+                                 int mode, float value, const float* noise, int noise_channels, void* stream) {
+    if (!x || !y || x == y || batch <= 0 || batch > 64 || channels <= 0 || channels > 65535 || h <= 0 || w <= 0) return MAUA_EINVAL;
+    if (pad_l < 0 || pad_r < 0 || pad_t < 0 || pad_b < 0 || mode < 0 || mode > 3) return MAUA_EINVAL;
+    if (mode == 2 && (pad_l >= w || pad_r >= w || pad_t >= h || pad_b >= h)) return MAUA_EINVAL;
+    if (mode == 3 && (pad_l > w || pad_r > w || pad_t > h || pad_b > h)) return MAUA_EINVAL;
+    if (noise && noise_channels != 1 && noise_channels != channels) return MAUA_EINVAL;
+    const int64_t oh = (int64_t)h + pad_t + pad_b, ow = (int64_t)w + pad_l + pad_r;
+    if ((int64_t)h * w >= (int64_t)1 << 29 || oh >= (int64_t)1 << 29 || ow >= (int64_t)1 << 29 || oh * ow >= (int64_t)1 << 29) return MAUA_EINVAL;
+    const int64_t planes = (int64_t)batch * channels;
+    const int quads = (int)((oh * ow + 3) / 4);
+    const int threads = planes * quads <= 64 ? 64 : 256;
+    const int64_t blocks = ceil_div64(planes * quads, threads);
+    if (blocks > 0x7fffffff) return MAUA_EINVAL;
+    const dim3 grid((unsigned)blocks);
+    if (ow % 4 == 0 && aligned16(y, noise))
+        hipLaunchKernelGGL(bend_pad_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, x, y, planes, channels, h, w, (int)oh, (int)ow,
+                           pad_l, pad_t, mode, value, noise, noise_channels, quads);
+    else
+        hipLaunchKernelGGL(bend_pad_kernel<false>, grid, dim3(threads), 0, (hipStream_t)stream, x, y, planes, channels, h, w, (int)oh, (int)ow,
+                           pad_l, pad_t, mode, value, noise, noise_channels, quads);
     MAUA_LAUNCH_CHECK();
     return 0;
 }

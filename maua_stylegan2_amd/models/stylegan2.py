@@ -452,12 +452,15 @@ class ManipulationLayer(nn.Module):
     def run(self, x, bends, bufs, tag, src=None):
         """Device path.  Eager (``src`` None): as ``forward``.  Inside a captured forward every bend is a module with the
         ``run_static(x, out, src)`` protocol (audioreactive/bend.py): it writes into a static buffer and reads its per-frame
-        parameters through the frame source, so one captured graph serves every batch of the render."""
+        parameters through the frame source, so one captured graph serves every batch of the render.  A bend that changes the map's
+        shape (audioreactive/bend.py: Pad) gives the shape of its output through ``static_shape``."""
         if src is None:
             return self.forward(x, bends)
         for i, bd in enumerate(bends):
             if bd["layer"] == self.layer:
-                x = bd["transform"].run_static(x, bufs(f"{tag}.bend{i}", tuple(x.shape)), src)
+                transform = bd["transform"]
+                shape = transform.static_shape(tuple(x.shape)) if hasattr(transform, "static_shape") else tuple(x.shape)
+                x = transform.run_static(x, bufs(f"{tag}.bend{i}", shape), src)
         return x
 
 
