@@ -430,6 +430,21 @@ int maua_rec_affinity_f32(const float* links, int s, float bandwidth, float* rec
 /* 3-D tileable Perlin noise (audioreactive/latent.py:188-246): grad [r0+1,r1+1,r2+1,3] -> out [n0,n1,n2]. */
 int maua_perlin3d_f32(const float* grad, float* out, int n0, int n1, int n2, int r0, int r1, int r2, void* stream);
 
+/* Looping latent sequences (additive to ABI 8; audioreactive/latent.py spline_loops, slerp_loops, loop_sections; csrc/latent_loops.hip).
+ * A cubic-spline or great-circle loop through a set of keys is linear in the keys once the knot count and period (the leg angles) are
+ * fixed, so a whole sectioned sequence is one gather-and-blend over a bank of keys:
+ *   out[f, :] = sum_i weights[row_of_frame[f], i] * bank[key_idx[sec_of_frame[f], i], :]
+ * bank [n_bank, feats], key_idx [n_sections, kmax] (int32 rows of bank), weights [n_rows, kmax] (columns a section does not use hold 0),
+ * row_of_frame / sec_of_frame [n_frames] (int32), out [n_frames, feats].  Per element the sum is the chain acc = fmaf(w_i, key_i, acc) for
+ * i ascending from acc = 0, in which a weight that is exactly 0 leaves acc as it is: a frame's bits depend on its weight row and its keys
+ * alone, not on kmax, the tables around it, the tile or the launch.  16-byte loads and stores where feats % 4 == 0 and bank and out are
+ * 16-byte aligned, element by element otherwise, with the same bits.  Indices found in the tables are clamped into their tables on the
+ * device.  n_frames == 0 is a successful no-op; MAUA_EINVAL, without a launch, on a null pointer, a non-positive size or kmax >
+ * MAUA_LOOP_MAX_KEYS. */
+#define MAUA_LOOP_MAX_KEYS 32
+int maua_keyframe_blend_f32(const float* bank, int n_bank, int feats, const int* key_idx, const float* weights, const int* row_of_frame,
+                            const int* sec_of_frame, float* out, int n_frames, int n_sections, int n_rows, int kmax, void* stream);
+
 /* Network-bending warp (audioreactive/bend.py:52-102): per-frame inverse affine map m[b] = {a00,a01,a02,a10,a11,a12}
  * (output pixel -> source pixel, in pixels), bilinear sampling of the reflect-padded source, zeros outside the padded
  * canvas (kornia warp_affine default padding_mode='zeros', align_corners as encoded by the host in m). */

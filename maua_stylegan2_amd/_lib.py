@@ -127,6 +127,7 @@ _SIGNATURES = {
     "maua_knn_links_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "maua_rec_affinity_f32": (c_int, [_P, c_int, c_float, _P, _P, _P]),
     "maua_perlin3d_f32": (c_int, [_P, _P] + [c_int] * 6 + [_P]),
+    "maua_keyframe_blend_f32": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P] + [c_int] * 4 + [_P]),
     "maua_affine_reflect_warp_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P]),
     "maua_affine_reflect_warp_mapped_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, _P, _P, _P]),
     "maua_bend_point_f32": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, _P, c_int, _P, _P, _P]),
