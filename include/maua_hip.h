@@ -104,6 +104,43 @@ typedef struct {
 int maua_randn_frames_f32(const maua_randn_slot_t* table, int n_slots, int batch, uint64_t seed, int frame0, maua_frame_source_t* src,
                           void* stream);
 
+/* Synthesised noise slots (additive to ABI 8; audioreactive/noise.py NoiseSynth, csrc/noise_synth.hip).  What an audio-reactive plugin does
+ * with noise — blending short loops by envelopes, gating fields by a static mask — is a sum of at most MAUA_NOISE_SYNTH_MAX_TERMS terms, so
+ * the maps of a slot are produced per launch from a recipe instead of living in HBM as a [n_frames, 1, h, w] sequence (36 GB for one 1024^2
+ * slot of a 9000-frame track; a 110-frame loop is 0.45 GB).  The table lives in DEVICE memory and is read by every launch, the seed included:
+ * a captured launch is re-bound to another render by rewriting the table, and only `frame0` is a kernel argument.
+ * Frames: local frame of sample b  f = b (src == NULL) or src->frame0 + b (read on the device); absolute frame  F = frame0 + f, `frame0`
+ * being the absolute frame at which the bound sequences (the envelopes) start, as for maua_randn_frames_f32.  For every entry with
+ * n_terms >= 1, dst != NULL and hw >= 1 (others are skipped), sample b and element e:
+ *   dst[b * hw + e] = gain * sum_{k < n_terms} envelope_k[f] * mask_k[e] * v_k
+ *   v_k = bank_k[((F + phase_k) mod period_k) * hw + e]                                      for a bank term,
+ *       = the counter-based N(0,1) value of (seed, F, slot, e) exactly as maua_randn_frames_f32 defines it   for the NULL-bank term (at most one).
+ * In fp32, in term order: acc = 0; acc = fma(round(envelope_k * mask_k), v_k, acc); then round(gain * acc) — the same bits whatever the
+ * batch, the access width or the launch.  16-byte loads and stores for the samples whose dst, bank rows and masks are all 16-byte aligned
+ * (hw % 4 != 0 makes every odd sample unaligned), element by element otherwise.  n_terms above the maximum is clamped; the per-entry values
+ * (periods, phases, envelope lengths >= the frames used) are the caller's to validate: the device only keeps a period below 1 from dividing.
+ * With src the launch points the frame source at the maps as maua_randn_frames_f32 does:
+ *   src->noise[slot] = dst - src->frame0 * hw,  src->noise_stride[slot] = hw        (slot in 0 .. MAUA_MAX_NOISE_SLOTS-1, entry not skipped).
+ * MAUA_EINVAL, before any HIP call: table == NULL, n_slots outside 1 .. MAUA_MAX_NOISE_SLOTS, batch < 1, frame0 < 0. */
+#define MAUA_NOISE_SYNTH_MAX_TERMS 4
+typedef struct {
+    const float* bank;      /* [period, hw] loop; NULL: the counter-based N(0,1) map of (seed, absolute frame, slot) */
+    const float* envelope;  /* [n_frames of the bound sequences] or NULL (= 1) */
+    const float* mask;      /* [hw] or NULL (= 1) */
+    int32_t period;         /* >= 1 when bank != NULL */
+    int32_t phase;          /* 0 .. period-1 */
+} maua_noise_term_t;
+typedef struct {
+    float* dst;             /* [batch, hw] */
+    int32_t hw;             /* floats per map */
+    int32_t slot;           /* third counter word of the NULL-bank term; with src also the noise slot of the frame source */
+    int32_t n_terms;        /* 0: entry skipped */
+    float gain;
+    uint64_t seed;          /* of the NULL-bank term */
+    maua_noise_term_t term[MAUA_NOISE_SYNTH_MAX_TERMS];
+} maua_noise_synth_slot_t;
+int maua_noise_synth_f32(const maua_noise_synth_slot_t* table, int n_slots, int batch, int frame0, maua_frame_source_t* src, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ generator layers
  * THE STYLE FOLD (ABI 4).  ModulatedConv2d multiplies its input by the per-sample styles before the shared-weight contraction
  * (models/stylegan2.py:220-221, w = scale * W * s  <=>  conv(scale * W, x * s)).  Every feature map of the generator has exactly one

@@ -57,6 +57,22 @@ class RandnSlot(ctypes.Structure):
     _fields_ = [("dst", c_void_p), ("hw", ctypes.c_int32), ("slot", ctypes.c_int32)]
 
 
+NOISE_SYNTH_MAX_TERMS = 4
+
+
+class NoiseTerm(ctypes.Structure):
+    """maua_noise_term_t (include/maua_hip.h): one term of a synthesised noise slot."""
+
+    _fields_ = [("bank", c_void_p), ("envelope", c_void_p), ("mask", c_void_p), ("period", ctypes.c_int32), ("phase", ctypes.c_int32)]
+
+
+class NoiseSynthSlot(ctypes.Structure):
+    """maua_noise_synth_slot_t (include/maua_hip.h): the recipe of one noise slot of a maua_noise_synth_f32 launch."""
+
+    _fields_ = [("dst", c_void_p), ("hw", ctypes.c_int32), ("slot", ctypes.c_int32), ("n_terms", ctypes.c_int32), ("gain", c_float),
+                ("seed", ctypes.c_uint64), ("term", NoiseTerm * NOISE_SYNTH_MAX_TERMS)]
+
+
 _P = c_void_p
 _SIGNATURES = {
     "maua_abi_version": (c_int, []),
@@ -69,6 +85,7 @@ _SIGNATURES = {
     "maua_upfirdn2d_f64": (c_int, [_P, _P, _P] + [c_int] * 14 + [_P]),
     "maua_frame_source_seek": (c_int, [_P, c_int, _P]),
     "maua_randn_frames_f32": (c_int, [_P, c_int, c_int, ctypes.c_uint64, c_int, _P, _P]),
+    "maua_noise_synth_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "maua_blur_noise_act_f32": (c_int, [_P, _P, _P] + [c_int] * 8 + [_P, _P, c_int64, _P, _P, _P, c_int, _P, c_int, _P]),
     "maua_upconv_blur_ok": (c_int, [c_int] * 4),
     "maua_upconv_blur_ws_floats": (c_int64, [c_int] * 5),

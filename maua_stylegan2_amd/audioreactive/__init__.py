@@ -3,6 +3,7 @@
 from . import signal as _signal_module
 from .bend import *  # noqa: F401,F403
 from .latent import *  # noqa: F401,F403
+from .noise import *  # noqa: F401,F403  (NoiseSynth, noise_term: synthesised noise slots, no counterpart in the reference)
 from .signal import *  # noqa: F401,F403
 from .signal import set_SMF  # noqa: F401
 from ..models.stylegan2 import Generator  # noqa: F401,E402  (the reference's latent.py leaks it into ar.* through its star import)

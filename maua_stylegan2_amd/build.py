@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libmaua_hip.so")
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "maua_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "philox.h"), os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "maua_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -30,6 +30,8 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     srcs = _sources()
     objs = [s[:-4] + ".o" for s in srcs]
+    if not force and not _stale(LIB, srcs + HEADERS):
+        return LIB  # a library newer than every source and header is current, with or without the objects it was linked from
 
     def compile_one(pair):
         src, obj = pair

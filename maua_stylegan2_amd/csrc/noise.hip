@@ -2,43 +2,11 @@
 // (seed, absolute frame, slot) is a pure function — Philox4x32-10 (Salmon et al., SC'11) + Box-Muller — so one table-driven launch at
 // the head of a captured forward fills the maps of every randomised layer of one batch, identically for every batch size, lane and shard.
 #include "common.h"
+#include "philox.h"  // philox4x32_10, box_muller: shared with csrc/noise_synth.hip
 
 namespace {
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
-constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-typedef __attribute__((address_space(1))) float global_float;
-typedef float vec4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) vec4f global_vec4f;
-
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(PHILOX_M0, c.x), lo0 = PHILOX_M0 * c.x;
-        const uint32_t hi1 = __umulhi(PHILOX_M1, c.z), lo1 = PHILOX_M1 * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += PHILOX_W0;
-        k1 += PHILOX_W1;
-    }
-    return c;
-}
-
-// u = ((x >> 9) + 0.5) * 2^-23: 24 significant bits, exact in fp32, inside (0, 1)
-__device__ __forceinline__ float unit_open(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-
-// (r cos 2 pi u1, r sin 2 pi u1), r = sqrt(-2 ln u0).  sincospif takes the angle in half turns: 2 u1 is exact, no rounded 2 pi u1.
-__device__ __forceinline__ void box_muller(uint32_t x0, uint32_t x1, float& a, float& b) {
-    const float r = sqrtf(-2.0f * logf(unit_open(x0)));
-    float sn, cs;
-    sincospif(2.0f * unit_open(x1), &sn, &cs);
-    a = r * cs;
-    b = r * sn;
-}
+using namespace maua_philox;
 
 // One thread = four consecutive floats of one map.  The table lives in device memory, so the host cannot size the grid by it: every
 // workgroup builds the prefix sums of the slots' quad counts (<= 32 entries) in LDS and the grid strides over their total.

@@ -163,7 +163,9 @@ def _collect_noise(get_noise, args, out_size, G_res, stylegan1, header=None):
     for scale in range(first, stop):
         side = 2 ** log_side(scale)
         nz = get_noise(height=mul_h * side, width=mul_w * side, scale=scale - first, num_scales=stop - first, args=args)
-        if nz is not None:
+        if isinstance(nz, ar.NoiseSynth) and (nz.height, nz.width) != (mul_h * side, mul_w * side):
+            raise RuntimeError(f"get_noise returned a NoiseSynth of {nz.height} x {nz.width} maps for the {mul_h * side} x {mul_w * side} scale")
+        if nz is not None:  # (a recipe's amplitude comes from a bounded sample of its frames: nothing is materialised)
             shown.append((list(nz.shape), nz.std()))  # (printed below: formatting a device scalar is a host sync per scale)
         maps.append(nz)
     if header is not None:
@@ -184,14 +186,32 @@ def _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames):
     dev = th.device("cuda", th.cuda.current_device()) if th.cuda.is_available() else th.device("cpu")
     on_dev = lambda t: None if t is None else t.to(dev, th.float32).contiguous()  # noqa: E731
     latents = sharding.scatter_frames(on_dev(latents), n_frames, device=dev)
-    n_noise = sharding.broadcast_object(len(noise) if rank == 0 else None)
-    noise = [sharding.scatter_frames(on_dev(noise[i]) if rank == 0 else None, n_frames, device=dev) for i in range(n_noise)]
+    # NoiseSynth recipes are broadcast, not scattered: their structure rides along with the slot count (a job without recipes sends the
+    # plain count, as before), their tensors — loops, envelopes, masks: small next to a per-frame sequence — follow one by one, and every
+    # rank cuts its frames out with ``window``, which copies nothing
+    lo, hi = sharding.shard_bounds(n_frames, rank, world)
+    recipes = {i: nz for i, nz in enumerate(noise) if isinstance(nz, ar.NoiseSynth)} if rank == 0 else {}
+    head = sharding.broadcast_object((len(noise) if not recipes else (len(noise), {i: nz.structure() for i, nz in recipes.items()}))
+                                     if rank == 0 else None)
+    n_noise, structures = head if isinstance(head, tuple) else (head, {})
+    noise = list(noise) if rank == 0 else [None] * n_noise
+    for i in range(n_noise):
+        if i in structures:
+            recipe = noise[i] if rank == 0 else ar.NoiseSynth.from_structure(structures[i], dev)
+            if recipe.device != dev:
+                raise RuntimeError(f"noise[{i}]: the recipe lives on {recipe.device}, this rank renders on {dev}")
+            for t in recipe.tensors():
+                sharding.broadcast_tensor(t)
+            if recipe.n_frames is not None and recipe.n_frames != n_frames:
+                raise RuntimeError(f"noise[{i}]: the recipe's envelopes cover {recipe.n_frames} frames, the job has {n_frames}")
+            noise[i] = recipe.window(lo, hi)
+        else:
+            noise[i] = sharding.scatter_frames(on_dev(noise[i]) if rank == 0 else None, n_frames, device=dev)
     is_float = sharding.broadcast_object(isinstance(truncation, float) if rank == 0 else None)
     if is_float:
         truncation = float(sharding.broadcast_object(truncation if rank == 0 else None))
     else:
         truncation = sharding.scatter_frames(on_dev(truncation) if rank == 0 else None, n_frames, device=dev)
-    lo, hi = sharding.shard_bounds(n_frames, rank, world)
     for bend in bends:
         if "modulation" in bend:
             bend["modulation"] = sharding.broadcast_tensor(on_dev(bend["modulation"]))[lo:hi]

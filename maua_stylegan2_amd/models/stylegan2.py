@@ -1160,7 +1160,8 @@ class Generator(nn.Module):
         modified tensor invalidates the packed weights, style tables and therefore the graph)."""
         return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
 
-    def capture_graph(self, batch, lane=0, frames_u8=False, bends=(), random_slots=(), noise_seed=0, noise_frame_offset=0):
+    def capture_graph(self, batch, lane=0, frames_u8=False, bends=(), random_slots=(), noise_seed=0, noise_frame_offset=0, synth_slots=(),
+                      synth_frame_offset=0):
         """Capture one forward of ``batch`` frames into a hipGraph and return its ``GraphLane``.  The captured kernels read
         their per-frame inputs (latents, truncation, noise maps, bend parameters) THROUGH a frame source in device memory
         (include/maua_hip.h): ``lane.bind(latents, noise, truncation)`` points it at sequences resident in HBM — any render,
@@ -1171,7 +1172,12 @@ class Generator(nn.Module):
         ``random_slots``: noise slots whose maps the captured forward GENERATES per replay (``randomize_noise``): it then starts with one
         maua_randn_frames_f32 launch that fills lane-private [batch, 1, h, w] buffers with the maps of (``noise_seed``, frame
         ``noise_frame_offset`` + frame0 + b, slot) — what ``random_noise`` returns for those frames — and points the frame source at them;
-        ``bind`` takes None for these slots.  Seed and offset are kernel arguments: part of the graph."""
+        ``bind`` takes None for these slots.  Seed and offset are kernel arguments: part of the graph.
+        ``synth_slots``: noise slots whose maps the captured forward SYNTHESISES per replay from a recipe (audioreactive/noise.py NoiseSynth):
+        one maua_noise_synth_f32 launch, behind the maua_randn_frames_f32 one, fills lane-private [batch, 1, h, w] buffers from a lane-private
+        table in device memory and points the frame source at them; ``bind`` takes a NoiseSynth for exactly these slots and writes the table,
+        so another render's recipes need no new capture.  Only ``synth_frame_offset`` (the recipes' frame offset: 0, or a shard's first frame)
+        is a kernel argument.  The two slot sets are disjoint."""
         dev = self.input.input.device
         if th.cuda.current_stream(dev).cuda_stream == 0:
             raise RuntimeError("capture_graph must run on a non-default stream (with torch.cuda.stream(s): ...): HIP cannot "
@@ -1187,7 +1193,18 @@ class Generator(nn.Module):
                 random_slots = tuple(self._noise_slots(random_slots)) if len(random_slots) else ()
                 generated = {i: self._buf(batch, f"g.randn_{i}", (batch, 1) + tuple(getattr(self.noises, f"noise_{i}").shape[-2:]))
                              for i in random_slots}
-                source = FrameSource(self, batch, lane, generated)
+                synth_slots = tuple(self._noise_slots(synth_slots)) if len(synth_slots) else ()
+                if set(synth_slots) & set(random_slots):
+                    raise RuntimeError(f"noise slots {sorted(set(synth_slots) & set(random_slots))} are both random_slots and synth_slots")
+                if not 0 <= int(synth_frame_offset) < 2 ** 31:
+                    raise RuntimeError(f"synth_frame_offset {synth_frame_offset} out of range")
+                synthesised = {i: self._buf(batch, f"g.synth_{i}", (batch, 1) + tuple(getattr(self.noises, f"noise_{i}").shape[-2:]))
+                               for i in synth_slots}
+                synth_table = None
+                if synth_slots:  # all zero = every entry empty: the launch is a no-op until ``bind`` has written the recipes
+                    synth_table = self._buf(batch, "g.synth_table", (len(synth_slots) * ctypes.sizeof(_lib.NoiseSynthSlot),), dtype=th.uint8)
+                    synth_table.zero_()
+                source = FrameSource(self, batch, lane, generated, synthesised, synth_table, int(synth_frame_offset))
                 randn_table = self._randn_table(random_slots, [generated[i] for i in random_slots]) if random_slots else None
                 u8 = None
                 if frames_u8:
@@ -1200,6 +1217,9 @@ class Generator(nn.Module):
                         _lib.check(_lib.load().maua_randn_frames_f32(randn_table.data_ptr(), len(random_slots), batch, int(noise_seed),
                                                                      int(noise_frame_offset), source.ptr, _lib.stream_ptr(dev)),
                                    "maua_randn_frames_f32")
+                    if synth_table is not None:  # the table is read on every replay: whatever ``bind`` wrote last
+                        _lib.check(_lib.load().maua_noise_synth_f32(synth_table.data_ptr(), len(synth_slots), batch, int(synth_frame_offset),
+                                                                    source.ptr, _lib.stream_ptr(dev)), "maua_noise_synth_f32")
                     return self._forward_device(None, None, None, tl, bends, frames_u8=u8, src=source.ptr, batch=batch)
 
                 run()  # warm-up: allocates every static buffer, packs the weights
@@ -1210,6 +1230,7 @@ class Generator(nn.Module):
             lane_ = GraphLane(self, graph, source, image, u8, tl, batch, lane, self.weights_key())
             lane_.random_slots, lane_.noise_seed, lane_.noise_frame_offset = random_slots, int(noise_seed), int(noise_frame_offset)
             lane_._randn_table = randn_table  # the captured launch reads it on every replay
+            lane_.synth_slots, lane_.synth_frame_offset = synth_slots, int(synth_frame_offset)
             return lane_
         finally:
             self._lane = 0
@@ -1219,12 +1240,16 @@ class FrameSource:
     """Host handle of a maua_frame_source_t in device memory (include/maua_hip.h): the pointers of the HBM-resident per-frame
     sequences a captured forward reads, plus the frame it starts at."""
 
-    def __init__(self, generator, batch, lane, generated=None):
+    def __init__(self, generator, batch, lane, generated=None, synthesised=None, synth_table=None, synth_frame_offset=0):
         self.generator = generator
         self.batch = batch
         # slot -> lane-private [batch, 1, h, w] buffer the captured forward fills itself (capture_graph's random_slots); its first launch
         # rewrites the slot's pointer / stride on every replay, so what ``bind`` leaves there is never read: one valid map, stride 0
         self.generated = dict(generated or {})
+        # slot -> lane-private buffer the captured forward synthesises from the recipe ``bind`` wrote into ``synth_table`` (capture_graph's
+        # synth_slots; one maua_noise_synth_slot_t per slot, in slot order); the launch rewrites pointer and stride like the random one
+        self.synthesised = dict(synthesised or {})
+        self.synth_table, self.synth_frame_offset = synth_table, int(synth_frame_offset)
         self.dev = generator._buf(batch, "g.frame_source", (ctypes.sizeof(_lib.FrameSource),), dtype=th.uint8)
         self.ptr = self.dev.data_ptr()
         self._keep = None
@@ -1236,8 +1261,10 @@ class FrameSource:
 
     def bind(self, latents, noise, trunc, _n_frames=None):
         """latents [n_frames, n_latent, style_dim]; noise: per slot None (the checkpoint's buffer for every frame), a
-        [n_frames, 1, h, w] sequence or one shared [1, 1, h, w] map; trunc [n_frames] or None — all fp32, on the device,
-        contiguous; they are kept alive by this handle until the next bind."""
+        [n_frames, 1, h, w] sequence or one shared [1, 1, h, w] map — or, for exactly the lane's synth slots, a NoiseSynth recipe;
+        trunc [n_frames] or None — all fp32, on the device, contiguous; they are kept alive by this handle until ``release``."""
+        from ..audioreactive.noise import NoiseSynth
+
         g = self.generator
         dev = g.input.input.device
         n_frames = latents.shape[0] if _n_frames is None else _n_frames
@@ -1259,7 +1286,30 @@ class FrameSource:
             keep.append(trunc)
         if len(noise) != g.num_layers or g.num_layers > _lib.MAX_NOISE_SLOTS:
             raise RuntimeError(f"{len(noise)} noise entries for {g.num_layers} layers")
+        synth_host = (_lib.NoiseSynthSlot * max(len(self.synthesised), 1))()  # zero = empty entries (the unbound lane)
         for i, nz in enumerate(noise):
+            if i in self.synthesised:
+                if isinstance(nz, NoiseSynth):
+                    if (nz.height, nz.width) != self.noise_hw[i]:
+                        raise RuntimeError(f"noise[{i}]: the recipe makes {nz.height} x {nz.width} maps, the layer takes "
+                                           f"{self.noise_hw[i][0]} x {self.noise_hw[i][1]}")
+                    if nz.n_frames is not None and nz.n_frames != n_frames:
+                        raise RuntimeError(f"noise[{i}]: the recipe's envelopes cover {nz.n_frames} frames, the render has {n_frames}")
+                    if nz.offset != self.synth_frame_offset:
+                        raise RuntimeError(f"noise[{i}]: the recipe starts at frame {nz.offset}, this lane was captured for frame offset "
+                                           f"{self.synth_frame_offset}")
+                    if nz.device != dev:
+                        raise RuntimeError(f"noise[{i}]: the recipe lives on {nz.device}, the generator on {dev}")
+                    synth_host[sorted(self.synthesised).index(i)] = nz.table_entry(self.synthesised[i].data_ptr(), i)
+                    keep.append(nz)
+                elif nz is not None or _n_frames is None:
+                    raise RuntimeError(f"noise[{i}] is synthesised by this lane (synth_slots): bind a NoiseSynth, not "
+                                       f"{'None' if nz is None else 'a tensor'}")
+                host.noise[i] = self.synthesised[i].data_ptr()
+                host.noise_stride[i] = 0
+                continue
+            if isinstance(nz, NoiseSynth):
+                raise RuntimeError(f"noise[{i}] is a NoiseSynth, but this lane was not captured with slot {i} among its synth_slots")
             if i in self.generated:
                 if nz is not None:
                     raise RuntimeError(f"noise[{i}] is generated by this lane (random_slots): bind it as None")
@@ -1280,6 +1330,8 @@ class FrameSource:
         raw = th.frombuffer(bytearray(bytes(host)), dtype=th.uint8)
         th.cuda.synchronize(dev)  # no replay of this lane may still be reading the previous pointers (bind is once per render)
         self.dev.copy_(raw.to(dev), non_blocking=False)
+        if self.synth_table is not None:  # the recipes of this render, under the same two synchronisations as the pointers
+            self.synth_table.copy_(th.frombuffer(bytearray(bytes(synth_host)), dtype=th.uint8).to(dev), non_blocking=False)
         th.cuda.synchronize(dev)
 
     def release(self):
@@ -1304,6 +1356,7 @@ class GraphLane:
         self._trunc_latent = trunc_latent
         self.weights_key = weights_key
         self.random_slots, self.noise_seed, self.noise_frame_offset = (), 0, 0
+        self.synth_slots, self.synth_frame_offset = (), 0
 
     def bind(self, latents, noise, truncation=None):
         """Point the lane at the sequences of a render (see FrameSource.bind).  ``truncation`` [n_frames] switches the

@@ -27,6 +27,7 @@ import numpy as np
 import torch as th
 
 from . import _lib, sharding
+from .audioreactive.noise import NoiseSynth
 
 th.set_grad_enabled(False)
 
@@ -268,30 +269,39 @@ def _lane_stream(dev, k):
 UNSEEDED_GRAPH_MIN_FRAMES = 2048  # randomised renders without generator.noise_seed below this length keep the eager path (synthesize)
 
 
-def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None):
+def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=None):
     """``n_lanes`` captured forwards (GraphLane) of ``batch_size`` frames with uint8 frame output, each on its own stream.
     Without bends they are cached on the generator and reused by every later render (a captured forward reads its inputs
     through a frame source, so nothing about a particular render is baked in); a changed weight drops the cache.  With bends the
     transforms' static operands are part of the graph: captured per call.  ``random`` = (slots, seed, frame offset): lanes that generate
     the noise maps of ``slots`` themselves (``Generator.capture_graph``'s random_slots); cached per slot set next to the static lanes, and
-    captured again when the seed or the offset — kernel arguments of the captured noise launch — differ from the cached lane's."""
+    captured again when the seed or the offset — kernel arguments of the captured noise launch — differ from the cached lane's.
+    ``synth`` = (slots, frame offset): lanes that synthesise the maps of ``slots`` from NoiseSynth recipes (capture_graph's synth_slots); cached
+    per slot set as well.  The recipes live in a device table that ``bind`` rewrites, so another render's recipes reuse the captured graph;
+    only another frame offset (a shard's first frame, the one kernel argument of that launch) captures again."""
     dev = device_of(generator)
     slots, seed, offset = random if random else ((), 0, 0)
     slots = tuple(slots)
+    synth_slots, synth_offset = (tuple(synth[0]), int(synth[1])) if synth else ((), 0)
     key = generator.weights_key()
     cache = generator.__dict__.setdefault("_graph_lanes", {})
     lanes = []
     tap = bool(getattr(generator, "tap_float_image", False))  # (parity tests: such lanes also write the fp32 image — other kernels arguments)
     for k in range(n_lanes):
         stream = _lane_stream(dev, k)
-        cache_key = (batch_size, k, tap) + ((slots,) if slots else ())
+        cache_key = (batch_size, k, tap) + ((slots,) if slots else ()) + ((("synth",) + synth_slots,) if synth_slots else ())
         lane = None if bends else cache.get(cache_key)
         if lane is not None and (lane.weights_key != key or (slots and (lane.noise_seed, lane.noise_frame_offset) != (seed, offset))):
+            lane = None
+        if lane is not None and synth_slots and lane.synth_frame_offset != synth_offset:
             lane = None
         if lane is None:
             stream.wait_stream(th.cuda.current_stream(dev))
             with th.cuda.stream(stream):
-                if slots:
+                if synth_slots:
+                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, random_slots=slots, noise_seed=seed,
+                                                   noise_frame_offset=offset, synth_slots=synth_slots, synth_frame_offset=synth_offset)
+                elif slots:
                     lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, random_slots=slots, noise_seed=seed,
                                                    noise_frame_offset=offset)
                 else:
@@ -352,7 +362,18 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
     n_total = len(latents)
     lo, hi = frame_range if frame_range is not None else (0, n_total)
     latents = latents.to(dev, th.float32).contiguous()  # resident in HBM for the whole render
-    noise = [None if nz is None else nz.to(dev, th.float32).contiguous() for nz in noise]
+    # (a NoiseSynth recipe — audioreactive/noise.py — passes through as it is: its tensors are on the device already)
+    noise = [nz if nz is None or isinstance(nz, NoiseSynth) else nz.to(dev, th.float32).contiguous() for nz in noise]
+    recipes = {i: nz for i, nz in enumerate(noise) if isinstance(nz, NoiseSynth)}
+    synth = None
+    if recipes:
+        offsets = {nz.offset for nz in recipes.values()}
+        if len(offsets) != 1:
+            raise RuntimeError(f"the NoiseSynth recipes of one render must share a frame offset, got {sorted(offsets)}")
+        for i, nz in recipes.items():
+            if nz.n_frames is not None and nz.n_frames != n_total:
+                raise RuntimeError(f"noise[{i}]: the recipe's envelopes cover {nz.n_frames} frames, the render has {n_total}")
+        synth = (tuple(recipes), offsets.pop())
     if isinstance(truncation, (int, float)):
         truncation = float(truncation)
         # a float != 1 (or a generator that carries a truncation latent) must reach the captured graph as well: it becomes a
@@ -400,7 +421,10 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
     caller_stream = th.cuda.current_stream(dev)
     lane_state = []  # (stream, GraphLane or None)
     if capturable and hi - lo >= batch_size:
-        lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random)
+        if synth is None:
+            lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random)
+        else:
+            lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random, synth)
         n_lanes = len(lane_state)
         for stream, lane in lane_state:
             lane.bind(latents, noise, trunc_t)  # once per render: the pointers of the HBM-resident sequences
@@ -424,7 +448,9 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
                     yield n, lane.u8  # the frame epilogue is part of the captured forward (fused into the last ToRGB)
                     k += 1
                     continue
-                noise_batch = [None if nz is None else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in noise]  # [1, ...] = one map for every frame
+                noise_batch = [None if nz is None or isinstance(nz, NoiseSynth) else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in noise]  # [1, ...] = one map for every frame
+                for i, recipe in recipes.items():  # the launch a graph lane makes for these frames, without a frame source
+                    noise_batch[i] = recipe.frames(n, b, i)
                 if random is not None:  # the same maps a graph lane generates for these frames
                     for i, nz in zip(random[0], generator.random_noise(random[2] + n, b, random[1], random[0])):
                         noise_batch[i] = nz
