@@ -193,7 +193,15 @@ int maua_upconv_blur_f32(const float* x, const float* wq, const float* s, int s_
  *      s[b*s_stride + s_off_l + i] = (1/sqrt(style_dim)) * sum_j mod_w_l[i,j] * latent'[b, lat_idx_l, j] + mod_b_l[i]
  *  demod (:223-225) in the shared-weight formulation, for layers with wsq != NULL:
  *      d[d_off_l + b*cout_l + o] = rsqrt( wscale_l^2 * sum_i wsq_l[o,i] * s[b, s_off_l + i]^2 + 1e-8 )
- *  `table` lives in DEVICE memory (n_layers entries). batch <= 64 per call. */
+ *  `table` lives in DEVICE memory (n_layers entries).  Any batch >= 1: both kernels walk the frames 16 at a time.
+ *  trunc != NULL with trunc_latent == NULL: the lerp runs against a zero mean latent, latent' = trunc[b] * latent.  With src the
+ *  latents / trunc arguments are ignored (frame source above); trunc_latent still comes from the argument.
+ *  Limits.  style_dim: a multiple of 64, at most 1024 (MAUA_EINVAL otherwise).  An entry's cin is unlimited for the affine, but an
+ *  entry with wsq != NULL needs cin <= 1024: the demod kernel keeps [16][cin] squared styles in 64 KB of LDS and 16 values per lane.
+ *  The launcher cannot see the table, so that limit is the CALLER's to enforce where the table is built (models/stylegan2.py
+ *  _style_table raises); a wider entry would write past the LDS and drop terms.  max_cin / max_cout >= every entry's cin / cout
+ *  (they size the grid; rows beyond them are not computed).
+ *  MAUA_EINVAL: latents and src both NULL, table / s / d NULL, batch, n_layers, max_cin or max_cout < 1. */
 typedef struct {
     const float* mod_w; /* [cin, style_dim] */
     const float* mod_b; /* [cin] */

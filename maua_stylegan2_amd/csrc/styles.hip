@@ -12,7 +12,7 @@
 namespace {
 
 constexpr int BCHUNK = 16;   // frames staged in LDS per pass
-constexpr int MAX_PER_LANE = 16;  // style_dim, cin <= 1024
+constexpr int MAX_PER_LANE = 16;  // style_dim <= 1024 (checked by the launcher); cin <= 1024 of a demodulated entry (checked where the table is built: include/maua_hip.h)
 constexpr int ROWS = 16;          // output rows per workgroup
 constexpr int RPW = ROWS / 4;     // rows per wave
 

@@ -101,8 +101,23 @@ class EqualLinear(nn.Module):
         return F.linear(inputs, self.weight * self.scale, bias=self.bias * self.lr_mul)
 
 
+DEMOD_MAX_CIN = 1024  # maua_demod_f32 (include/maua_hip.h): [16][cin] squared styles in 64 KB of LDS, 16 values per lane
+
+
+def _check_demod_cin(cin):
+    """maua_demod_f32 cannot see its table (it lives in device memory), so the limit of a demodulated entry is enforced where the table is
+    built: wider, demod_kernel would write past its LDS and drop terms without any error."""
+    if cin > DEMOD_MAX_CIN:
+        raise NotImplementedError(f"demodulation is built for at most {DEMOD_MAX_CIN} input channels (got {cin}): maua_demod_f32 keeps "
+                                  "the squared styles of 16 frames in 64 KB of LDS")
+
+
 def _style_table(entries, device):
-    """entries: list of dict(mod_w, mod_b, wsq|None, cin, cout, lat_idx, s_off, d_off, wscale) -> device byte tensor."""
+    """entries: list of dict(mod_w, mod_b, wsq|None, cin, cout, lat_idx, s_off, d_off, wscale) -> device byte tensor.  Raises for a
+    demodulated entry (wsq given) wider than DEMOD_MAX_CIN, before anything is uploaded."""
+    for e in entries:
+        if e["wsq"] is not None:
+            _check_demod_cin(e["cin"])
     arr = (_lib.StyleLayer * len(entries))()
     for i, e in enumerate(entries):
         arr[i].mod_w = e["mod_w"].data_ptr()
@@ -350,10 +365,12 @@ class ModulatedConv2d(nn.Module):
 def _layer_styles(conv, inputs, style):
     """(checked inputs, s [batch, Cin], d [batch, Cout] or None when ``conv`` does not demodulate) of ONE ModulatedConv2d for ``style``
     [batch, style_dim]: the one-entry form of the generator's style table, for the standalone ``forward`` of the layer classes."""
+    cin, cout = conv.in_channel, conv.out_channel
+    if conv.demodulate:
+        _check_demod_cin(cin)  # (before the weight pack and every other launch)
     lib = _lib.load()
     x, style = _lib.require_cuda(inputs, "inputs"), _lib.require_cuda(style, "style")
     batch, dev = x.shape[0], x.device
-    cin, cout = conv.in_channel, conv.out_channel
     s = th.empty((batch, cin), dtype=th.float32, device=dev)
     d = th.empty((batch, cout), dtype=th.float32, device=dev) if conv.demodulate else None
     with th.cuda.device(dev):

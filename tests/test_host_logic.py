@@ -481,3 +481,22 @@ def test_parked_heap_is_refcounted_and_respects_a_foreign_freeze():
     except RuntimeError:
         pass
     assert gc.get_freeze_count() == 0
+
+
+def test_style_table_refuses_a_demodulated_entry_wider_than_the_demod_kernel(monkeypatch):
+    """maua_demod_f32 stages [16][cin] squared styles in 64 KB of LDS and cannot see its table (device memory): a demodulated entry with
+    cin > 1024 is refused where the table is built, and by the standalone layer path before the library is loaded."""
+    from maua_stylegan2_amd.models import stylegan2
+
+    w = torch.zeros(4)
+    entry = dict(mod_w=w, mod_b=w, wsq=w, cin=1024, cout=8, lat_idx=0, s_off=0, d_off=0, wscale=1.0)
+    assert stylegan2._style_table([entry, dict(entry, wsq=None, cin=8192)], "cpu").numel() > 0  # (the affine has no such limit)
+    with pytest.raises(NotImplementedError, match="1024 input channels"):
+        stylegan2._style_table([entry, dict(entry, cin=1025)], "cpu")
+
+    def no_launch():
+        raise AssertionError("the library was reached before the refusal")
+
+    monkeypatch.setattr(stylegan2._lib, "load", no_launch)
+    with pytest.raises(NotImplementedError, match="1024 input channels"):
+        stylegan2.ModulatedConv2d(1040, 8, 3, 64)(torch.zeros(1, 1040, 4, 4), torch.zeros(1, 64))
