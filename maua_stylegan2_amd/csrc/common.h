@@ -41,16 +41,60 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
     return base + idx;
 }
 
-__device__ __forceinline__ float lrelu_gain(float v) { return (v > 0.f ? v : v * 0.2f) * 1.41421356237309515f; }
+// sqrt(2): the gain of the leaky ReLU (FusedLeakyReLU's scale).  Every tail folds it into gain, bias and noise weight once.
+constexpr float kSqrt2 = 1.41421356237309515f;
+
+__device__ __forceinline__ float lrelu_gain(float v) { return (v > 0.f ? v : v * 0.2f) * kSqrt2; }
+
+// ---- the StyledConv tail (noise, bias, leaky ReLU * sqrt2) as every convolution / blur entry receives it
+// Where this launch's noise comes from: the caller's map, or — with a frame source (include/maua_hip.h) — slot `noise_slot` of the
+// HBM-resident sequence at the launch's first frame.  Uniform scalar loads; the ONE place that knows the frame source's layout.
+template <typename NoisePtr>  // const float*, with or without __restrict__
+__device__ __forceinline__ void maua_noise_source(NoisePtr& noise, int64_t& batch_stride, const maua_frame_source_t* src, int noise_slot) {
+    if (src) {
+        batch_stride = src->noise_stride[noise_slot];
+        noise = src->noise[noise_slot];
+        if (noise) noise += (int64_t)src->frame0 * batch_stride;
+    }
+}
+
+struct TailArgs {
+    const float* noise;          // [B or 1, H, W] or null
+    const float* noise_w;        // [1]
+    const float* bias;           // [Cout] or null
+    int64_t noise_batch_stride;
+    const maua_frame_source_t* src;  // when set: noise / noise_batch_stride come from src->noise[noise_slot] at frame src->frame0
+    int noise_slot;
+
+    // The entries' argument check (0 or MAUA_EINVAL).  tail_applied = false: this launch stores the raw map, a frame source's noise is
+    // not read and its weight may be absent (maua_modconv3x3_f32 without fuse_act).
+    int check(bool tail_applied = true) const {
+        if ((noise || (src && tail_applied)) && !noise_w) return MAUA_EINVAL;
+        if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+        return 0;
+    }
+};
+
+// fused ToRGB (models/stylegan2.py:346-365) of a plain StyledConv
+struct RgbArgs {
+    const float* w;      // [3, Cout]
+    const float* s;      // styles of the ToRGB layer, [B, s_stride] (already offset to the layer's slice)
+    const float* bias;   // [3]
+    const float* skip;   // [B, 3, H/2, W/2] or null
+    const float* k4;     // 4x4 upsample taps
+    float* out;          // [B, 3, H, W]; mode 3: [B, 3 m_tiles, H, W]
+    uint8_t* u8;         // when set: the image leaves as uint8 NHWC frames [B, H, W, 3] (render.py:40-43); out may then be null
+    float wscale;
+    int mode;            // 1 on, 2 on and the feature map itself is not stored, 3 partial: every m-tile's share of the sum goes to out (no
+                         // bias, no skip; 2-D Winograd only), the feature map is stored
+};
 
 // modconv_w2d.hip (mode 5 of maua_modconv3x3_f32 / maua_styledconv_torgb_f32): 2-D Winograd F(2x4, 3x3) plain convolution
 int maua_w2d_tiles(int cin, int cout, int h, int w, int* tm, int* tn);
 const char* maua_w2d_last_instance();
 int maua_w2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, int batch, int cin,
-                    int cout, int h, int w, float wscale, int fuse_act, const float* noise, int64_t noise_batch_stride,
-                    const float* noise_w, const float* bias, const float* rgb_w, const float* rgb_s, float rgb_wscale,
-                    const float* rgb_bias, const float* rgb_skip, const float* rgb_k4, float* rgb_out, uint8_t* rgb_u8,
-                    int rgb_mode, const maua_frame_source_t* src, int noise_slot, const float* post_s, void* stream);
+                    int cout, int h, int w, float wscale, int fuse_act, const TailArgs& tail, const RgbArgs* rgb, const float* post_s,
+                    void* stream);
 
 // modconv_up2d.hip (mode 6 of maua_modconv3x3_f32): transposed convolution with F(2,2) on both axes of its polyphase form
 const char* maua_up2d_last_instance();
@@ -68,7 +112,6 @@ int maua_up2d16_launch(const float* x, const float* wq, const float* s, int s_st
 int maua_sbf16_ok(int cin, int cout, int h, int w);
 const char* maua_sbf16_last_instance();
 int maua_sbf16_launch(const float* x, const void* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
-                      int cout, int h, int w, int up, float wscale, int fuse_act, const float* noise, int64_t noise_batch_stride,
-                      const float* noise_w, const float* bias, const maua_frame_source_t* src, int noise_slot, void* stream);
+                      int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, void* stream);
 int maua_up2d_edge_launch(const float* x, const float* edge_taps, const float* s, int s_stride, const float* d, float* y, const float* xcol,
                           int batch, int cin, int cout, int h, int w, float wscale, void* stream);

@@ -67,11 +67,7 @@ __global__ __launch_bounds__(256) void const_conv_kernel(const float* __restrict
     const int tid = threadIdx.x, il = tid & 7, ol = tid >> 3;
     const int p = blockIdx.x % CC_HW, g = blockIdx.x / CC_HW;
     const int o = g * 32 + ol, groups = cout / 32, nk = cin / 8;
-    if (src) {
-        noise_batch_stride = src->noise_stride[noise_slot];
-        noise = src->noise[noise_slot];
-        if (noise) noise += (int64_t)src->frame0 * noise_batch_stride;
-    }
+    maua_noise_source(noise, noise_batch_stride, src, noise_slot);
     const float nw = noise ? noise_w[0] : 0.f;
     const float bv = bias ? bias[o] : 0.f;
     const float* Tp = T + (((size_t)g * CC_HW + p) * nk * 32 + ol) * 8 + il;
@@ -187,8 +183,7 @@ extern "C" int maua_const_styledconv_f32(const float* T, const float* s, int s_s
                                          int noise_slot, int batch, int cin, int cout, int h, int w, float wscale, void* stream) {
     if (!T || !s || !y || batch <= 0) return MAUA_EINVAL;
     if (!maua_const_conv_ok(cin, cout, h, w)) return MAUA_ENOSYS;
-    if ((noise || src) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    if (int rc = TailArgs{noise, noise_w, bias, noise_batch_stride, src, noise_slot}.check()) return rc;
     if (rgb_partial && (!rgb_w || !rgb_s)) return MAUA_EINVAL;
     const size_t lds = (size_t)CC_MAXB * cin * sizeof(float);
     if (lds > 48 * 1024) return MAUA_ENOSYS;

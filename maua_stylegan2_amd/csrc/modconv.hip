@@ -32,7 +32,7 @@
 // several images and for the 32-channel F(2,3) config).  Measured rule of this chip that shapes everything above: VALU /
 // SALU instructions of co-resident waves do NOT hide under the 64-cycle MFMAs (profiles/r01_pmc_modconv.md) — fewer
 // MFMAs per output (Winograd) and fewer non-MFMA instructions are what pay, not occupancy or prefetch depth.
-#include "common.h"
+#include "epilogue.h"
 
 #include <cstdio>
 #include <type_traits>
@@ -715,18 +715,14 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
     float* outp = to_ws ? (p.ws + (size_t)split * g.ws_slab) : p.y;
     const float* noise_base = p.noise;
     int64_t noise_bstride = g.noise_batch_stride;
-    if (p.src) {  // uniform scalar loads: base of this launch's first frame inside the HBM-resident sequence
-        noise_bstride = p.src->noise_stride[p.noise_slot];
-        noise_base = p.src->noise[p.noise_slot];
-        if (noise_base) noise_base += (int64_t)p.src->frame0 * noise_bstride;
-    }
+    maua_noise_source(noise_base, noise_bstride, p.src, p.noise_slot);
     const float nw = (!to_ws && g.fuse_act && noise_base) ? p.noise_w[0] : 0.f;  // (scaled by act_gain where it is applied)
     const size_t plane_out = (size_t)g.OH * g.OW;
     float* Eg = lds;        // [BM] gain
     float* Eb = lds + BM;   // [BM] bias
     // leaky ReLU is positively homogeneous: its sqrt(2) gain is folded into gain, bias and noise once, and the activation
     // itself is max(t, 0.2 t) — 4 instead of 7 VALU operations per output value
-    const float act_gain = (!to_ws && g.fuse_act) ? 1.41421356237309515f : 1.f;
+    const float act_gain = (!to_ws && g.fuse_act) ? kSqrt2 : 1.f;
     if (!MULTI) {
         for (int i = tid; i < BM; i += 256) {
             const int o = m0 + i;
@@ -965,7 +961,7 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
                         if (p.rgb_u8) {  // render.py:40-43: clamp(-1, 1), (x + 1) * 127.5, truncating cast
 #pragma unroll
                             for (int px = 0; px < PXN; ++px)
-                                pix[px] |= (uint32_t)((fminf(fmaxf(val[px], -1.f), 1.f) + 1.f) * 127.5f) << (8 * c);
+                                pix[px] |= rgb8_quant(val[px]) << (8 * c);
                             if (!p.rgb_out) continue;  // (both given: the fp32 planes are written as well — the parity tests' tap)
                         }
                         float* ro = rgb_img + (size_t)c * plane_out + rgb_off;
@@ -975,11 +971,8 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
                     }
                     if (p.rgb_u8) {
                         uint8_t* fo = p.rgb_u8 + ((size_t)b0 * plane_out + rgb_off) * 3;
-                        if (PXN == 4 && ok1) {  // 12 bytes at a 12-byte multiple: three dword stores
-                            uint32_t* fw = reinterpret_cast<uint32_t*>(fo);
-                            fw[0] = pix[0] | (pix[1 % PXN] << 24);
-                            fw[1] = (pix[1 % PXN] >> 8) | (pix[2 % PXN] << 16);
-                            fw[2] = (pix[2 % PXN] >> 16) | (pix[3 % PXN] << 8);
+                        if (PXN == 4 && ok1) {
+                            store_rgb8x4(fo, pix[0], pix[1 % PXN], pix[2 % PXN], pix[3 % PXN]);
                         } else {
 #pragma unroll
                             for (int px = 0; px < PXN; ++px)
@@ -1011,11 +1004,7 @@ __global__ __launch_bounds__(256) void reduce_tail_kernel(const float* __restric
                                                           const float* __restrict__ bias, int fuse_act, int cout,
                                                           int64_t plane, int64_t total,
                                                           const maua_frame_source_t* __restrict__ src, int noise_slot) {
-    if (src) {
-        noise_batch_stride = src->noise_stride[noise_slot];
-        noise = src->noise[noise_slot];
-        if (noise) noise += (int64_t)src->frame0 * noise_batch_stride;
-    }
+    maua_noise_source(noise, noise_batch_stride, src, noise_slot);
     const float nw = (fuse_act && noise) ? noise_w[0] : 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         // every operand of this element is fetched before the first use: the slab values (up to 32, all in flight: with four at a time a
@@ -1033,7 +1022,7 @@ __global__ __launch_bounds__(256) void reduce_tail_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < 32; ++k) a[k] = ws[(size_t)(s + k) * slab + i];
 #pragma unroll
-            for (int k = 0; k < 32; k += 4) v += (a[k] + a[k + 1]) + (a[k + 2] + a[k + 3]);  // (the association of the 4-wide form)
+            for (int k = 0; k < 32; k += 4) v += (a[k] + a[k + 1]) + (a[k + 2] + a[k + 3]);  // (slab_sum's association, epilogue.h; 32 / 16 slabs in flight)
         }
         if (s + 16 <= splits) {
             float a[16];
@@ -1072,20 +1061,16 @@ __global__ __launch_bounds__(256) void reduce_blur_tail_kernel(const float* __re
     const int RH = 2 * h + 1, RW = 2 * w + 1, OH = 2 * h, OW = 2 * w, PW = RW + 2;
     const int bc = blockIdx.x, b = bc / cout, c = bc - b * cout;
     const int tid = threadIdx.x;
-    if (src) {
-        noise_batch_stride = src->noise_stride[noise_slot];
-        noise = src->noise[noise_slot];
-        if (noise) noise += (int64_t)src->frame0 * noise_batch_stride;
-    }
+    maua_noise_source(noise, noise_batch_stride, src, noise_slot);
     float kf[4][4];  // flipped taps (uniform loads)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) kf[i][j] = k4[(3 - i) * 4 + (3 - j)];
     const float dv = d ? d[bc] : 1.f;
-    const float g = 1.41421356237309515f;
-    const float nw = noise ? noise_w[0] * 1.41421356237309515f : 0.f;
-    const float bs = bias ? bias[c] * 1.41421356237309515f : 0.f;
+    const float g = kSqrt2;
+    const float nw = noise ? noise_w[0] * kSqrt2 : 0.f;
+    const float bs = bias ? bias[c] * kSqrt2 : 0.f;
     const float post = post_s ? post_s[(size_t)b * post_stride + c] : 1.f;
     const float* wp = ws + (size_t)bc * RH * RW;
     const int n_raw = RH * RW, n_out = OH * OW;
@@ -1107,35 +1092,7 @@ __global__ __launch_bounds__(256) void reduce_blur_tail_kernel(const float* __re
             const int e = tid + 256 * q, r = e / RW;
             nsl[q] = e >= n_raw ? 0 : (edge_slab0 && (r == RH - 1 || e - r * RW == RW - 1)) ? 1 : splits;
         }
-        int sp = 0;
-        for (; sp + 8 <= splits; sp += 8) {
-            float a[NE][8];
-#pragma unroll
-            for (int q = 0; q < NE; ++q)
-#pragma unroll
-                for (int k = 0; k < 8; ++k) a[q][k] = (sp + k < nsl[q]) ? wp[(size_t)(sp + k) * slab + tid + 256 * q] : 0.f;
-#pragma unroll
-            for (int q = 0; q < NE; ++q) {
-                v[q] += (a[q][0] + a[q][1]) + (a[q][2] + a[q][3]);  // (reduce_tail_kernel's association)
-                v[q] += (a[q][4] + a[q][5]) + (a[q][6] + a[q][7]);
-            }
-        }
-        for (; sp + 4 <= splits; sp += 4) {
-            float a[NE][4];
-#pragma unroll
-            for (int q = 0; q < NE; ++q)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) a[q][k] = (sp + k < nsl[q]) ? wp[(size_t)(sp + k) * slab + tid + 256 * q] : 0.f;
-#pragma unroll
-            for (int q = 0; q < NE; ++q) v[q] += (a[q][0] + a[q][1]) + (a[q][2] + a[q][3]);
-        }
-        for (; sp < splits; ++sp) {
-            float a[NE];
-#pragma unroll
-            for (int q = 0; q < NE; ++q) a[q] = (sp < nsl[q]) ? wp[(size_t)sp * slab + tid + 256 * q] : 0.f;
-#pragma unroll
-            for (int q = 0; q < NE; ++q) v[q] += a[q];
-        }
+        slab_sum(v, splits, [&](int q, int sp) { return (sp < nsl[q]) ? wp[(size_t)sp * slab + tid + 256 * q] : 0.f; });
 #pragma unroll
         for (int q = 0; q < NE; ++q) {
             const int e = tid + 256 * q;
@@ -1192,11 +1149,7 @@ __global__ __launch_bounds__(256) void reduce_tail_rgbpart_kernel(const float* _
     t /= ptiles;
     const int gidx = t % groups, b = t / groups;
     const int pix = pt * PT + px;
-    if (src) {
-        noise_batch_stride = src->noise_stride[noise_slot];
-        noise = src->noise[noise_slot];
-        if (noise) noise += (int64_t)src->frame0 * noise_batch_stride;
-    }
+    maua_noise_source(noise, noise_batch_stride, src, noise_slot);
     const float nw = noise ? noise_w[0] : 0.f;
     const float nzv = nw != 0.f ? noise[(size_t)b * noise_batch_stride + pix] : 0.f;
     float dv[NC], bv[NC], ms[NC], w0[NC], w1[NC], w2[NC], v[NC];
@@ -1212,31 +1165,7 @@ __global__ __launch_bounds__(256) void reduce_tail_rgbpart_kernel(const float* _
         w0[q] = rgb_w[c], w1[q] = rgb_w[cout + c], w2[q] = rgb_w[2 * cout + c];
         v[q] = 0.f;
     }
-    int sp = 0;
-    for (; sp + 8 <= splits; sp += 8) {  // eight slabs of every element in flight
-        float a[NC][8];
-#pragma unroll
-        for (int q = 0; q < NC; ++q)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) a[q][k] = ws[(size_t)(sp + k) * slab + idx[q]];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) {
-            v[q] += (a[q][0] + a[q][1]) + (a[q][2] + a[q][3]);  // (reduce_tail_kernel's association)
-            v[q] += (a[q][4] + a[q][5]) + (a[q][6] + a[q][7]);
-        }
-    }
-    for (; sp + 4 <= splits; sp += 4) {
-        float a[NC][4];
-#pragma unroll
-        for (int q = 0; q < NC; ++q)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[q][k] = ws[(size_t)(sp + k) * slab + idx[q]];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) v[q] += (a[q][0] + a[q][1]) + (a[q][2] + a[q][3]);
-    }
-    for (; sp < splits; ++sp)
-#pragma unroll
-        for (int q = 0; q < NC; ++q) v[q] += ws[(size_t)sp * slab + idx[q]];
+    slab_sum(v, splits, [&](int q, int sp) { return ws[(size_t)sp * slab + idx[q]]; });
     float r0 = 0.f, r1 = 0.f, r2 = 0.f;
 #pragma unroll
     for (int q = 0; q < NC; ++q) {
@@ -1566,15 +1495,9 @@ extern "C" int maua_modconv_last_instance(char* buf, int buf_len) {
 }
 
 namespace {
-struct RgbArgs {
-    const float* w; const float* s; const float* bias; const float* skip; const float* k4; float* out;
-    float wscale; int store_features; uint8_t* u8;
-};
-
 int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, const float* d, float* y, int batch,
-                 int cin, int cout, int h, int w, int up, float wscale, int fuse_act, const float* noise,
-                 int64_t noise_batch_stride, const float* noise_w, const float* bias, float* ws, const RgbArgs* rgb,
-                 const maua_frame_source_t* src, int noise_slot, const float* post_s, void* stream, int* partial_splits = nullptr) {
+                 int cin, int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, float* ws, const RgbArgs* rgb,
+                 const float* post_s, void* stream, int* partial_splits = nullptr) {
     // partial_splits != NULL (modes 0 .. 3, the low-resolution entries): the convolution leaves its split-K slabs (one slab when K is not
     // split) in ws and the caller reduces them; *partial_splits receives the slab count
     if (!x || !wp || !y || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return MAUA_EINVAL;
@@ -1583,21 +1506,15 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
     // transposed kernels have instances without the multiply; post_s = the consumer's styles, applied to the stored map by the
     // 2-D Winograd kernels' epilogue
     if ((!s && up != 5 && up != 6) || (post_s && up != 5)) return MAUA_ENOSYS;
-    if ((noise || (src && fuse_act)) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    if (int rc = tail.check(fuse_act != 0)) return rc;  // (without fuse_act a frame source's noise is not read: its weight may be absent)
     if (up == 5) {  // 2-D Winograd F(2x4, 3x3), modconv_w2d.hip
-        const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, fuse_act, noise, noise_batch_stride,
-                                       noise_w, bias, rgb ? rgb->w : nullptr, rgb ? rgb->s : nullptr, rgb ? rgb->wscale : 0.f,
-                                       rgb ? rgb->bias : nullptr, rgb ? rgb->skip : nullptr, rgb ? rgb->k4 : nullptr,
-                                       rgb ? rgb->out : nullptr, rgb ? rgb->u8 : nullptr, rgb ? (rgb->store_features ? 1 : 2) : 0,
-                                       src, noise_slot, post_s, stream);
+        const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, fuse_act, tail, rgb, post_s, stream);
         if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_w2d_last_instance());
         return rc;
     }
     if (up == 7 || up == 8) {  // plain (7) / transposed (8) conv with split-bf16 products (side measurement), modconv_sbf16.hip
         if (rgb) return MAUA_ENOSYS;
-        const int rc = maua_sbf16_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, up == 8, wscale, fuse_act, noise,
-                                         noise_batch_stride, noise_w, bias, src, noise_slot, stream);
+        const int rc = maua_sbf16_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, up == 8, wscale, fuse_act, tail, stream);
         if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_sbf16_last_instance());
         return rc;
     }
@@ -1616,20 +1533,20 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
     pl.g.s_stride = s_stride;
     pl.g.wscale = wscale;
     pl.g.fuse_act = fuse_act;
-    pl.g.noise_batch_stride = noise_batch_stride;
+    pl.g.noise_batch_stride = tail.noise_batch_stride;
 #ifdef MAUA_EXPERIMENTS
     pl.g.debug = g_conv_debug;
 #endif
     pl.g.rgb = 0;
     pl.g.rgb_wscale = 0.f;
-    ConvPtrs ptrs{x, wp, s, d, noise, noise_w, bias, y, ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, src, noise_slot};
+    ConvPtrs ptrs{x, wp, s, d, tail.noise, tail.noise_w, tail.bias, y, ws, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tail.src, tail.noise_slot};
     if (rgb) {
         // fusable only when one workgroup holds every channel of its pixels in a single wave row (BM >= Cout, WM == 1),
         // no split-K, one image per tile, the tail fused
         const bool ok = up != 1 && up != 4 && fuse_act && pl.wm == 1 && pl.g.m_tiles == 1 && pl.g.splits == 1 && pl.g.lni == 0 &&
                         rgb->w && rgb->s && rgb->bias && (rgb->out || rgb->u8) && (!rgb->skip || (rgb->k4 && !(h & 1) && !(w & 1)));
         if (!ok) return MAUA_ENOSYS;
-        pl.g.rgb = rgb->store_features ? 1 : 2;
+        pl.g.rgb = rgb->mode;
         pl.g.rgb_wscale = rgb->wscale;
         ptrs.rgb_w = rgb->w, ptrs.rgb_s = rgb->s, ptrs.rgb_bias = rgb->bias, ptrs.rgb_skip = rgb->skip;
         ptrs.rgb_k4 = rgb->k4, ptrs.rgb_out = rgb->out, ptrs.rgb_u8 = rgb->u8;
@@ -1668,8 +1585,8 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
         const int64_t total = pl.g.ws_slab;
         const int64_t blocks = ceil_div64(total, 256);
         hipLaunchKernelGGL(reduce_tail_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, ws,
-                           pl.g.splits, pl.g.ws_slab, y, d, noise, noise_batch_stride, noise_w, bias, fuse_act, cout,
-                           (int64_t)pl.g.OH * pl.g.OW, total, src, noise_slot);
+                           pl.g.splits, pl.g.ws_slab, y, d, tail.noise, tail.noise_batch_stride, tail.noise_w, tail.bias, fuse_act, cout,
+                           (int64_t)pl.g.OH * pl.g.OW, total, tail.src, tail.noise_slot);
         MAUA_LAUNCH_CHECK();
     }
     return 0;
@@ -1680,8 +1597,8 @@ extern "C" int maua_modconv3x3_f32(const float* x, const float* wp, const float*
                                    float* y, int batch, int cin, int cout, int h, int w, int up, float wscale,
                                    int fuse_act, const float* noise, int64_t noise_batch_stride, const float* noise_w,
                                    const float* bias, float* ws, const maua_frame_source_t* src, int noise_slot, void* stream) {
-    return modconv_impl(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, up, wscale, fuse_act, noise, noise_batch_stride,
-                        noise_w, bias, ws, nullptr, src, noise_slot, nullptr, stream);
+    const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
+    return modconv_impl(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, up, wscale, fuse_act, tail, ws, nullptr, nullptr, stream);
 }
 
 // ---- low-resolution entries: convolution (modes 0 / 1) + the fused reducers above
@@ -1707,16 +1624,16 @@ extern "C" int maua_upconv_blur_lowres_f32(const float* x, const float* wp, cons
                                            int h, int w, int up, float wscale, const float* post_s, void* stream) {
     if (!x || !wp || !s || !y || !ws || !k4 || batch <= 0 || (up != 1 && up != 6)) return MAUA_EINVAL;
     if (!maua_lowres_ok(cin, cout, h, w, up)) return MAUA_ENOSYS;
-    if ((noise || src) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
+    if (int rc = tail.check()) return rc;
     int splits = 0;
     const int64_t slab = (int64_t)batch * cout * (2 * h + 1) * (2 * w + 1);
     if (up == 6) {  // F(2,2) on both axes (wp = maua_pack_weight_up2d_f32), K split over workgroups; the exported column behind the slabs
         float* xcol = ws + (int64_t)maua_up2d16_splits(batch, cin, cout, h, w) * slab;
         if (int rc = maua_up2d16_launch(x, wp, s, s_stride, ws, xcol, batch, cin, cout, h, w, wscale, &splits, stream)) return rc;
         snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_up2d_last_instance());
-    } else if (int rc = modconv_impl(x, wp, s, s_stride, nullptr, y, batch, cin, cout, h, w, 1, wscale, 0, nullptr, 0, nullptr, nullptr, ws,
-                                     nullptr, nullptr, 0, nullptr, stream, &splits))  // (the convolution writes slabs only: y is a placeholder)
+    } else if (int rc = modconv_impl(x, wp, s, s_stride, nullptr, y, batch, cin, cout, h, w, 1, wscale, 0, TailArgs{}, ws, nullptr, nullptr, stream,
+                                     &splits))  // (the convolution writes slabs only: y is a placeholder)
         return rc;
     const size_t lds = (size_t)(2 * h + 3) * (2 * w + 3) * sizeof(float);
     hipLaunchKernelGGL(reduce_blur_tail_kernel, dim3((unsigned)(batch * cout)), dim3(256), lds, (hipStream_t)stream, ws, splits, slab, y, d, k4,
@@ -1732,11 +1649,10 @@ extern "C" int maua_styledconv_rgbpart_lowres_f32(const float* x, const float* w
                                                   int cout, int h, int w, int mode, float wscale, void* stream) {
     if (!x || !wp || !s || !y || !ws || !rgb_w || !rgb_s || !rgb_partial || batch <= 0 || (mode != 0 && mode != 2 && mode != 3)) return MAUA_EINVAL;
     if (!maua_lowres_ok(cin, cout, h, w, mode)) return MAUA_ENOSYS;
-    if ((noise || src) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
+    if (int rc = tail.check()) return rc;
     int splits = 0;
-    if (int rc = modconv_impl(x, wp, s, s_stride, nullptr, y, batch, cin, cout, h, w, mode, wscale, 0, nullptr, 0, nullptr, nullptr, ws, nullptr,
-                              nullptr, 0, nullptr, stream, &splits))
+    if (int rc = modconv_impl(x, wp, s, s_stride, nullptr, y, batch, cin, cout, h, w, mode, wscale, 0, TailArgs{}, ws, nullptr, nullptr, stream, &splits))
         return rc;
     const int64_t slab = (int64_t)batch * cout * h * w;
     const int pt = (h * w) % 32 == 0 ? 32 : 16;
@@ -1758,10 +1674,11 @@ extern "C" int maua_styledconv_torgb_partial_f32(const float* x, const float* wp
                                                  float* rgb_partial, const maua_frame_source_t* src, int noise_slot,
                                                  const float* post_s, void* stream) {
     if (mode != 5) return MAUA_ENOSYS;  // only the 2-D Winograd kernel leaves partial ToRGB sums
-    if (!x || !wp || !y || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || ((noise || src) && !noise_w)) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
-    const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, 1, noise, noise_batch_stride, noise_w, bias,
-                                   rgb_w, rgb_s, rgb_wscale, nullptr, nullptr, nullptr, rgb_partial, nullptr, 3, src, noise_slot, post_s, stream);
+    if (!x || !wp || !y || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return MAUA_EINVAL;
+    const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
+    if (int rc = tail.check()) return rc;
+    const RgbArgs rgb{rgb_w, rgb_s, nullptr, nullptr, nullptr, rgb_partial, nullptr, rgb_wscale, 3};
+    const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, 1, tail, &rgb, post_s, stream);
     if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_w2d_last_instance());
     return rc;
 }
@@ -1773,8 +1690,8 @@ extern "C" int maua_styledconv_torgb_f32(const float* x, const float* wp, const 
                                          const float* rgb_bias, const float* rgb_skip, const float* rgb_k4, float* rgb_out,
                                          int store_features, uint8_t* frames_u8, const maua_frame_source_t* src, int noise_slot,
                                          const float* post_s, void* stream) {
-    RgbArgs rgb{rgb_w, rgb_s, rgb_bias, rgb_skip, rgb_k4, rgb_out, rgb_wscale, store_features, frames_u8};
+    const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
+    const RgbArgs rgb{rgb_w, rgb_s, rgb_bias, rgb_skip, rgb_k4, rgb_out, frames_u8, rgb_wscale, store_features ? 1 : 2};
     if (mode == 1) return MAUA_ENOSYS;
-    return modconv_impl(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, mode, wscale, 1, noise, noise_batch_stride, noise_w,
-                        bias, nullptr, &rgb, src, noise_slot, post_s, stream);
+    return modconv_impl(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, mode, wscale, 1, tail, nullptr, &rgb, post_s, stream);
 }

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void modconv_sbf16_kernel(SbArgs p) {
     const unsigned plane_bytes = (unsigned)plane * 4u;
 
     const bool act = p.fuse_act != 0;
-    const float act_gain = act ? 1.41421356237309515f : 1.f;
+    const float act_gain = act ? kSqrt2 : 1.f;
     for (int e = tid; e < p.Cin; e += 256) Ss[e] = p.s[(size_t)b0 * p.s_stride + e];
     for (int i = tid; i < SB_BM; i += 256) {
         float gain = p.wscale * act_gain;
@@ -265,11 +265,7 @@ __global__ __launch_bounds__(256, 2) void modconv_sbf16_kernel(SbArgs p) {
     // 16 output channels of one pixel column per tile: rows (j & 3) + 8 (j >> 2) + 4 hi32 of the 32 x 32 result tile
     const float* noise_base = p.noise;
     int64_t noise_bstride = p.noise_batch_stride;
-    if (p.src) {
-        noise_bstride = p.src->noise_stride[p.noise_slot];
-        noise_base = p.src->noise[p.noise_slot];
-        if (noise_base) noise_base += (int64_t)p.src->frame0 * noise_bstride;
-    }
+    maua_noise_source(noise_base, noise_bstride, p.src, p.noise_slot);
     const float nw = (act && noise_base) ? p.noise_w[0] * act_gain : 0.f;
     const float slope = act ? 0.2f : 1.f;
     float* yimg = p.y + ((size_t)b0 * p.Cout + m0 + wave * 32) * plane;
@@ -541,15 +537,14 @@ int sbf16_launch_phase(const SbArgs& a, size_t lds_bytes, hipStream_t st) {
 // four phase launches over the positions p < H, q < W, then the edge lines (output row 2H, column 2W) by modconv_up2d.hip's fp32 edge
 // kernel on the edge tap matrices stored behind the bf16 records; ws = [B, cin, H] floats (the exported last input column).
 int maua_sbf16_launch(const float* x, const void* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
-                      int cout, int h, int w, int up, float wscale, int fuse_act, const float* noise, int64_t noise_batch_stride,
-                      const float* noise_w, const float* bias, const maua_frame_source_t* src, int noise_slot, void* stream) {
+                      int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, void* stream) {
     if (!(up ? maua_sbf16_up_ok(cin, cout, h, w) : maua_sbf16_ok(cin, cout, h, w))) return MAUA_EINVAL;
     if ((int64_t)cin * h * w * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor range / 32-bit offsets
     if (up && (fuse_act || !ws)) return MAUA_EINVAL;
     SbArgs a{};
-    a.x = x, a.wq = static_cast<const bf16x8*>(wq), a.s = s, a.d = d, a.noise = noise, a.noise_w = noise_w, a.bias = bias, a.y = y;
+    a.x = x, a.wq = static_cast<const bf16x8*>(wq), a.s = s, a.d = d, a.noise = tail.noise, a.noise_w = tail.noise_w, a.bias = tail.bias, a.y = y;
     a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale, a.fuse_act = fuse_act;
-    a.noise_batch_stride = noise_batch_stride, a.src = src, a.noise_slot = noise_slot;
+    a.noise_batch_stride = tail.noise_batch_stride, a.src = tail.src, a.noise_slot = tail.noise_slot;
     a.tiles_x = w / SB_TW, a.tiles_y = h / SB_TH, a.m_tiles = cout / SB_BM, a.n_chunks = cin / SB_KC;
     const size_t lds_bytes = (size_t)2 * SB_BUF_BYTES + sizeof(float) * ((size_t)cin + 2 * SB_BM);
     hipStream_t st = (hipStream_t)stream;

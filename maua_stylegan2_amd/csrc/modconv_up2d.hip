@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void modconv_up2d_kernel(Up2dArgs p) {
         Eg[i] = gain;
         if constexpr (FUSE == 2) {
             Eg[U2_BM + i] = p.post_s ? p.post_s[(size_t)b0 * p.s_stride + m0 + i] : 1.f;  // scale of the stored map
-            Eg[2 * U2_BM + i] = p.bias ? p.bias[m0 + i] * 1.41421356237309515f : 0.f;       // bias * sqrt2, once per workgroup (round 6: it was
+            Eg[2 * U2_BM + i] = p.bias ? p.bias[m0 + i] * kSqrt2 : 0.f;       // bias * sqrt2, once per workgroup (round 6: it was
         }                                                                                   // two global loads per channel pair and TILE)
     }
     float* SV = Eg + 3 * U2_BM;
@@ -455,16 +455,12 @@ __global__ __launch_bounds__(256, 2) void modconv_up2d_kernel(Up2dArgs p) {
         const int j_e = lane_e & 15, kq_e = lane_e >> 4;
         float kx[4], ky[4];
         u2_blur_taps(pk->k4, kx, ky);
-        const float act_gain = 1.41421356237309515f;
+        const float act_gain = kSqrt2;
         const int OHb = 2 * pk->H, OWb = 2 * pk->W;
         const int Y0 = 2 * ty0 + 4 * wv - 2, X0 = 2 * tx0 + 4 * j_e + (shifted ? 2 : 0);  // (FUSE == 2: 60 tile_x + 4 j either way)
         const float* noise_base = pk->noise;
         int64_t noise_bstride = pk->noise_batch_stride;
-        if (pk->src) {  // (uniform scalar loads)
-            noise_bstride = pk->src->noise_stride[pk->noise_slot];
-            noise_base = pk->src->noise[pk->noise_slot];
-            if (noise_base) noise_base += (int64_t)pk->src->frame0 * noise_bstride;
-        }
+        maua_noise_source(noise_base, noise_bstride, pk->src, pk->noise_slot);
         const float nw = noise_base ? pk->noise_w[0] * act_gain : 0.f;
         // which of this lane's outputs are kept: FUSE == 2: lanes 1 .. 14 (+ lane 0 of the first tile column), inside the map
         const bool x_keep = ((FUSE == 2 && !FUSE_ABL(16)) ? j_e <= 14 : true) && X0 < OWb;  // (lane 15 has no right neighbour)
@@ -667,14 +663,10 @@ __global__ __launch_bounds__(256) void up2d_seam_kernel(Up2dArgs p, int n_bnd) {
     float kx[4], ky[4];
     u2_blur_taps(p.k4, kx, ky);
     (void)kx;
-    const float act_gain = 1.41421356237309515f;
+    const float act_gain = kSqrt2;
     const float* noise_base = p.noise;
     int64_t noise_bstride = p.noise_batch_stride;
-    if (p.src) {
-        noise_bstride = p.src->noise_stride[p.noise_slot];
-        noise_base = p.src->noise[p.noise_slot];
-        if (noise_base) noise_base += (int64_t)p.src->frame0 * noise_bstride;
-    }
+    maua_noise_source(noise_base, noise_bstride, p.src, p.noise_slot);
     const float nw = noise_base ? p.noise_w[0] * act_gain : 0.f;
     float gain = p.wscale * act_gain;
     if (p.d) gain *= p.d[(size_t)b * p.Cout + c];
@@ -972,8 +964,7 @@ extern "C" int maua_upconv_blur_f32(const float* x, const float* wq, const float
                                     int w, float wscale, const float* post_s, void* stream) {
     if (!x || !wq || !y || !k4 || batch <= 0) return MAUA_EINVAL;
     if (!maua_upconv_blur_ok(cin, cout, h, w)) return MAUA_ENOSYS;
-    if ((noise || src) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    if (int rc = TailArgs{noise, noise_w, bias, noise_batch_stride, src, noise_slot}.check()) return rc;
     if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)U2_NU * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
     const FusePlan f = fuse_plan(batch, cout, h, w);
     if (f.n_seg > 1 && !ws) return MAUA_EINVAL;

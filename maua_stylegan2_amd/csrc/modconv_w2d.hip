@@ -26,7 +26,7 @@
 //     channel offset; no selects (row 1 of A_y^T = row 0 with a sign, leaky ReLU = max(t, slope t)).
 // Operands reach LDS by MUBUF `buffer_load ... lds` DMA, double buffered, one barrier per 4-channel K step; the packed weight
 // (maua_pack_weight_wino2d_f32) is laid out in HBM exactly as the LDS tile image, so its DMA is a linear copy.
-#include "common.h"
+#include "epilogue.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -312,14 +312,10 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
     // their ~1 us round trip was exposed in every workgroup)
     float* E = lds + e_off;
     const bool act = p.fuse_act != 0;
-    const float act_gain = act ? 1.41421356237309515f : 1.f;
+    const float act_gain = act ? kSqrt2 : 1.f;
     const float* noise_base = p.noise;
     int64_t noise_bstride = p.noise_batch_stride;
-    if (p.src) {  // uniform scalar loads: base of this launch's first frame inside the HBM-resident sequence
-        noise_bstride = p.src->noise_stride[p.noise_slot];
-        noise_base = p.src->noise[p.noise_slot];
-        if (noise_base) noise_base += (int64_t)p.src->frame0 * noise_bstride;
-    }
+    maua_noise_source(noise_base, noise_bstride, p.src, p.noise_slot);
     const float nw = (act && noise_base) ? p.noise_w[0] * act_gain : 0.f;
     for (int i = tid; i < BM; i += 256) {
         const int o = m0 + i;
@@ -618,14 +614,8 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
     const float* zbase = Z + cp * 4;
     const int zo_off = (cr ? 3 : 0) * 16 * NPOS * 4;
 
-    // 2x FIR-upsampled skip image of the fused ToRGB: upfirdn2d(skip, k4, up=2, pad=(2,1)) at (oy, x) has two live source rows / columns,
-    // iy0 = floor((oy-1)/2), iy0+1 with taps k4[3]/k4[1] for even oy and k4[2]/k4[0] for odd (models/stylegan2.py:34-52,
-    // op/upfirdn2d.py:159-200).  All 24 source values of the 4 output pixels (2 live rows x 4 live columns x 3 channels) are fetched
-    // unconditionally from clamped addresses, in flight together; positions outside the skip image are masked through their tap
-    // weight (per-pixel conditional loads serialise ~48 dependent L2 round trips behind each other: measured 0.5 ms of the 1024^2
-    // layer).  Output column x = ox + px reads source columns (x-1)>>1 and +1: px 0 -> k 0,1; 1, 2 -> k 1,2; 3 -> k 2,3 of
-    // k = (ox>>1) - 1 + {0..3}, with taps k4[.][3], k4[.][1] for even x and k4[.][2], k4[.][0] for odd x.  The loads go out before
-    // the combine of the LAST pass (the accumulators are dead by then), so that their round trip hides behind it.
+    // 2x FIR-upsampled skip image of the fused ToRGB (layout of sv / wy / wx: skip_quad_add, epilogue.h).  The loads go out before the combine of
+    // the LAST pass (the accumulators are dead by then), so that their round trip hides behind it.
     const int sh = p.H >> 1, sw = p.W >> 1;
     const bool want_skip = (p.rgb == 1 || p.rgb == 2) && p.rgb_skip && cg == 0;
     float sv[3][2][4], wy[2], wx[4];
@@ -718,46 +708,20 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
             *reinterpret_cast<f32x4*>(part + (size_t)c * plane) = rgbv[c];
         return;
     }
-    const size_t rgb_plane = plane;
-    float* rgb_img = p.rgb_out + (size_t)b0 * 3 * rgb_plane;
     f32x4 outc[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) outc[c] = rgbv[c] + p.rgb_bias[c];
-    if (p.rgb_skip) {
-        const int ty_ = (oy & 1) ? 2 : 3;
-        float kt[2][4];  // the two live tap rows
-#pragma unroll
-        for (int qy = 0; qy < 2; ++qy)
-#pragma unroll
-            for (int t4 = 0; t4 < 4; ++t4) kt[qy][t4] = p.rgb_k4[(ty_ - 2 * qy) * 4 + t4] * wy[qy];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            const int k0 = (px + 1) >> 1;              // first live source column of this pixel
-            const int t0 = (px & 1) ? 2 : 3;           // its tap; the second live column uses tap t0 - 2
-#pragma unroll
-            for (int qy = 0; qy < 2; ++qy) {
-                const float w0 = kt[qy][t0] * wx[k0], w1 = kt[qy][t0 - 2] * wx[k0 + 1];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) outc[c][px] = fmaf(w0, sv[c][qy][k0], fmaf(w1, sv[c][qy][k0 + 1], outc[c][px]));
-            }
-        }
-    }
-    if (p.rgb_u8) {  // fused frame epilogue: clamp(-1, 1), (x + 1) * 127.5, truncating cast; 12 bytes = three dword stores
+    if (p.rgb_skip) skip_quad_add(p.rgb_k4, oy, sv, wy, wx, outc);
+    if (p.rgb_u8) {  // fused frame epilogue
         uint32_t pix[4];
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            pix[px] = 0u;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) pix[px] |= (uint32_t)((fminf(fmaxf(outc[c][px], -1.f), 1.f) + 1.f) * 127.5f) << (8 * c);
-        }
-        uint32_t* fw = reinterpret_cast<uint32_t*>(p.rgb_u8 + ((size_t)b0 * rgb_plane + pix_off) * 3);
-        fw[0] = pix[0] | (pix[1] << 24);
-        fw[1] = (pix[1] >> 8) | (pix[2] << 16);
-        fw[2] = (pix[2] >> 16) | (pix[3] << 8);
+        for (int px = 0; px < 4; ++px) pix[px] = pack_rgb8(outc[0][px], outc[1][px], outc[2][px]);
+        store_rgb8x4(p.rgb_u8 + ((size_t)b0 * plane + pix_off) * 3, pix[0], pix[1], pix[2], pix[3]);
         if (!p.rgb_out) return;  // (both given: the fp32 planes are written as well — the parity tests' tap)
     }
+    float* rgb_img = p.rgb_out + (size_t)b0 * 3 * plane;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(rgb_img + (size_t)c * rgb_plane + pix_off) = outc[c];
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(rgb_img + (size_t)c * plane + pix_off) = outc[c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -884,14 +848,10 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
     const float* dummy = p.wq;  // (always valid)
     const float s_first = *((!PRE && tid < p.Cin) ? p.s + (size_t)b0 * p.s_stride + tid : dummy);
     const bool act = p.fuse_act != 0;
-    const float act_gain = act ? 1.41421356237309515f : 1.f;
+    const float act_gain = act ? kSqrt2 : 1.f;
     const float* noise_base = p.noise;
     int64_t noise_bstride = p.noise_batch_stride;
-    if (p.src) {
-        noise_bstride = p.src->noise_stride[p.noise_slot];
-        noise_base = p.src->noise[p.noise_slot];
-        if (noise_base) noise_base += (int64_t)p.src->frame0 * noise_bstride;
-    }
+    maua_noise_source(noise_base, noise_bstride, p.src, p.noise_slot);
     const float nw = (act && noise_base) ? p.noise_w[0] * act_gain : 0.f;
     if (tid < BM) {
         // ALL table loads go out together, unconditionally: absent operands (no demodulation, no bias, no ToRGB) read a valid dummy
@@ -1185,43 +1145,17 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
         }
     if (!finisher) return;
     const unsigned pix_off = pix0 + (unsigned)cr * (unsigned)p.W;
-    const size_t rgb_plane = plane;
-    if (p.rgb_skip) {
-        const int ty_ = (oy & 1) ? 2 : 3;
-        float kt[2][4];
-#pragma unroll
-        for (int qy = 0; qy < 2; ++qy)
-#pragma unroll
-            for (int t4 = 0; t4 < 4; ++t4) kt[qy][t4] = p.rgb_k4[(ty_ - 2 * qy) * 4 + t4] * wy[qy];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            const int k0 = (px + 1) >> 1;
-            const int t0 = (px & 1) ? 2 : 3;
-#pragma unroll
-            for (int qy = 0; qy < 2; ++qy) {
-                const float w0 = kt[qy][t0] * wx[k0], w1 = kt[qy][t0 - 2] * wx[k0 + 1];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) outc[c][px] = fmaf(w0, sv[c][qy][k0], fmaf(w1, sv[c][qy][k0 + 1], outc[c][px]));
-            }
-        }
-    }
-    if (p.rgb_u8) {
+    if (p.rgb_skip) skip_quad_add(p.rgb_k4, oy, sv, wy, wx, outc);
+    if (p.rgb_u8) {  // fused frame epilogue
         uint32_t pix[4];
 #pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            pix[px] = 0u;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) pix[px] |= (uint32_t)((fminf(fmaxf(outc[c][px], -1.f), 1.f) + 1.f) * 127.5f) << (8 * c);
-        }
-        uint32_t* fw = reinterpret_cast<uint32_t*>(p.rgb_u8 + ((size_t)b0 * rgb_plane + pix_off) * 3);
-        fw[0] = pix[0] | (pix[1] << 24);
-        fw[1] = (pix[1] >> 8) | (pix[2] << 16);
-        fw[2] = (pix[2] >> 16) | (pix[3] << 8);
-        if (!p.rgb_out) return;
+        for (int px = 0; px < 4; ++px) pix[px] = pack_rgb8(outc[0][px], outc[1][px], outc[2][px]);
+        store_rgb8x4(p.rgb_u8 + ((size_t)b0 * plane + pix_off) * 3, pix[0], pix[1], pix[2], pix[3]);
+        if (!p.rgb_out) return;  // (both given: the fp32 planes are written as well — the parity tests' tap)
     }
-    float* rgb_img = p.rgb_out + (size_t)b0 * 3 * rgb_plane;
+    float* rgb_img = p.rgb_out + (size_t)b0 * 3 * plane;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(rgb_img + (size_t)c * rgb_plane + pix_off) = outc[c];
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(rgb_img + (size_t)c * plane + pix_off) = outc[c];
 }
 
 size_t w2dw_lds_bytes(int cin) {
@@ -1327,25 +1261,24 @@ int maua_w2d_tiles(int cin, int cout, int h, int w, int* tm, int* tn) {
 const char* maua_w2d_last_instance() { return g_w2d_instance; }
 
 int maua_w2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, int batch, int cin,
-                    int cout, int h, int w, float wscale, int fuse_act, const float* noise, int64_t noise_batch_stride,
-                    const float* noise_w, const float* bias, const float* rgb_w, const float* rgb_s, float rgb_wscale,
-                    const float* rgb_bias, const float* rgb_skip, const float* rgb_k4, float* rgb_out, uint8_t* rgb_u8,
-                    int rgb_mode, const maua_frame_source_t* src, int noise_slot, const float* post_s, void* stream) {
+                    int cout, int h, int w, float wscale, int fuse_act, const TailArgs& tail, const RgbArgs* rgb, const float* post_s,
+                    void* stream) {
     int tm = 0, tn = 0;
     if (!maua_w2d_tiles(cin, cout, h, w, &tm, &tn)) return MAUA_EINVAL;
     if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)24 * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
     W2dArgs a{};
-    a.x = x, a.wq = wq, a.s = s, a.d = d, a.noise = noise, a.noise_w = noise_w, a.bias = bias, a.y = y;
-    a.rgb_w = rgb_w, a.rgb_s = rgb_s, a.rgb_bias = rgb_bias, a.rgb_skip = rgb_skip, a.rgb_k4 = rgb_k4, a.rgb_out = rgb_out;
-    a.rgb_u8 = rgb_u8, a.post_s = post_s;
+    a.x = x, a.wq = wq, a.s = s, a.d = d, a.y = y, a.post_s = post_s;
+    a.noise = tail.noise, a.noise_w = tail.noise_w, a.bias = tail.bias, a.noise_batch_stride = tail.noise_batch_stride;
+    a.src = tail.src, a.noise_slot = tail.noise_slot;
+    const RgbArgs r = rgb ? *rgb : RgbArgs{};  // (mode 0: off)
+    a.rgb_w = r.w, a.rgb_s = r.s, a.rgb_bias = r.bias, a.rgb_skip = r.skip, a.rgb_k4 = r.k4, a.rgb_out = r.out, a.rgb_u8 = r.u8;
+    a.rgb = r.mode, a.rgb_wscale = r.wscale;
     a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale, a.fuse_act = fuse_act;
-    a.noise_batch_stride = noise_batch_stride;
-    a.src = src, a.noise_slot = noise_slot;
     a.tiles_x = w / 32, a.tiles_y = h / (4 * tn), a.m_tiles = cout / (16 * tm), a.n_chunks = cin / W2D_CC;
-    a.rgb = rgb_mode, a.rgb_wscale = rgb_wscale;
+    const int rgb_mode = r.mode;
     if (rgb_mode == 3) {
-        if (!fuse_act || !rgb_w || !rgb_s || !rgb_out) return MAUA_EINVAL;
-    } else if (rgb_mode && (a.m_tiles != 1 || !fuse_act || !rgb_w || !rgb_s || !rgb_bias || (!rgb_out && !rgb_u8) || (rgb_skip && (!rgb_k4 || (h & 1) || (w & 1)))))
+        if (!fuse_act || !r.w || !r.s || !r.out) return MAUA_EINVAL;
+    } else if (rgb_mode && (a.m_tiles != 1 || !fuse_act || !r.w || !r.s || !r.bias || (!r.out && !r.u8) || (r.skip && (!r.k4 || (h & 1) || (w & 1)))))
         return MAUA_ENOSYS;
     hipStream_t st = (hipStream_t)stream;
 #ifndef MAUA_W2D_NO_WW

@@ -171,20 +171,16 @@ __global__ __launch_bounds__(256) void fir_tile_kernel(const float* __restrict__
         const int b = plane / tail.channels;
         const int c = plane - b * tail.channels;
         // leaky ReLU * sqrt2 as max(t, 0.2 t) on pre-scaled operands: t = sqrt2 (g v + nw noise + bias)
-        g = 1.41421356237309515f * (tail.gain ? tail.gain[plane] : 1.f);
-        bs = tail.bias ? tail.bias[c] * 1.41421356237309515f : 0.f;
+        g = kSqrt2 * (tail.gain ? tail.gain[plane] : 1.f);
+        bs = tail.bias ? tail.bias[c] * kSqrt2 : 0.f;
         if (tail.post_s) post = tail.post_s[(size_t)b * tail.post_stride + c];
 #pragma unroll
         for (int o = 0; o < TH; ++o) nzv[o] = 0.f;
         const float* noise = tail.noise;
         int64_t nstride = tail.noise_batch_stride;
-        if (tail.src) {  // uniform scalar loads
-            nstride = tail.src->noise_stride[tail.noise_slot];
-            noise = tail.src->noise[tail.noise_slot];
-            if (noise) noise += (int64_t)tail.src->frame0 * nstride;
-        }
+        maua_noise_source(noise, nstride, tail.src, tail.noise_slot);
         if (noise) {
-            nw = tail.noise_w[0] * 1.41421356237309515f;
+            nw = tail.noise_w[0] * kSqrt2;
 #ifdef MAUA_DEVICE_PASS
             const __amdgpu_buffer_rsrc_t n_rsrc = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float*>(noise) + (size_t)b * nstride, 0, (int)((unsigned)out_h * out_row_bytes), 0x00020000);
@@ -688,8 +684,7 @@ extern "C" int maua_blur_noise_act_f32(const float* x, const float* k, float* y,
                                        const float* bias, const maua_frame_source_t* src, int noise_slot, const float* post_s,
                                        int post_stride, void* stream) {
     if (!x || !k || !y || batch <= 0 || channels <= 0 || in_h <= 0 || in_w <= 0) return MAUA_EINVAL;
-    if ((noise || src) && !noise_w) return MAUA_EINVAL;
-    if (src && (noise_slot < 0 || noise_slot >= MAUA_MAX_NOISE_SLOTS)) return MAUA_EINVAL;
+    if (int rc = TailArgs{noise, noise_w, bias, noise_batch_stride, src, noise_slot}.check()) return rc;
     const int out_h = in_h + pad0 + pad1 - kh + 1, out_w = in_w + pad0 + pad1 - kw + 1;
     if (out_h <= 0 || out_w <= 0) return MAUA_EINVAL;
     // Block order.  Channel-fastest (planes that share a noise tile back to back: the tile stays in one XCD's L2) pays on the 1024-row maps,

@@ -1,4 +1,6 @@
 """GPU parity: ModulatedConv2d / StyledConv / ToRGB on the HIP path vs golden vectors from the reference."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -300,14 +302,9 @@ def test_modconv_winograd2d_vs_oracle(gpu, cin, cout, h, w, batch):
     np.testing.assert_allclose(got, direct, atol=2e-4, rtol=1e-4)
 
 
-@pytest.mark.parametrize("cin,cout,h,w,with_skip", [(64, 64, 32, 64, True), (32, 32, 32, 32, True), (128, 64, 16, 32, False),
-                                                     (32, 32, 48, 64, True), (64, 128, 32, 32, True), (128, 256, 16, 64, False),
-                                                     (32, 512, 8, 32, True), (32, 32, 40, 32, True), (64, 32, 16, 64, False)])
-def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, with_skip):
-    """StyledConv + ToRGB folded into one launch (maua_styledconv_torgb_f32: <= 64-channel plain layers, every kernel mode that
-    the layer shape selects — 2-D Winograd here) against the same two layers run as separate launches and against the oracle;
-    with ``store`` off the feature map is not written at all.  Wider layers (2, 4, 8 output-channel tiles): the conv leaves
-    per-tile partial ToRGB sums (maua_styledconv_torgb_partial_f32) and maua_torgb_f32 adds them up."""
+def _fused_torgb_setup(gpu, cin, cout, h, w, with_skip, pin_mode):
+    """StyledConv + ToRGB with random weights, inputs, the oracle's feature map / image and the styles / demodulation factors from the
+    table kernels: what a fused StyledConv.run call needs.  ``pin_mode(conv)`` sets the layer's kernel thresholds."""
     from maua_stylegan2_amd.models.stylegan2 import StyledConv, ToRGB
     from oracle import stylegan2_oracle as so
 
@@ -326,8 +323,7 @@ def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, wit
     conv.load_state_dict({k[2:]: v for k, v in sd.items() if k.startswith("C.")}, strict=True)
     rgb.load_state_dict({k[2:]: v for k, v in sd.items() if k.startswith("T.")}, strict=True)
     conv, rgb = conv.to(gpu), rgb.to(gpu)
-    conv.conv.winograd2d_min_cout = 32
-    assert conv.conv.conv_mode(h, w) == 5
+    pin_mode(conv)
     x = torch.from_numpy(r.standard_normal((b, cin, h, w)).astype(np.float32))
     s1 = torch.from_numpy(r.standard_normal((b, 512)).astype(np.float32))
     s2 = torch.from_numpy(r.standard_normal((b, 512)).astype(np.float32))
@@ -335,11 +331,6 @@ def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, wit
     skip = torch.from_numpy(r.standard_normal((b, 3, h // 2, w // 2)).astype(np.float32)) if with_skip else None
     feat_want = so.styled_conv(sd, "C", x, s1, nz, False)
     img_want = so.to_rgb(sd, "T", feat_want, s2, skip).numpy()
-    # separate launches (the public modules)
-    feat = conv(x.to(gpu), s1.to(gpu), noise=nz.to(gpu))
-    img_sep = rgb(feat, s2.to(gpu), skip.to(gpu) if with_skip else None).cpu().numpy()
-    np.testing.assert_allclose(img_sep, img_want, atol=2e-3, rtol=1e-4)
-    # fused launch through StyledConv.run on precomputed styles
     lib = _lib.load()
     from maua_stylegan2_amd.models.stylegan2 import _style_table
 
@@ -352,6 +343,30 @@ def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, wit
     _lib.check(lib.maua_style_affine_f32(lat.data_ptr(), b, 2, 512, None, None, table.data_ptr(), 2, max(cin, cout),
                                          styles.data_ptr(), cin + cout, None, st), "affine")
     _lib.check(lib.maua_demod_f32(table.data_ptr(), 2, cout, styles.data_ptr(), cin + cout, demod.data_ptr(), b, st), "demod")
+    return dict(conv=conv, rgb=rgb, sd=sd, x=x, s1=s1, s2=s2, nz=nz, skip=skip, feat_want=feat_want, img_want=img_want, styles=styles,
+                demod=demod, b=b)
+
+
+@pytest.mark.parametrize("cin,cout,h,w,with_skip", [(64, 64, 32, 64, True), (32, 32, 32, 32, True), (128, 64, 16, 32, False),
+                                                     (32, 32, 48, 64, True), (64, 128, 32, 32, True), (128, 256, 16, 64, False),
+                                                     (32, 512, 8, 32, True), (32, 32, 40, 32, True), (64, 32, 16, 64, False)])
+def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, with_skip):
+    """StyledConv + ToRGB folded into one launch (maua_styledconv_torgb_f32: <= 64-channel plain layers, every kernel mode that
+    the layer shape selects — 2-D Winograd here) against the same two layers run as separate launches and against the oracle;
+    with ``store`` off the feature map is not written at all.  Wider layers (2, 4, 8 output-channel tiles): the conv leaves
+    per-tile partial ToRGB sums (maua_styledconv_torgb_partial_f32) and maua_torgb_f32 adds them up."""
+    def pin_mode(conv):
+        conv.conv.winograd2d_min_cout = 32
+        assert conv.conv.conv_mode(h, w) == 5
+
+    f = _fused_torgb_setup(gpu, cin, cout, h, w, with_skip, pin_mode)
+    conv, rgb, x, s1, s2, nz, skip, b = (f[k] for k in ("conv", "rgb", "x", "s1", "s2", "nz", "skip", "b"))
+    feat_want, img_want, styles, demod = f["feat_want"], f["img_want"], f["styles"], f["demod"]
+    # separate launches (the public modules)
+    feat = conv(x.to(gpu), s1.to(gpu), noise=nz.to(gpu))
+    img_sep = rgb(feat, s2.to(gpu), skip.to(gpu) if with_skip else None).cpu().numpy()
+    np.testing.assert_allclose(img_sep, img_want, atol=2e-3, rtol=1e-4)
+    # fused launch through StyledConv.run on precomputed styles
     for store in ((True, False) if cout <= 64 else (True,)):
         out_img = torch.full((b, 3, h, w), float("nan"), device=gpu)
         feat_buf = {}
@@ -368,6 +383,49 @@ def test_fused_torgb_epilogue_equals_separate_launches(gpu, cin, cout, h, w, wit
             np.testing.assert_allclose(feat_buf["f"].cpu().numpy(), feat_want.numpy(), atol=5e-4, rtol=1e-4)
         else:
             assert torch.isnan(feat_buf["f"]).all()  # never written
+
+
+_HUGE = 1 << 30
+
+
+@pytest.mark.parametrize("with_skip", [True, False])
+@pytest.mark.parametrize("cin,cout,h,w,huge,mode,instance", [
+    (32, 32, 16, 32, (), 5, r"modconv_w2dw_kernel<"),                                                                      # modconv_w2dw_kernel
+    (32, 64, 8, 32, (), 5, r"modconv_w2d_kernel<4, 2, "),                                                                       # modconv_w2d_kernel<4, 2>
+    (8, 32, 16, 32, ("winograd2d_min_cout",), 3, r"modconv_mfma_kernel<\d+, \d+, \d+, 3, "),                                                 # pixel quads: the three-dword store of modconv.hip
+    (8, 32, 16, 32, ("winograd2d_min_cout", "winograd43_min_cout"), 2, r"modconv_mfma_kernel<\d+, \d+, \d+, 2, "),                           # pixel pairs
+    (8, 32, 16, 16, ("winograd2d_min_cout", "winograd43_min_cout", "winograd_min_cout"), 0, r"modconv_mfma_kernel<\d+, \d+, \d+, 0, ")])     # single pixels
+def test_fused_torgb_uint8_frames_equal_oracle(gpu, cin, cout, h, w, huge, mode, instance, with_skip):
+    """The uint8 frame epilogue of the fused ToRGB, per kernel that has a copy of it: frames (in a red-zoned window: the 12-byte stores must
+    not overrun) bit-equal to the oracle's frames_to_uint8 of the tapped fp32 image, the tap itself within the fused test's tolerance."""
+    from oracle import stylegan2_oracle as so
+    from redzone import Guard
+
+    def pin_mode(conv):
+        conv.conv.winograd2d_min_cout = 32
+        for name in huge:
+            setattr(conv.conv, name, _HUGE)
+        assert conv.conv.conv_mode(h, w) == mode
+
+    f = _fused_torgb_setup(gpu, cin, cout, h, w, with_skip, pin_mode)
+    b = f["b"]
+    g = Guard(gpu)
+    u8 = g.out((b, h, w, 3), "u8", torch.uint8)
+    out_img = torch.full((b, 3, h, w), float("nan"), device=gpu)
+    feat_buf = {}
+
+    def bufs(name, shape):
+        feat_buf[name] = torch.full(shape, float("nan"), device=gpu)
+        return feat_buf[name]
+
+    fuse = dict(module=f["rgb"], s_off=cin, skip=f["skip"].to(gpu) if with_skip else None, out=out_img, store=True, u8=u8, tap=True)
+    f["conv"].run(f["x"].to(gpu), f["styles"], 0, f["demod"].view(b, cout), f["nz"].to(gpu), bufs, "f", rgb=fuse)
+    assert fuse.get("done"), "the layer was expected to take the fused path"
+    assert re.match(instance, _lib.last_modconv_instance()), _lib.last_modconv_instance()  # the copy of the epilogue this case is about
+    tap = out_img.cpu()
+    assert np.array_equal(u8.cpu().numpy(), so.frames_to_uint8(tap))
+    np.testing.assert_allclose(tap.numpy(), f["img_want"], atol=2e-3, rtol=1e-4)
+    g.check(written=("u8",), nonfinite_ok=("u8",))
 
 
 def _lowres_setup(gpu, cin, cout, h, w, b, up, seed):
