@@ -390,6 +390,12 @@ int maua_frames_to_u8(const float* img, uint8_t* out, int batch, int h, int w, v
  * (dst + 0.5) * in/out - 0.5, clamped taps, horizontal pass rounded to 8 bits, then vertical).  MAUA_ENOSYS for a down-scale. */
 int maua_crop_resize_u8(const uint8_t* in, uint8_t* out, int batch, int in_h, int in_w, int x0, int y0, int crop_w, int crop_h,
                         int out_w, int out_h, void* stream);
+/* Packed uint8 frames rgb[B,h,w,3] (what the two entries above produce) -> planar YUV 4:2:0 out[B, h*w*3/2]: per frame the Y plane
+ * [h, w], then U [h/2, w/2], then V [h/2, w/2] (I420, ffmpeg's rawvideo yuv420p).  ITU-R BT.601 limited range in integer arithmetic
+ * (the formula is in csrc/yuv420.hip), chroma from the box average of each 2 x 2 block (centre siting).  h and w even and positive
+ * (MAUA_EINVAL otherwise); batch == 0 is a successful no-op, more than 65535 frames a launch are MAUA_ENOSYS.  Any even width and any
+ * alignment is served; w % 8 == 0 with 8-byte aligned buffers takes the vector path.  (Additive: the ABI version is unchanged.) */
+int maua_rgb_to_yuv420p_u8(const uint8_t* rgb, uint8_t* out, int batch, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ audio / temporal
  * Circular Gaussian FIR along time (audioreactive/signal.py:319-368): x [T, F] -> y [T, F], taps[2*radius+1]

@@ -58,6 +58,8 @@ CLI_FLAGS = (
     ("--base_res_factor", dict(type=float, default=1)),
     ("--ffmpeg_preset", dict(type=str, default="slow")),
     ("--output_file", dict(type=str, default=None)),
+    # (not one of the reference's: what travels to the encoder — planar 4:2:0 is made on the device, render.frames_to_yuv420p)
+    ("--pipe_pix_fmt", dict(type=str, default="rgb24", choices=render.PIPE_PIX_FMTS)),
 )
 
 
@@ -347,8 +349,10 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # randomize_noise: every rank generates the maps of its frames from the job's one broadcast seed (Generator.random_noise)
         generator.noise_seed = seed + 3
     try:
+        # generate() keeps the reference's parameter list: the pipe format arrives in the namespace (--pipe_pix_fmt, a plugin's OVERRIDE,
+        # a caller's own ``args``) or through $MAUA_PIPE_PIX_FMT
         written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
-                          output_file, randomize_noise, ffmpeg_preset, shard)
+                          output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None))
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -359,8 +363,11 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
 
 
 def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
-            randomize_noise, ffmpeg_preset, shard):
-    if shard is None:
+            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None):
+    if pipe_pix_fmt not in (None, "rgb24"):
+        written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
+                                      truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt)
+    elif shard is None:
         written = render.render(generator=generator, latents=latents, noise=noise, audio_file=audio_file, offset=offset,
                                 duration=duration, batch_size=batch, truncation=truncation, bends=bends, rewrites=rewrites,
                                 out_size=out_size, output_file=output_file, randomize_noise=randomize_noise,
@@ -420,6 +427,7 @@ def main(argv=None):
         settings[key] = value
         setattr(args, key, value)
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
+    settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)
     finally:

@@ -15,6 +15,8 @@ with ``input_is_latent=True``), different machinery:
 
 Sinks: ffmpeg rawvideo pipe (same pixel format / codec arguments as render.py:58-91) when an ``ffmpeg`` binary exists,
 otherwise raw rgb24 bytes to ``output_file`` (+ ".rgb24"), or a null sink for benchmarking (``output_file=None``).
+Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to planar YUV 4:2:0 on the device (frames_to_yuv420p) before
+they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
 """
 import gc
 import os
@@ -50,39 +52,71 @@ def _output_dims(out_size):
     raise Exception("The only output sizes currently supported are: 512, 1024, 1080, or 1920")
 
 
+PIPE_PIX_FMTS = ("rgb24", "yuv420p")  # what travels to the sink: packed RGB (the reference's, default) or planar 4:2:0 made on the device
+# how a yuv420p pipe is tagged: the matrix / range csrc/yuv420.hip converts with (BT.601 limited range), so that players decode with it
+YUV420P_TAGS = ["-colorspace", "smpte170m", "-color_primaries", "smpte170m", "-color_trc", "smpte170m", "-color_range", "tv"]
+
+
+def _pipe_pix_fmt(pix_fmt):
+    """A ``pipe_pix_fmt`` argument resolved: None -> $MAUA_PIPE_PIX_FMT -> rgb24."""
+    pix_fmt = pix_fmt or os.environ.get("MAUA_PIPE_PIX_FMT") or "rgb24"
+    if pix_fmt not in PIPE_PIX_FMTS:
+        raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
+    return pix_fmt
+
+
 class FrameSink:
-    """Ordered consumer of uint8 [H, W, 3] frames."""
+    """Ordered consumer of uint8 [H, W, 3] frames (``pix_fmt="rgb24"``) or of flat planar I420 frames [H * W * 3 / 2]
+    (``pix_fmt="yuv420p"``: converted, and for wide outputs resized, on the device — frames_to_yuv420p)."""
 
     def __init__(self, output_file, width, height, framerate, audio_file=None, offset=0, duration=None,
-                 ffmpeg_preset="slow"):
+                 ffmpeg_preset="slow", pix_fmt="rgb24"):
+        if pix_fmt not in PIPE_PIX_FMTS:
+            raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
+        if pix_fmt == "yuv420p" and (width % 2 or height % 2):
+            raise ValueError(f"yuv420p needs even dimensions, got {width}x{height}")
         self.w, self.h = width, height
+        self.pix_fmt = pix_fmt
         self.proc = None
         self.file = None
         self.count = 0
         if output_file is None:
             return
         if shutil.which("ffmpeg") is not None:
-            cmd = ["ffmpeg", "-hide_banner", "-y", "-v", "warning", "-f", "rawvideo", "-pix_fmt", "rgb24", "-framerate",
+            cmd = ["ffmpeg", "-hide_banner", "-y", "-v", "warning", "-f", "rawvideo", "-pix_fmt", pix_fmt, "-framerate",
                    f"{framerate}", "-s", f"{width}x{height}", "-i", "pipe:"]
             if audio_file is not None:
                 cmd += ["-ss", f"{offset}", "-t", f"{duration}", "-guess_layout_max", "0", "-i", audio_file]
             cmd += ["-r", f"{framerate}", "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-preset", ffmpeg_preset]
+            if pix_fmt == "yuv420p":
+                cmd += YUV420P_TAGS
             if audio_file is not None:
                 cmd += ["-b:a", "320K", "-ac", "2"]
             cmd += [output_file]
             self.proc = subprocess.Popen(cmd, stdin=subprocess.PIPE)
         else:
-            path = output_file if output_file.endswith(".rgb24") else output_file + ".rgb24"
+            ext = "." + pix_fmt
+            path = output_file if output_file.endswith(ext) else output_file + ext
             audio = f" -ss {offset} -t {duration} -guess_layout_max 0 -i {audio_file}" if audio_file is not None else ""
             mux = " -b:a 320K -ac 2" if audio_file is not None else ""
-            target = output_file[:-len(".rgb24")] if output_file.endswith(".rgb24") else output_file
-            print(f"ffmpeg binary not found: writing raw rgb24 frames ({width}x{height}) to {path}\n"
-                  f"  encode later with: ffmpeg -f rawvideo -pix_fmt rgb24 -framerate {framerate} -s {width}x{height} -i {path}{audio} "
-                  f"-r {framerate} -vcodec libx264 -pix_fmt yuv420p -preset {ffmpeg_preset}{mux} {target}")
+            tags = " " + " ".join(YUV420P_TAGS) if pix_fmt == "yuv420p" else ""
+            target = output_file[:-len(ext)] if output_file.endswith(ext) else output_file
+            print(f"ffmpeg binary not found: writing raw {pix_fmt} frames ({width}x{height}) to {path}\n"
+                  f"  encode later with: ffmpeg -f rawvideo -pix_fmt {pix_fmt} -framerate {framerate} -s {width}x{height} -i {path}{audio} "
+                  f"-r {framerate} -vcodec libx264 -pix_fmt yuv420p -preset {ffmpeg_preset}{tags}{mux} {target}")
             self.file = open(path, "wb")
 
     def write(self, frame):
-        """frame: numpy uint8 [H, W, 3]; wide 2048-px outputs are cropped + resized as render.py:98-105."""
+        """frame: numpy uint8 [H, W, 3]; wide 2048-px outputs are cropped + resized as render.py:98-105.  A yuv420p sink takes the flat
+        planar frame [H * W * 3 / 2] as it is: it was resized on the device before the conversion, neither PIL nor the crop applies."""
+        if self.pix_fmt == "yuv420p":
+            if frame.ndim != 1 or frame.shape[0] != self.w * self.h * 3 // 2:
+                raise ValueError(f"a yuv420p frame of {self.w}x{self.h} is a flat array of {self.w * self.h * 3 // 2} bytes, got shape "
+                                 f"{tuple(frame.shape)}")
+            if self.proc is not None or self.file is not None:
+                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(np.ascontiguousarray(frame)).cast("B"))
+            self.count += 1
+            return
         if frame.shape[1] == 2048 or frame.shape[0] == 2048:
             import PIL.Image
 
@@ -207,6 +241,32 @@ def crop_resize_for_delivery(u8, out_size, scratch):
         _lib.check(_lib.load().maua_crop_resize_u8(u8.data_ptr(), out.data_ptr(), b, h, w, x0, y0, cw, ch, ow, oh,
                                                    _lib.stream_ptr(u8.device)), "maua_crop_resize_u8")
     return out
+
+
+def frames_to_yuv420p(u8, scratch):
+    """uint8 [b, H, W, 3] device frames (frames_to_uint8 / crop_resize_for_delivery) -> planar YUV 4:2:0 [b, H * W * 3 // 2] uint8 on the
+    device, on the current (= producing) stream: per frame the Y plane, then U, then V (I420: ffmpeg's rawvideo yuv420p), BT.601 limited
+    range by maua_rgb_to_yuv420p_u8.  ``scratch``: dict holding the reusable output buffers, the protocol of crop_resize_for_delivery."""
+    if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != th.uint8 or not u8.is_cuda:
+        raise RuntimeError(f"frames_to_yuv420p takes uint8 [b, H, W, 3] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
+    b, h, w, _ = u8.shape
+    if h % 2 or w % 2:
+        raise ValueError(f"yuv420p needs even frame dimensions, got {w}x{h}")
+    u8 = u8.contiguous()
+    key = ("yuv420p", u8.data_ptr(), b, h, w)
+    out = scratch.get(key)
+    if out is None:
+        out = scratch[key] = th.empty((b, h * w * 3 // 2), dtype=th.uint8, device=u8.device)
+    with th.cuda.device(u8.device):
+        _lib.check(_lib.load().maua_rgb_to_yuv420p_u8(u8.data_ptr(), out.data_ptr(), b, h, w, _lib.stream_ptr(u8.device)),
+                   "maua_rgb_to_yuv420p_u8")
+    return out
+
+
+def _deliverable(u8, out_size, pix_fmt, scratch):
+    """A batch as it leaves the device: wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0."""
+    u8 = crop_resize_for_delivery(u8, out_size, scratch)
+    return frames_to_yuv420p(u8, scratch) if pix_fmt == "yuv420p" else u8
 
 
 _LANE_STREAMS = {}
@@ -503,10 +563,13 @@ def render(generator, latents, noise, offset, duration, batch_size, out_size, ou
 
 
 def render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                 bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None):
+                 bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
     """``render`` with an optional ``_shard = (lo, hi, n_frames)``: set by generate() after sharding.scatter_frames, it says
-    that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames."""
+    that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames.
+    ``pipe_pix_fmt``: "rgb24" or "yuv420p" (PIPE_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24) — what crosses to the host, to rank 0
+    and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the environment variable."""
     width, height = _output_dims(out_size)
+    pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
     rank, world = sharding.rank_world()
     # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM, sharding.FrameStream) or "host"
     # (per-rank D2H into shared memory, sharding.HostFrameStore)
@@ -527,7 +590,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     dev = device_of(generator)
     sink = None
     if rank == 0:
-        sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset)
+        sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt)
 
     worker = SinkWorker(sink) if sink is not None else None
     locked = False
@@ -556,7 +619,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
             resized = {}
             for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
                                         randomize_noise, lanes=n_lanes):
-                u8 = crop_resize_for_delivery(u8, out_size, resized)  # 2048-px frames leave the device as 1920x1080 already
+                u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)  # 2048-px frames leave the device as 1920x1080 already
                 slot = free.get()
                 count = u8.shape[0]
                 # slots hold a FULL batch; the tail batch of a render uses a prefix (re-pinning per shape cost 2 x 6.5 ms per render)
@@ -603,7 +666,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
             try:
                 for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
                                             randomize_noise, frame_range=frame_range):
-                    u8 = crop_resize_for_delivery(u8, out_size, resized)
+                    u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)
                     if store is None:
                         store = sharding.HostFrameStore(n_frames, batch_size, tuple(u8.shape[1:]), dev, token)
                         if rank == 0:
@@ -611,7 +674,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
                     store.push(k, u8)
                     k += 1
                 if store is None:
-                    store = sharding.HostFrameStore(n_frames, batch_size, _stream_frame_shape(generator, out_size), dev, token)
+                    store = sharding.HostFrameStore(n_frames, batch_size, _stream_frame_shape(generator, out_size, pipe_pix_fmt), dev, token)
                     if rank == 0:
                         reader = start_reader()
                 store.finish()
@@ -638,7 +701,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
 
             for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
                                         randomize_noise, frame_range=frame_range):
-                u8 = crop_resize_for_delivery(u8, out_size, resized)
+                u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)
                 if stream is None:  # the frame shape is whatever the generator (and its layer-0 bends) produce
                     stream = sharding.FrameStream(n_frames, batch_size, tuple(u8.shape[1:]), dev)
                 stream.push(k, u8)
@@ -646,7 +709,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
                 if rank == 0:
                     deliver(False)
             if stream is None:  # a rank whose block is empty (more ranks than frames) still takes part in every round
-                stream = sharding.FrameStream(n_frames, batch_size, _stream_frame_shape(generator, out_size), dev)
+                stream = sharding.FrameStream(n_frames, batch_size, _stream_frame_shape(generator, out_size, pipe_pix_fmt), dev)
             stream.finish()
             if rank == 0:
                 deliver(True)
@@ -670,12 +733,14 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     return sink.count if sink is not None else 0
 
 
-def _stream_frame_shape(generator, out_size):
+def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
     """[H, W, 3] of the frames the generator produces for ``out_size`` (1920 / 1080 render 2048-px-wide / -high frames
-    that the sink crops and resizes, render.py:98-105)."""
+    that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p"."""
     side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
     if out_size == 1920:
-        return (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
-    if out_size == 1080:
-        return (1920, 1080, 3) if side == 1024 else (2 * side, side, 3)
-    return (side, side, 3)
+        shape = (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
+    elif out_size == 1080:
+        shape = (1920, 1080, 3) if side == 1024 else (2 * side, side, 3)
+    else:
+        shape = (side, side, 3)
+    return (shape[0] * shape[1] * 3 // 2,) if pix_fmt == "yuv420p" else shape
