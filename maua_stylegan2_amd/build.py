@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libmaua_hip.so")
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "epilogue.h"), os.path.join(CSRC, "philox.h"), os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "maua_hip.h")]
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "maua_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/maua_hip.h"
 
@@ -12,7 +13,7 @@
     } while (0)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize for a kernel that uses more than the default 64 KB of LDS.  The attribute belongs to
-// (function, device): SUCCESS is remembered per device in the caller's `done` bit mask (one static per launcher), a failure is
+// (function, device): SUCCESS is remembered per device in the caller's `done` bit mask (maua_launch_conv's, one per instance), a failure is
 // returned as the launch's hipError_t (> 0, the contract of include/maua_hip.h) and retried by the next call instead of being cached
 // for the life of the process.  Relaxed atomics: two threads racing on the first call both set the attribute, which is harmless.
 static inline int maua_allow_full_lds(const void* kern, unsigned long long* done, int bytes = 160 * 1024) {
@@ -29,6 +30,34 @@ static inline int maua_allow_full_lds(const void* kern, unsigned long long* done
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Grid of a grid-stride kernel (weight packers, reducers, frame conversion): one 256-thread block per 256 elements, at most `cap` blocks.
+static inline unsigned pack_grid(int64_t total, int64_t cap = 4096) {
+    const int64_t blocks = ceil_div64(total, 256);
+    return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+// An operand the kernels address through a raw buffer descriptor (conv_device.h) with 32-bit byte offsets: descriptors carry 2^31 - 1
+// checked bytes and the offset 2^31 means "outside" (the source of the zero padding), so every real byte offset must stay below that.
+static inline bool fits_raw_descriptor(int64_t bytes) { return bytes <= 0x7fffffffLL; }
+
+// Name of the kernel template instance that the last convolution launch of this process ran, as rocprofv3 prints it
+// (maua_modconv_last_instance): bench.py, tools/microbench.py and the tables under profiles/ join on it.  A launch that is followed by
+// helper kernels (edge lines, seam pass, reducers) keeps its main kernel's name.
+inline char g_conv_instance[96] = "";
+
+// THE launch of a convolution kernel instance (256 threads, dynamic LDS beyond the default 64 KB allowed): attribute, name, launch,
+// check.  The kernel is a template argument, never a host function-pointer variable (build.py on -fsanitize=function says why), which
+// also gives every instance its own `lds_ok` mask.
+template <auto Kern, typename... Args>
+int maua_launch_conv(const char* name, int64_t blocks, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    static unsigned long long lds_ok = 0;  // devices on which the attribute has been set
+    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(Kern), &lds_ok)) return rc;
+    snprintf(g_conv_instance, sizeof(g_conv_instance), "%s", name);
+    hipLaunchKernelGGL(Kern, dim3((unsigned)blocks), dim3(256), lds_bytes, st, args...);
+    MAUA_LAUNCH_CHECK();
+    return 0;
+}
 
 // Bijective XCD-aware remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"): block b runs on
 // XCD b % 8; give every XCD one contiguous chunk of the logical tile range so that neighbouring tiles
@@ -91,13 +120,11 @@ struct RgbArgs {
 
 // modconv_w2d.hip (mode 5 of maua_modconv3x3_f32 / maua_styledconv_torgb_f32): 2-D Winograd F(2x4, 3x3) plain convolution
 int maua_w2d_tiles(int cin, int cout, int h, int w, int* tm, int* tn);
-const char* maua_w2d_last_instance();
 int maua_w2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, int batch, int cin,
                     int cout, int h, int w, float wscale, int fuse_act, const TailArgs& tail, const RgbArgs* rgb, const float* post_s,
                     void* stream);
 
 // modconv_up2d.hip (mode 6 of maua_modconv3x3_f32): transposed convolution with F(2,2) on both axes of its polyphase form
-const char* maua_up2d_last_instance();
 int64_t maua_up2d_ws_floats(int batch, int cin, int h);
 int maua_up2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
                      int cout, int h, int w, float wscale, void* stream);
@@ -110,7 +137,6 @@ int maua_up2d16_launch(const float* x, const float* wq, const float* s, int s_st
 
 // modconv_sbf16.hip (mode 7 of maua_modconv3x3_f32; side measurement, off by default): plain 3x3 convolution with split-bf16 products
 int maua_sbf16_ok(int cin, int cout, int h, int w);
-const char* maua_sbf16_last_instance();
 int maua_sbf16_launch(const float* x, const void* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
                       int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, void* stream);
 int maua_up2d_edge_launch(const float* x, const float* edge_taps, const float* s, int s_stride, const float* d, float* y, const float* xcol,

@@ -171,8 +171,7 @@ extern "C" int maua_const_conv_ok(int cin, int cout, int h, int w) { return h ==
 extern "C" int maua_pack_const_conv_f32(const float* w, const float* c, float* T, int cout, int cin, int h, int wd, void* stream) {
     if (!w || !c || !T) return MAUA_EINVAL;
     if (!maua_const_conv_ok(cin, cout, h, wd)) return MAUA_ENOSYS;
-    const int64_t blocks = ceil_div64((int64_t)cout * cin, 256);
-    hipLaunchKernelGGL(pack_const_conv_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, w, c, T, cout, cin);
+    hipLaunchKernelGGL(pack_const_conv_kernel, dim3(pack_grid((int64_t)cout * cin)), dim3(256), 0, (hipStream_t)stream, w, c, T, cout, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }

@@ -32,15 +32,10 @@
 // several images and for the 32-channel F(2,3) config).  Measured rule of this chip that shapes everything above: VALU /
 // SALU instructions of co-resident waves do NOT hide under the 64-cycle MFMAs (profiles/r01_pmc_modconv.md) — fewer
 // MFMAs per output (Winograd) and fewer non-MFMA instructions are what pay, not occupancy or prefetch depth.
+#include "conv_device.h"
 #include "epilogue.h"
 
 #include <cstdio>
-#include <type_traits>
-
-// the buffer-descriptor builtins (MUBUF `buffer_load ... lds`) only exist in the device pass
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MAUA_DEVICE_PASS 1
-#endif
 
 // Ablation / A-B switches only exist in -DMAUA_EXPERIMENTS builds (tools/build_exp.sh): the product kernels carry no debug
 // branches and the product library exports no tuning entry.
@@ -53,12 +48,6 @@
 #endif
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef f32x2 f32x2u __attribute__((aligned(4)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));
 
 // channels per K chunk: the weight tile As[rows][CC][BM] is kept at <= 18..24 KB so that the double buffer fits 2-3x per CU
 constexpr int chunk_channels(int bm, int bn = 0, int mode = 0) {
@@ -553,24 +542,15 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
         // in flight the compiler's wait insertion treats the LGKM counter as out of order and turns EVERY LDS wait of the
         // chunk into lgkmcnt(0) (profiles/r01_isa_modconv.md); with the buffer form it emits partial counts, which is what
         // the look-ahead LDS reads of the pipelined MFMA phases need.
-#ifdef MAUA_DEVICE_PASS
-        const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp), 0, 0x7fffffff, 0x00020000);
-#endif
+        const buffer_rsrc_t w_rsrc = raw_buffer(p.wp);
         auto issue_dma = [&](int chunk, int buf) {
             float* dst = As + buf * A_FLOATS;
-            (void)dst;
 #pragma unroll
             for (int k = 0; k < A_PER_WAVE; ++k) {
                 const int i = wave + 4 * k;  // scalar
                 constexpr bool RAGGED = (NTAPS * CC) % RPI != 0;  // only then can lanes of the last instruction be masked
                 if (i < A_INSTR && (!RAGGED || a_goff[k] >= 0))
-#ifdef MAUA_DEVICE_PASS
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                        w_rsrc, (__attribute__((address_space(3))) void*)(dst + i * 256), 16, a_goff[k] * 4,
-                        (int)(((size_t)chunk * CC * g.CoutPad + m0) * 4), 0, 0);
-#else
-                    (void)a_goff[k];
-#endif
+                    lds_dma16(w_rsrc, dst + i * 256, a_goff[k] * 4, (int)(((size_t)chunk * CC * g.CoutPad + m0) * 4));
             }
         };
         auto load_patch = [&](int chunk) {
@@ -636,12 +616,9 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
                 rel_bytes[i] = pvalid[i] ? (unsigned)(src_off[i] - b0 * g.Cin * (int)plane_in) * 4u : 0u;
             const char* ximg = reinterpret_cast<const char*>(p.x + (size_t)b0 * g.Cin * plane_in);
             const size_t plane_bytes = plane_in * sizeof(float);
-            (void)ximg, (void)plane_bytes;  // (only the device pass builds the descriptor)
-#ifdef MAUA_DEVICE_PASS
+            (void)plane_bytes;  // (its one use is the device pass's 4-byte DMA below)
             // one image's features (Cin planes, < 2 GiB: checked on the host) behind a raw buffer descriptor
-            const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<char*>(ximg), 0, 0x7fffffff, 0x00020000);
-#endif
+            const buffer_rsrc_t x_rsrc = raw_buffer(ximg);
             auto issue_patch = [&](int chunk, int buf) {
                 float* dst = Ps + buf * PBUF + wave * 64;
                 (void)dst;
@@ -1397,18 +1374,12 @@ Plan make_plan(int batch, int cin, int cout, int h, int w, int mode) {
     return pl;
 }
 
-char g_last_instance[96] = "";
-
 template <int BM, int BN, int WM, int UP, bool MULTI, bool FAST, int MAXP>
 int launch_conv_impl2(const Plan& pl, const ConvPtrs& ptrs, hipStream_t st) {
-    auto kern = modconv_mfma_kernel<BM, BN, WM, UP, MULTI, FAST, MAXP>;
-    snprintf(g_last_instance, sizeof(g_last_instance), "modconv_mfma_kernel<%d, %d, %d, %d, %s, %s, %d>", BM, BN, WM, UP,
-             MULTI ? "true" : "false", FAST ? "true" : "false", MAXP);
-    static unsigned long long lds_ok = 0;  // per launcher: devices on which the attribute has been set (common.h)
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(kern), &lds_ok, 160 * 1024)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)pl.blocks), dim3(256), pl.lds_bytes, st, pl.g, ptrs);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    char name[96];
+    snprintf(name, sizeof(name), "modconv_mfma_kernel<%d, %d, %d, %d, %s, %s, %d>", BM, BN, WM, UP, MULTI ? "true" : "false",
+             FAST ? "true" : "false", MAXP);
+    return maua_launch_conv<modconv_mfma_kernel<BM, BN, WM, UP, MULTI, FAST, MAXP>>(name, pl.blocks, pl.lds_bytes, st, pl.g, ptrs);
 }
 
 template <int BM, int BN, int WM, int UP, bool MULTI, bool FAST>
@@ -1440,10 +1411,8 @@ int maua_conv_cfg_set(int v) { g_conv_cfg = v; return 0; }
 extern "C" int maua_pack_weight_f32(const float* w, float* wp, float* wsq, int cout, int cin, int ktaps, void* stream) {
     if (!w || cout <= 0 || cin <= 0 || ktaps <= 0) return MAUA_EINVAL;
     const int cout_pad = pad32(cout);
-    const int64_t total = (int64_t)cout_pad * cin;
-    const int64_t blocks = ceil_div64(total, 256);
-    hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, wp, wsq, cout, cout_pad, cin, ktaps);
+    hipLaunchKernelGGL(pack_weight_kernel, dim3(pack_grid((int64_t)cout_pad * cin)), dim3(256), 0, (hipStream_t)stream, w, wp, wsq, cout,
+                       cout_pad, cin, ktaps);
     MAUA_LAUNCH_CHECK();
     return 0;
 }
@@ -1451,9 +1420,7 @@ extern "C" int maua_pack_weight_f32(const float* w, float* wp, float* wsq, int c
 extern "C" int maua_pack_weight_wino_f32(const float* w, float* wq, int cout, int cin, void* stream) {
     if (!w || !wq || cout <= 0 || cin <= 0) return MAUA_EINVAL;
     const int cout_pad = wino_cout_pad(cout);
-    const int64_t blocks = ceil_div64((int64_t)cout_pad * cin, 256);
-    hipLaunchKernelGGL(pack_weight_wino_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, wq, cout, cout_pad, cin);
+    hipLaunchKernelGGL(pack_weight_wino_kernel, dim3(pack_grid((int64_t)cout_pad * cin)), dim3(256), 0, (hipStream_t)stream, w, wq, cout, cout_pad, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }
@@ -1461,9 +1428,7 @@ extern "C" int maua_pack_weight_wino_f32(const float* w, float* wq, int cout, in
 extern "C" int maua_pack_weight_upwino_f32(const float* w, float* wq, int cout, int cin, void* stream) {
     if (!w || !wq || cout <= 0 || cin <= 0) return MAUA_EINVAL;
     const int cout_pad = pad32(cout);
-    const int64_t blocks = ceil_div64((int64_t)cout_pad * cin, 256);
-    hipLaunchKernelGGL(pack_weight_upwino_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, wq, cout, cout_pad, cin);
+    hipLaunchKernelGGL(pack_weight_upwino_kernel, dim3(pack_grid((int64_t)cout_pad * cin)), dim3(256), 0, (hipStream_t)stream, w, wq, cout, cout_pad, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }
@@ -1471,9 +1436,7 @@ extern "C" int maua_pack_weight_upwino_f32(const float* w, float* wq, int cout, 
 extern "C" int maua_pack_weight_wino43_f32(const float* w, float* wq, int cout, int cin, void* stream) {
     if (!w || !wq || cout <= 0 || cin <= 0) return MAUA_EINVAL;
     const int cout_pad = wino_cout_pad(cout);
-    const int64_t blocks = ceil_div64((int64_t)cout_pad * cin, 256);
-    hipLaunchKernelGGL(pack_weight_wino43_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, wq, cout, cout_pad, cin);
+    hipLaunchKernelGGL(pack_weight_wino43_kernel, dim3(pack_grid((int64_t)cout_pad * cin)), dim3(256), 0, (hipStream_t)stream, w, wq, cout, cout_pad, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }
@@ -1490,7 +1453,7 @@ extern "C" int64_t maua_modconv_ws_floats(int batch, int cin, int cout, int h, i
 // timings with the per-instance PMC tables under profiles/ without re-implementing the plan.
 extern "C" int maua_modconv_last_instance(char* buf, int buf_len) {
     if (!buf || buf_len <= 0) return MAUA_EINVAL;
-    snprintf(buf, (size_t)buf_len, "%s", g_last_instance);
+    snprintf(buf, (size_t)buf_len, "%s", g_conv_instance);
     return 0;
 }
 
@@ -1507,22 +1470,15 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
     // 2-D Winograd kernels' epilogue
     if ((!s && up != 5 && up != 6) || (post_s && up != 5)) return MAUA_ENOSYS;
     if (int rc = tail.check(fuse_act != 0)) return rc;  // (without fuse_act a frame source's noise is not read: its weight may be absent)
-    if (up == 5) {  // 2-D Winograd F(2x4, 3x3), modconv_w2d.hip
-        const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, fuse_act, tail, rgb, post_s, stream);
-        if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_w2d_last_instance());
-        return rc;
-    }
+    if (up == 5)  // 2-D Winograd F(2x4, 3x3), modconv_w2d.hip
+        return maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, fuse_act, tail, rgb, post_s, stream);
     if (up == 7 || up == 8) {  // plain (7) / transposed (8) conv with split-bf16 products (side measurement), modconv_sbf16.hip
         if (rgb) return MAUA_ENOSYS;
-        const int rc = maua_sbf16_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, up == 8, wscale, fuse_act, tail, stream);
-        if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_sbf16_last_instance());
-        return rc;
+        return maua_sbf16_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, up == 8, wscale, fuse_act, tail, stream);
     }
     if (up == 6) {  // transposed conv, F(2,2) on both axes, modconv_up2d.hip: raw output only (the blur kernel applies the tail)
         if (fuse_act || rgb) return MAUA_EINVAL;
-        const int rc = maua_up2d_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, wscale, stream);
-        if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_up2d_last_instance());
-        return rc;
+        return maua_up2d_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, wscale, stream);
     }
     if ((int64_t)batch * cin * h * w > 0x7fffffffLL) return MAUA_EINVAL;  // 32-bit patch offsets
     if (up < 0 || up > 4 || ((up == 2 || up == 4) && (w & 1)) || (up == 3 && (w & 3))) return MAUA_EINVAL;
@@ -1583,8 +1539,7 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
     }
     if (pl.g.splits > 1) {
         const int64_t total = pl.g.ws_slab;
-        const int64_t blocks = ceil_div64(total, 256);
-        hipLaunchKernelGGL(reduce_tail_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, ws,
+        hipLaunchKernelGGL(reduce_tail_kernel, dim3(pack_grid(total, 2048)), dim3(256), 0, st, ws,
                            pl.g.splits, pl.g.ws_slab, y, d, tail.noise, tail.noise_batch_stride, tail.noise_w, tail.bias, fuse_act, cout,
                            (int64_t)pl.g.OH * pl.g.OW, total, tail.src, tail.noise_slot);
         MAUA_LAUNCH_CHECK();
@@ -1631,7 +1586,6 @@ extern "C" int maua_upconv_blur_lowres_f32(const float* x, const float* wp, cons
     if (up == 6) {  // F(2,2) on both axes (wp = maua_pack_weight_up2d_f32), K split over workgroups; the exported column behind the slabs
         float* xcol = ws + (int64_t)maua_up2d16_splits(batch, cin, cout, h, w) * slab;
         if (int rc = maua_up2d16_launch(x, wp, s, s_stride, ws, xcol, batch, cin, cout, h, w, wscale, &splits, stream)) return rc;
-        snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_up2d_last_instance());
     } else if (int rc = modconv_impl(x, wp, s, s_stride, nullptr, y, batch, cin, cout, h, w, 1, wscale, 0, TailArgs{}, ws, nullptr, nullptr, stream,
                                      &splits))  // (the convolution writes slabs only: y is a placeholder)
         return rc;
@@ -1678,9 +1632,7 @@ extern "C" int maua_styledconv_torgb_partial_f32(const float* x, const float* wp
     const TailArgs tail{noise, noise_w, bias, noise_batch_stride, src, noise_slot};
     if (int rc = tail.check()) return rc;
     const RgbArgs rgb{rgb_w, rgb_s, nullptr, nullptr, nullptr, rgb_partial, nullptr, rgb_wscale, 3};
-    const int rc = maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, 1, tail, &rgb, post_s, stream);
-    if (rc == 0) snprintf(g_last_instance, sizeof(g_last_instance), "%s", maua_w2d_last_instance());
-    return rc;
+    return maua_w2d_launch(x, wp, s, s_stride, d, y, batch, cin, cout, h, w, wscale, 1, tail, &rgb, post_s, stream);
 }
 
 extern "C" int maua_styledconv_torgb_f32(const float* x, const float* wp, const float* s, int s_stride, const float* d,

@@ -25,23 +25,14 @@
 //   A operand: the packed weight (maua_pack_weight_sbf16_f32) is stored in HBM in MFMA lane order, [m-tile][chunk][tap][hi | lo]
 //     [lane][8], and goes straight to registers (one 16-byte load per lane and half, two taps ahead): no LDS, no DMA.
 // The transposed layers (mode 8) run the same arithmetic in their polyphase form on the input grid — modconv_sbf16_up_kernel below.
-#include "common.h"
+#include "conv_device.h"
 
 #include <cstdio>
-#include <type_traits>
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MAUA_DEVICE_PASS 1
-#endif
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SB_BM = 128;   // output channels per workgroup
 constexpr int SB_KC = 16;    // input channels per K chunk = K of v_mfma_f32_32x32x16_bf16
@@ -51,7 +42,6 @@ constexpr int SB_ITEMS = 2 * SB_PH * SB_PW;             // (k half, row, col) re
 constexpr int SB_PER_THREAD = (SB_ITEMS + 255) / 256;   // 3
 constexpr int SB_PLANE_BYTES = SB_ITEMS * 16;           // one hi (or lo) plane of a chunk
 constexpr int SB_BUF_BYTES = 2 * SB_PLANE_BYTES;
-constexpr unsigned SB_OOB = 0x80000000u;
 
 struct SbArgs {
     const float* x;
@@ -71,14 +61,6 @@ struct SbArgs {
     const maua_frame_source_t* src;
     int noise_slot;
 };
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
     const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);
@@ -142,14 +124,11 @@ __global__ __launch_bounds__(256, 2) void modconv_sbf16_kernel(SbArgs p) {
         const int row = rem / SB_PW, col = rem % SB_PW;
         const int yy = ty0 - 1 + row, xx = tx0 - 1 + col;
         const bool ok = idx < SB_ITEMS && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        item_voff[q] = ok ? (unsigned)kb * 8u * plane_bytes + ((unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : SB_OOB;
+        item_voff[q] = ok ? (unsigned)kb * 8u * plane_bytes + ((unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : kOutOfRange;
         item_lds[q] = (unsigned)idx * 16u;
         item_kb[q] = idx < SB_ITEMS ? kb : -1;
     }
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x) + (size_t)b0 * p.Cin * plane, 0, (int)((unsigned)p.Cin * plane_bytes), 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(p.x + (size_t)b0 * p.Cin * plane, (int)((unsigned)p.Cin * plane_bytes));
     // one item (8 channels of one patch pixel) is in flight at a time: item q of the next chunk is requested at tap 3 q and written to LDS
     // three taps later — 8 staging registers instead of 24
     float stage[8];
@@ -336,16 +315,12 @@ __global__ __launch_bounds__(256, 2) void modconv_sbf16_up_kernel(SbArgs p) {
         const int row = rem / SU_PW, col = rem % SU_PW;
         const int yy = ty0 - 1 + row, xx = tx0 - 1 + col;
         const bool ok = idx < SU_ITEMS && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        item_voff[q] = ok ? (unsigned)kb * 8u * plane_bytes + ((unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : SB_OOB;
+        item_voff[q] = ok ? (unsigned)kb * 8u * plane_bytes + ((unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : kOutOfRange;
         item_lds[q] = (unsigned)idx * 16u;
         item_kb[q] = idx < SU_ITEMS ? kb : -1;
     }
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x) + (size_t)b0 * p.Cin * plane, 0, (int)((unsigned)p.Cin * plane_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16x8*>(p.wq) + (size_t)mt_id * p.n_chunks * 18 * 64, 0, (int)((unsigned)p.n_chunks * SU_ABUF_BYTES), 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(p.x + (size_t)b0 * p.Cin * plane, (int)((unsigned)p.Cin * plane_bytes));
+    const buffer_rsrc_t w_rsrc = raw_buffer(p.wq + (size_t)mt_id * p.n_chunks * 18 * 64, (int)((unsigned)p.n_chunks * SU_ABUF_BYTES));
     float stage[SU_PER_THREAD][8];
     auto fetch = [&](int chunk) {
 #ifdef MAUA_DEVICE_PASS
@@ -376,17 +351,11 @@ __global__ __launch_bounds__(256, 2) void modconv_sbf16_up_kernel(SbArgs p) {
         }
     };
     auto issue_a = [&](int chunk, int buf) {  // 18 pieces of 1 KiB, dealt to the four waves
-#ifdef MAUA_DEVICE_PASS
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             const int i = wave + 4 * k;  // (scalar)
-            if (i < 18)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(lds_raw + buf * SU_ABUF_BYTES + i * 1024),
-                                                         16, i * 1024 + lane * 16, chunk * SU_ABUF_BYTES, 0, 0);
+            if (i < 18) lds_dma16(w_rsrc, lds_raw + buf * SU_ABUF_BYTES + i * 1024, i * 1024 + lane * 16, chunk * SU_ABUF_BYTES);
         }
-#else
-        (void)chunk, (void)buf;
-#endif
     };
 
     f32x16 acc[4][2];
@@ -507,8 +476,6 @@ __global__ __launch_bounds__(256) void pack_edge_taps_kernel(const float* __rest
     }
 }
 
-char g_sbf16_instance[48] = "";
-
 }  // namespace
 
 int maua_sbf16_ok(int cin, int cout, int h, int w) {
@@ -519,52 +486,26 @@ int maua_sbf16_up_ok(int cin, int cout, int h, int w) {
     return cin > 0 && cout > 0 && cin % SB_KC == 0 && cout % 32 == 0 && h % SB_TH == 0 && w % SB_TW == 0;
 }
 
-const char* maua_sbf16_last_instance() { return g_sbf16_instance; }
-
-namespace {
-template <int PHASE>
-int sbf16_launch_phase(const SbArgs& a, size_t lds_bytes, hipStream_t st) {
-    static unsigned long long lds_ok = 0;  // per launcher: devices on which the attribute has been set (common.h)
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_sbf16_kernel<PHASE>), &lds_ok, 160 * 1024)) return rc;
-    const int64_t blocks = (int64_t)a.B * a.tiles_y * a.tiles_x * a.m_tiles;
-    hipLaunchKernelGGL(modconv_sbf16_kernel<PHASE>, dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    MAUA_LAUNCH_CHECK();
-    return 0;
-}
-}  // namespace
-
 // up = 0: the plain convolution (+ tail when fuse_act).  up = 1: the stride-2 transposed convolution, raw map [B, Cout, 2H+1, 2W+1]:
 // four phase launches over the positions p < H, q < W, then the edge lines (output row 2H, column 2W) by modconv_up2d.hip's fp32 edge
 // kernel on the edge tap matrices stored behind the bf16 records; ws = [B, cin, H] floats (the exported last input column).
 int maua_sbf16_launch(const float* x, const void* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
                       int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, void* stream) {
     if (!(up ? maua_sbf16_up_ok(cin, cout, h, w) : maua_sbf16_ok(cin, cout, h, w))) return MAUA_EINVAL;
-    if ((int64_t)cin * h * w * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor range / 32-bit offsets
+    if (!fits_raw_descriptor((int64_t)cin * h * w * 4)) return MAUA_EINVAL;  // one image
     if (up && (fuse_act || !ws)) return MAUA_EINVAL;
     SbArgs a{};
     a.x = x, a.wq = static_cast<const bf16x8*>(wq), a.s = s, a.d = d, a.noise = tail.noise, a.noise_w = tail.noise_w, a.bias = tail.bias, a.y = y;
     a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale, a.fuse_act = fuse_act;
     a.noise_batch_stride = tail.noise_batch_stride, a.src = tail.src, a.noise_slot = tail.noise_slot;
     a.tiles_x = w / SB_TW, a.tiles_y = h / SB_TH, a.m_tiles = cout / SB_BM, a.n_chunks = cin / SB_KC;
-    const size_t lds_bytes = (size_t)2 * SB_BUF_BYTES + sizeof(float) * ((size_t)cin + 2 * SB_BM);
     hipStream_t st = (hipStream_t)stream;
-    if (!up) {
-        snprintf(g_sbf16_instance, sizeof(g_sbf16_instance), "modconv_sbf16_kernel<-1>");
-        return sbf16_launch_phase<-1>(a, lds_bytes, st);
-    }
-    snprintf(g_sbf16_instance, sizeof(g_sbf16_instance), "modconv_sbf16_up_kernel");
-    {
-        static unsigned long long lds_ok = 0;  // per launcher: devices on which the attribute has been set (common.h)
-        if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_sbf16_up_kernel), &lds_ok, 160 * 1024)) return rc;
-        a.m_tiles = cout / 32;
-        const size_t up_lds = (size_t)2 * SU_ABUF_BYTES + (size_t)2 * SU_BBUF_BYTES + sizeof(float) * ((size_t)cin + 32);
-        const int64_t blocks = (int64_t)batch * a.tiles_y * a.tiles_x * a.m_tiles;
-        hipLaunchKernelGGL(modconv_sbf16_up_kernel, dim3((unsigned)blocks), dim3(256), up_lds, st, a);
-        MAUA_LAUNCH_CHECK();
-    }
+    if (up) a.m_tiles = cout / 32;
+    const int64_t blocks = (int64_t)batch * a.tiles_y * a.tiles_x * a.m_tiles;
+    if (!up) return maua_launch_conv<modconv_sbf16_kernel<-1>>("modconv_sbf16_kernel<-1>", blocks, (size_t)2 * SB_BUF_BYTES + sizeof(float) * ((size_t)cin + 2 * SB_BM), st, a);
+    if (int rc = maua_launch_conv<modconv_sbf16_up_kernel>("modconv_sbf16_up_kernel", blocks, (size_t)2 * SU_ABUF_BYTES + (size_t)2 * SU_BBUF_BYTES + sizeof(float) * ((size_t)cin + 32), st, a)) return rc;
     const int64_t rows = (int64_t)batch * cin * h;
-    const int64_t blocks = ceil_div64(rows, 256);
-    hipLaunchKernelGGL(export_last_column_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, x, ws, rows, w);
+    hipLaunchKernelGGL(export_last_column_kernel, dim3(pack_grid(rows)), dim3(256), 0, st, x, ws, rows, w);
     MAUA_LAUNCH_CHECK();
     const float* edge = reinterpret_cast<const float*>(static_cast<const unsigned char*>(wq) + (size_t)cout * cin * 9 * 2 * 2);
     return maua_up2d_edge_launch(x, edge, s, s_stride, d, y, ws, batch, cin, cout, h, w, wscale, stream);
@@ -578,13 +519,10 @@ extern "C" int64_t maua_pack_weight_sbf16_bytes(int cout, int cin) {
 extern "C" int maua_pack_weight_sbf16_f32(const float* w, void* wq, int cout, int cin, void* stream) {
     if (!w || !wq || !maua_sbf16_up_ok(cin, cout, SB_TH, SB_TW)) return MAUA_EINVAL;
     const int64_t total = (int64_t)(cout / 32) * (cin / SB_KC) * 9 * 64 * 4;
-    const int64_t blocks = ceil_div64(total, 256);
-    hipLaunchKernelGGL(pack_weight_sbf16_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, w,
-                       static_cast<unsigned*>(wq), cout, cin);
+    hipLaunchKernelGGL(pack_weight_sbf16_kernel, dim3(pack_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, w, static_cast<unsigned*>(wq), cout, cin);
     MAUA_LAUNCH_CHECK();
     float* edge = reinterpret_cast<float*>(static_cast<unsigned char*>(wq) + (size_t)cout * cin * 9 * 2 * 2);
-    const int64_t eb = ceil_div64((int64_t)cout * cin, 256);
-    hipLaunchKernelGGL(pack_edge_taps_kernel, dim3((unsigned)(eb < 4096 ? eb : 4096)), dim3(256), 0, (hipStream_t)stream, w, edge, cout, cin);
+    hipLaunchKernelGGL(pack_edge_taps_kernel, dim3(pack_grid((int64_t)cout * cin)), dim3(256), 0, (hipStream_t)stream, w, edge, cout, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }

@@ -32,7 +32,7 @@
 // over).  The remaining output row 2H and column 2W belong to positions whose own input is the zero padding: two 1-D polyphase
 // transposed convolutions of the last input row / column with the kernel's last row / column, 1.5 MAC per output
 // (up2d_edge_kernel: direct MFMA, ~1/H of the layer's work).
-#include "common.h"
+#include "conv_device.h"
 
 #include <algorithm>
 #include <array>
@@ -42,19 +42,8 @@
 #include <mutex>
 #include <queue>
 #include <vector>
-#include <type_traits>
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MAUA_DEVICE_PASS 1
-#endif
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4u __attribute__((aligned(4)));
-typedef f32x2 f32x2u __attribute__((aligned(4)));
 
 constexpr int U2_NU = 16;                                 // transformed-kernel entries per (cout, cin)
 constexpr int U2_BM = 32;                                 // output channels per workgroup (two 16-row m-tiles, interleaved)
@@ -73,30 +62,13 @@ __host__ __device__ constexpr int u2_a_floats(int cc) { return U2_NU * cc * U2_B
 __host__ __device__ constexpr int u2_p_instr(int cc) { return (cc * (U2_PLANE / 4) + 63) / 64; }  // patch: whole DMA instructions
 __host__ __device__ constexpr int u2_pbuf(int cc) { return u2_p_instr(cc) * 256; }         // >= cc x 352 floats
 
-// single `ds_read_b64` / `ds_read_b32` through inline assembly with explicit lgkmcnt waits: see modconv_w2d.hip (left alone the
-// compiler pairs 8-byte reads into ds_read2_b64, which is serviced at half the bytes per clock on a 32-bank modulus)
-template <int OFF>
-__device__ __forceinline__ f32x2 lds_read64(unsigned addr) {
-    f32x2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
+// Dynamic LDS of modconv_up2d_kernel<CC, FUSE>, THE byte count of every launcher: As[2][A_FLOATS] | Ps[2][PBUF] | Ss[Cin] | Eg[3][32] |
+// (FUSE == 2) SV[4][3][64][8].  The kernel spells the same offsets out itself: taking them from a shared function changed the listing of
+// its raw-output instances.
+constexpr size_t u2_lds_bytes(int cc, int fuse, int cin) {
+    return sizeof(float) * ((size_t)2 * u2_a_floats(cc) + (size_t)2 * u2_pbuf(cc) + (size_t)((cin + 3) & ~3) + 3 * U2_BM + (fuse == 2 ? 4 * 3 * 64 * 8 : 0));
 }
-__device__ __forceinline__ float lds_read32(unsigned addr) {
-    float v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(f32x2& a) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N));
-}
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
+static_assert((size_t)2 * u2_a_floats(8) + (size_t)2 * u2_pbuf(8) >= 2 * 4 * 3 * 64 * 8, "the exchange region lives in the operand buffers");
 
 struct Up2dArgs {
     const float* x;
@@ -179,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void modconv_up2d_kernel(Up2dArgs p) {
     constexpr int A_PER_WAVE = 2 * CC / 4;                 // weight DMA instructions per wave and K step
     constexpr int P_PER_WAVE = (U2_P_INSTR + 3) / 4;       // patch DMA instructions per wave and K step (the last ones may be idle)
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // LDS: As[2][A_FLOATS] | Ps[2][PBUF] | Ss[Cin] | Eg[32] | (FUSE == 2) SV[4][3][64][8]: the h-rows the next tile of the segment needs
+    // LDS (u2_lds_bytes): As[2][A_FLOATS] | Ps[2][PBUF] | Ss[Cin] | Eg[3][32] | (FUSE == 2) SV[4][3][64][8]: the h-rows the next tile of the segment needs
     float* Ps = lds + 2 * U2_A_FLOATS;
     float* Ss = Ps + 2 * U2_PBUF;
 
@@ -218,15 +190,11 @@ __global__ __launch_bounds__(256, 2) void modconv_up2d_kernel(Up2dArgs p) {
     const char* ximg = reinterpret_cast<const char*>(p.x + (size_t)b0 * p.Cin * plane);
     const size_t plane_bytes = plane * sizeof(float);
     unsigned rel_bytes[P_PER_WAVE];
-    (void)ximg, (void)plane_bytes, (void)rel_bytes;
-#ifdef MAUA_DEVICE_PASS
     // (FUSE == 2: the exact size of the image — a segment that straddles its last element must not touch memory behind it; the range check is per dword
     // and includes the scalar offset: tools/dma_range_probe.hip)
-    const __amdgpu_buffer_rsrc_t x_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ximg), 0, FUSE == 2 ? (int)((size_t)p.Cin * plane_bytes) : 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wq), 0, 0x7fffffff, 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(ximg, FUSE == 2 ? (int)((size_t)p.Cin * plane_bytes) : 0x7fffffff), w_rsrc = raw_buffer(p.wq);
     auto issue = [&](int chunk, int buf) {
+        // (the builtin itself, not conv_device.h's lds_dma16: through the wrapper the raw-output instances' prologues come out in another order)
 #ifdef MAUA_DEVICE_PASS
         const int wbase = (int)(((size_t)mt_id * p.n_chunks + chunk) * U2_A_FLOATS * sizeof(float));
 #pragma unroll
@@ -308,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void modconv_up2d_kernel(Up2dArgs p) {
         const int pr = rem / U2_PSEGS, sg = rem % U2_PSEGS;
         const int yy = ty0 - 1 + pr, xx = tx0 - 4 + 4 * sg;
         const bool ok = c < CC && rem < U2_PROWS * U2_PSEGS && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        rel_bytes[g] = ok ? ((unsigned)c * (unsigned)plane + (unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : 0x80000000u;  // (< 2^31: checked by the launcher)
+        rel_bytes[g] = ok ? ((unsigned)c * (unsigned)plane + (unsigned)yy * (unsigned)p.W + (unsigned)xx) * 4u : kOutOfRange;  // (< 2^31: checked by the launcher)
     }
 
     // ---- accumulators (one 16 x 16 tile = 4 registers each; [.][m-tile]): 25 products x 2 m-tiles = 200 registers
@@ -822,7 +790,30 @@ __global__ __launch_bounds__(256) void pack_weight_up2d_kernel(const float* __re
     }
 }
 
-char g_up2d_instance[64] = "";
+// The part of Up2dArgs that every launcher fills the same way, for tiles of tw x rows positions and cc channels per K step.  Split-K, the
+// fused tail and the seam buffers are the caller's own.
+Up2dArgs up2d_args(const float* x, const float* wq, const float* s, int s_stride, const float* d, int batch, int cin, int cout, int h, int w,
+                   float wscale, int tw, int rows, int cc) {
+    Up2dArgs a{};
+    a.x = x, a.wq = wq, a.s = s, a.d = d;
+    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
+    a.tiles_x = w / tw, a.tiles_y = h / rows, a.m_tiles = cout / U2_BM, a.n_chunks = cin / cc;
+    return a;
+}
+
+// edge lines: W + 1 positions along the bottom row (incl. the corner), H along the right column
+int up2d_launch_edges(const Up2dArgs& a, const float* taps, hipStream_t st) {
+    const int nt0 = ceil_div(a.W + 1, 16), nt1 = ceil_div(a.H, 16);
+    const int64_t eblocks = (int64_t)a.B * (a.Cout / 16) * (nt0 + nt1);
+    hipLaunchKernelGGL(up2d_edge_kernel, dim3((unsigned)eblocks), dim3(256), 0, st, a, taps, nt0, nt1);
+    MAUA_LAUNCH_CHECK();
+    return 0;
+}
+
+// the operands behind raw buffer descriptors: one image, the packed weight
+bool up2d_fits_descriptors(int cin, int cout, int h, int w) {
+    return fits_raw_descriptor((int64_t)cin * h * w * 4) && fits_raw_descriptor((int64_t)U2_NU * cin * cout * 4);
+}
 
 }  // namespace
 
@@ -835,28 +826,19 @@ extern "C" int64_t maua_pack_weight_up2d_floats(int cout, int cin) { return (int
 
 extern "C" int maua_pack_weight_up2d_f32(const float* w, float* wq, int cout, int cin, void* stream) {
     if (!w || !wq || cout <= 0 || cin <= 0 || cin % 4 || cout % U2_BM) return MAUA_EINVAL;
-    const int64_t blocks = ceil_div64((int64_t)cout * cin, 256);
-    hipLaunchKernelGGL(pack_weight_up2d_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, w, wq,
-                       cout, cin);
+    hipLaunchKernelGGL(pack_weight_up2d_kernel, dim3(pack_grid((int64_t)cout * cin)), dim3(256), 0, (hipStream_t)stream, w, wq, cout, cin);
     MAUA_LAUNCH_CHECK();
     return 0;
 }
-
-const char* maua_up2d_last_instance() { return g_up2d_instance; }
 
 // The edge lines alone (output row 2H, column 2W of the transposed convolution) from the five fp32 edge tap matrices [5][cin][cout] and the
 // exported last input column xcol [B, cin, H]: used by the split-bf16 side path (modconv_sbf16.hip), whose phase kernels cover p < H, q < W.
 int maua_up2d_edge_launch(const float* x, const float* edge_taps, const float* s, int s_stride, const float* d, float* y, const float* xcol,
                           int batch, int cin, int cout, int h, int w, float wscale, void* stream) {
     if (!x || !edge_taps || !y || !xcol || cout % 16) return MAUA_EINVAL;
-    Up2dArgs a{};
-    a.x = x, a.wq = nullptr, a.s = s, a.d = d, a.y = y, a.xcol = const_cast<float*>(xcol);
-    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
-    const int nt0 = ceil_div(w + 1, 16), nt1 = ceil_div(h, 16);
-    const int64_t eblocks = (int64_t)batch * (cout / 16) * (nt0 + nt1);
-    hipLaunchKernelGGL(up2d_edge_kernel, dim3((unsigned)eblocks), dim3(256), 0, (hipStream_t)stream, a, edge_taps, nt0, nt1);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    Up2dArgs a = up2d_args(x, nullptr, s, s_stride, d, batch, cin, cout, h, w, wscale, 32, 8, u2_cc(cin));
+    a.y = y, a.xcol = const_cast<float*>(xcol);
+    return up2d_launch_edges(a, edge_taps, (hipStream_t)stream);
 }
 
 // ---- the whole up-sampling StyledConv in one pass over the accumulators (FUSE == 2) -------------------------------------------------------
@@ -965,25 +947,17 @@ extern "C" int maua_upconv_blur_f32(const float* x, const float* wq, const float
     if (!x || !wq || !y || !k4 || batch <= 0) return MAUA_EINVAL;
     if (!maua_upconv_blur_ok(cin, cout, h, w)) return MAUA_ENOSYS;
     if (int rc = TailArgs{noise, noise_w, bias, noise_batch_stride, src, noise_slot}.check()) return rc;
-    if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)U2_NU * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
+    if (!up2d_fits_descriptors(cin, cout, h, w)) return MAUA_EINVAL;
     const FusePlan f = fuse_plan(batch, cout, h, w);
     if (f.n_seg > 1 && !ws) return MAUA_EINVAL;
     constexpr int cc = 8;
-    Up2dArgs a{};
-    a.x = x, a.wq = wq, a.s = s, a.d = d, a.y = nullptr, a.xcol = nullptr;
-    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
-    a.tiles_x = f.tiles_x, a.tiles_y = f.n_seg, a.m_tiles = cout / U2_BM, a.n_chunks = cin / cc;
-    a.seg_tiles = f.seg_tiles, a.tiles_total_y = f.tiles_total_y;
+    Up2dArgs a = up2d_args(x, wq, s, s_stride, d, batch, cin, cout, h, w, wscale, 32, 8, cc);
+    a.tiles_x = f.tiles_x, a.tiles_y = f.n_seg, a.seg_tiles = f.seg_tiles, a.tiles_total_y = f.tiles_total_y;  // (60-column tiles in segments)
     a.yb = y, a.hbuf = ws, a.k4 = k4, a.noise = noise, a.noise_w = noise_w, a.bias = bias, a.noise_batch_stride = noise_batch_stride;
     a.src = src, a.noise_slot = noise_slot, a.post_s = post_s;
-    const size_t lds_bytes = sizeof(float) * ((size_t)2 * u2_a_floats(cc) + (size_t)2 * u2_pbuf(cc) + (size_t)((cin + 3) & ~3) + 3 * U2_BM + 4 * 3 * 64 * 8);
-    static_assert((size_t)2 * u2_a_floats(8) + (size_t)2 * u2_pbuf(8) >= 2 * 4 * 3 * 64 * 8, "the exchange region lives in the operand buffers");
+    const size_t lds_bytes = u2_lds_bytes(cc, 2, cin);
     if (lds_bytes > 80 * 1024) return MAUA_ENOSYS;  // two workgroups per CU
     const int64_t blocks = (int64_t)batch * f.n_seg * f.tiles_x * a.m_tiles;
-    static unsigned long long lds_ok = 0, lds_ok_pre = 0;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 2, false>), &lds_ok, 160 * 1024)) return rc;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 2, true>), &lds_ok_pre, 160 * 1024)) return rc;
-    snprintf(g_up2d_instance, sizeof(g_up2d_instance), s ? "modconv_up2d_kernel<8, 2, false, 32>" : "modconv_up2d_kernel<8, 2, true, 32>");
     hipStream_t st = (hipStream_t)stream;
 #ifdef MAUA_EXPERIMENTS
     if (getenv("MAUA_FUSE_DEBUG")) {
@@ -993,9 +967,9 @@ extern "C" int maua_upconv_blur_f32(const float* x, const float* wq, const float
                 cin, cout, h, w, batch, f.tiles_x, f.tiles_total_y, f.n_seg, f.seg_tiles, (long long)blocks, lds_bytes, occ);
     }
 #endif
-    if (s) hipLaunchKernelGGL((modconv_up2d_kernel<8, 2, false>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    else hipLaunchKernelGGL((modconv_up2d_kernel<8, 2, true>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    MAUA_LAUNCH_CHECK();
+    if (int rc = s ? maua_launch_conv<modconv_up2d_kernel<8, 2, false>>("modconv_up2d_kernel<8, 2, false, 32>", blocks, lds_bytes, st, a)
+                   : maua_launch_conv<modconv_up2d_kernel<8, 2, true>>("modconv_up2d_kernel<8, 2, true, 32>", blocks, lds_bytes, st, a))
+        return rc;
     if (f.n_seg > 1) {
         const int64_t threads = (int64_t)batch * cout * (f.n_seg - 1) * (2 * w / 4);
         hipLaunchKernelGGL(up2d_seam_kernel, dim3((unsigned)ceil_div64(threads, 256)), dim3(256), 0, st, a, f.n_seg - 1);
@@ -1014,21 +988,14 @@ extern "C" int maua_exp_upconv_blur_fused_f32(const float* x, const float* wq, c
     if (!maua_modconv_up2d_ok(cin, cout, h, w) || !yb || !k4) return MAUA_EINVAL;
     const int cc = u2_cc(cin);
     if (cc != 8) return MAUA_ENOSYS;
-    Up2dArgs a{};
-    a.x = x, a.wq = wq, a.s = s, a.d = d, a.y = nullptr, a.xcol = nullptr;
-    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
-    a.tiles_x = w / 32, a.tiles_y = h / 8, a.m_tiles = cout / U2_BM, a.n_chunks = cin / cc;
+    Up2dArgs a = up2d_args(x, wq, s, s_stride, d, batch, cin, cout, h, w, wscale, 32, 8, cc);
     a.yb = yb, a.k4 = k4, a.noise = noise, a.noise_w = noise_w, a.bias = bias, a.noise_batch_stride = noise_batch_stride;
-    const size_t k_loop = sizeof(float) * ((size_t)2 * u2_a_floats(cc) + (size_t)2 * u2_pbuf(cc) + (size_t)((cin + 3) & ~3) + 3 * U2_BM);
+    const size_t k_loop = u2_lds_bytes(cc, 1, cin);
     const size_t lds_bytes = k_loop > 49152 + 4096 ? k_loop : 49152 + 4096;
     const int64_t blocks = (int64_t)batch * a.tiles_y * a.tiles_x * a.m_tiles;
     a.real_blocks = (int)blocks;
     const int64_t launched = blocks + blocks * extra_pct / 100;
-    static unsigned long long lds_ok = 0;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 1>), &lds_ok, 160 * 1024)) return rc;
-    hipLaunchKernelGGL((modconv_up2d_kernel<8, 1>), dim3((unsigned)launched), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    return maua_launch_conv<modconv_up2d_kernel<8, 1>>("modconv_up2d_kernel<8, 1, false, 32>", launched, lds_bytes, (hipStream_t)stream, a);
 }
 #endif
 
@@ -1051,62 +1018,41 @@ int maua_up2d16_splits(int batch, int cin, int cout, int h, int w) {
 int maua_up2d16_launch(const float* x, const float* wq, const float* s, int s_stride, float* y, float* xcol, int batch, int cin, int cout, int h,
                        int w, float wscale, int* splits_out, void* stream) {
     if (!maua_up2d16_ok(cin, cout, h, w) || !x || !wq || !s || !y || !xcol || !splits_out) return MAUA_EINVAL;
-    if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)U2_NU * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
+    if (!up2d_fits_descriptors(cin, cout, h, w)) return MAUA_EINVAL;
     if ((int64_t)U2_BM * (2 * h + 1) * (2 * w + 1) * 4 > 0xffffffffLL) return MAUA_EINVAL;                              // 32-bit store offsets
     constexpr int cc = 8;
-    Up2dArgs a{};
-    a.x = x, a.wq = wq, a.s = s, a.d = nullptr, a.y = y, a.xcol = xcol;
-    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
-    a.tiles_x = w / 16, a.tiles_y = h / 16, a.m_tiles = cout / U2_BM, a.n_chunks = cin / cc;
+    Up2dArgs a = up2d_args(x, wq, s, s_stride, nullptr, batch, cin, cout, h, w, wscale, 16, 16, cc);
+    a.y = y, a.xcol = xcol;
     a.splits = maua_up2d16_splits(batch, cin, cout, h, w);
     a.chunks_per_split = (a.n_chunks + a.splits - 1) / a.splits;
     a.splits = (a.n_chunks + a.chunks_per_split - 1) / a.chunks_per_split;
     a.slab = (int64_t)batch * cout * (2 * h + 1) * (2 * w + 1);
     *splits_out = a.splits;
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds_bytes = sizeof(float) * ((size_t)2 * u2_a_floats(cc) + (size_t)2 * u2_pbuf(cc) + (size_t)((cin + 3) & ~3) + 3 * U2_BM);
     const int64_t blocks = (int64_t)batch * a.tiles_y * a.tiles_x * a.m_tiles * a.splits;
-    static unsigned long long lds_ok = 0;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 0, false, 16>), &lds_ok, 160 * 1024)) return rc;
-    snprintf(g_up2d_instance, sizeof(g_up2d_instance), "modconv_up2d_kernel<8, 0, false, 16>");
-    hipLaunchKernelGGL((modconv_up2d_kernel<8, 0, false, 16>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    MAUA_LAUNCH_CHECK();
-    const int nt0 = ceil_div(w + 1, 16), nt1 = ceil_div(h, 16);
-    const int64_t eblocks = (int64_t)batch * (cout / 16) * (nt0 + nt1);
-    hipLaunchKernelGGL(up2d_edge_kernel, dim3((unsigned)eblocks), dim3(256), 0, st, a, wq + (size_t)U2_NU * cin * cout, nt0, nt1);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    if (int rc = maua_launch_conv<modconv_up2d_kernel<8, 0, false, 16>>("modconv_up2d_kernel<8, 0, false, 16>", blocks, u2_lds_bytes(cc, 0, cin), st, a))
+        return rc;
+    return up2d_launch_edges(a, wq + (size_t)U2_NU * cin * cout, st);
 }
 
 int maua_up2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, float* ws, int batch, int cin,
                      int cout, int h, int w, float wscale, void* stream) {
     if (!maua_modconv_up2d_ok(cin, cout, h, w) || !ws) return MAUA_EINVAL;
-    if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)U2_NU * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
+    if (!up2d_fits_descriptors(cin, cout, h, w)) return MAUA_EINVAL;
     if ((int64_t)U2_BM * (2 * h + 1) * (2 * w + 1) * 4 > 0xffffffffLL) return MAUA_EINVAL;                              // 32-bit store offsets
-    Up2dArgs a{};
-    a.x = x, a.wq = wq, a.s = s, a.d = d, a.y = y, a.xcol = ws;
-    a.B = batch, a.Cin = cin, a.Cout = cout, a.H = h, a.W = w, a.s_stride = s_stride, a.wscale = wscale;
     const int cc = u2_cc(cin);
-    a.tiles_x = w / 32, a.tiles_y = h / 8, a.m_tiles = cout / U2_BM, a.n_chunks = cin / cc;
+    Up2dArgs a = up2d_args(x, wq, s, s_stride, d, batch, cin, cout, h, w, wscale, 32, 8, cc);
+    a.y = y, a.xcol = ws;
     a.splits = 1, a.chunks_per_split = a.n_chunks, a.slab = 0;
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds_bytes = sizeof(float) * ((size_t)2 * u2_a_floats(cc) + (size_t)2 * u2_pbuf(cc) + (size_t)((cin + 3) & ~3) + 3 * U2_BM);
+    const size_t lds_bytes = u2_lds_bytes(cc, 0, cin);
     const int64_t blocks = (int64_t)batch * a.tiles_y * a.tiles_x * a.m_tiles;
-    static unsigned long long lds_ok[4] = {0, 0, 0, 0};  // per instance: devices on which the attribute has been set (common.h)
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<4, 0, false>), &lds_ok[0], 160 * 1024)) return rc;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 0, false>), &lds_ok[1], 160 * 1024)) return rc;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<4, 0, true>), &lds_ok[2], 160 * 1024)) return rc;
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_up2d_kernel<8, 0, true>), &lds_ok[3], 160 * 1024)) return rc;
-    snprintf(g_up2d_instance, sizeof(g_up2d_instance), s ? "modconv_up2d_kernel<%d, 0, false, 32>" : "modconv_up2d_kernel<%d, 0, true, 32>", cc);
-    if (cc == 8 && s) hipLaunchKernelGGL((modconv_up2d_kernel<8, 0, false>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    else if (cc == 8) hipLaunchKernelGGL((modconv_up2d_kernel<8, 0, true>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    else if (s) hipLaunchKernelGGL((modconv_up2d_kernel<4, 0, false>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    else hipLaunchKernelGGL((modconv_up2d_kernel<4, 0, true>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, a);
-    MAUA_LAUNCH_CHECK();
-    // edge lines: W + 1 positions along the bottom row (incl. the corner), H along the right column
-    const int nt0 = ceil_div(w + 1, 16), nt1 = ceil_div(h, 16);
-    const int64_t eblocks = (int64_t)batch * (cout / 16) * (nt0 + nt1);
-    hipLaunchKernelGGL(up2d_edge_kernel, dim3((unsigned)eblocks), dim3(256), 0, st, a, wq + (size_t)U2_NU * cin * cout, nt0, nt1);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    char name[64];
+    snprintf(name, sizeof(name), "modconv_up2d_kernel<%d, 0, %s, 32>", cc, s ? "false" : "true");
+    if (int rc = s ? (cc == 4 ? maua_launch_conv<modconv_up2d_kernel<4, 0, false>>(name, blocks, lds_bytes, st, a)
+                              : maua_launch_conv<modconv_up2d_kernel<8, 0, false>>(name, blocks, lds_bytes, st, a))
+                   : (cc == 4 ? maua_launch_conv<modconv_up2d_kernel<4, 0, true>>(name, blocks, lds_bytes, st, a)
+                              : maua_launch_conv<modconv_up2d_kernel<8, 0, true>>(name, blocks, lds_bytes, st, a)))
+        return rc;
+    return up2d_launch_edges(a, wq + (size_t)U2_NU * cin * cout, st);
 }

@@ -26,15 +26,11 @@
 //     channel offset; no selects (row 1 of A_y^T = row 0 with a sign, leaky ReLU = max(t, slope t)).
 // Operands reach LDS by MUBUF `buffer_load ... lds` DMA, double buffered, one barrier per 4-channel K step; the packed weight
 // (maua_pack_weight_wino2d_f32) is laid out in HBM exactly as the LDS tile image, so its DMA is a linear copy.
+#include "conv_device.h"
 #include "epilogue.h"
 
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MAUA_DEVICE_PASS 1
-#endif
 
 // Compile-time ablation mask, experiment builds only (tools/build_exp.sh <name> -DMAUA_W2D_ABL=<mask>; results are wrong by construction,
 // the timing is an upper bound of what optimising that part could return): 1 no MFMA, 2 no DMA after the first chunk, 4 no feature
@@ -54,10 +50,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // Staged patch: rows of ten 16-byte segments = image columns tx0-4 .. tx0+35 (16-byte aligned in HBM, so that every segment
 // lies wholly inside or wholly outside the image and the zero padding comes from the DMA's out-of-range rule); a position's
 // 6-float window starts at row float 4 jx + 3.  LDS row stride 48 floats = 12 segment slots: two position rows (2 patch rows
@@ -66,59 +58,6 @@ constexpr int W2D_SEGS = 10;
 constexpr int W2D_PWS = 48;
 constexpr int W2D_ROWS_PER_DMA = 5;  // 64 lanes x 16 bytes = 5 1/3 LDS rows: a DMA instruction covers 5 rows (+ 4 slots of the 6th)
 constexpr int W2D_CC = 4;     // input channels per K step = K of v_mfma_f32_16x16x4_f32
-
-// LDS reads of the main loop are issued as single `ds_read_b64` instructions through inline assembly: left to itself the
-// compiler pairs neighbouring 8-byte reads into ds_read2_b64 / ds_read2st64_b64, which are serviced in 16-lane groups on a
-// 32-bank modulus at half the bytes per clock (MI355X_MICROARCH.md, LDS table) — measured 30 % of the LDS-active cycles of this
-// kernel as bank conflicts for a layout that is conflict-free under ds_read_b64's rule (32-lane groups, 64 banks).  The
-// compiler does not count inline-assembly LDS operations, so the waits are explicit as well; a wait "produces" the values it
-// guards (tied operands), which keeps their consumers behind it.
-template <int OFF>
-__device__ __forceinline__ f32x2 lds_read64(unsigned addr) {
-    f32x2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-__device__ __forceinline__ float lds_read32(unsigned addr) {
-    float v;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(f32x2& a) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(f32x2& a, f32x2& b) {
-    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
-}
-// 16-byte MUBUF store whose channel offset is a SCALAR (soffset SGPR), followed by its own wait states.  Round 6 finding, measured on the
-// MI355X (tools/dbg/w2dw_val.py: every thread's value correct in its register, the fourth dword of the stored row not): the compiler
-// treats a buffer store of more than 64 bits as hazard-free when its soffset is a register (LLVM GCNHazardRecognizer::createsVALUHazard:
-// "this hazard only exists if the instruction is not using a register in the soffset field") and lets the very next instructions
-// overwrite the data registers — it had emitted `buffer_store_dwordx4 v[190:193], .., s67 offen` followed at once by four v_mov into
-// v190..v193 for the next row, and on gfx950 the row-0 store then carried the NEXT row's last dword in a quarter of its lanes.  With an
-// immediate soffset it keeps 2 wait states (and those builds were right).  The store therefore goes out as one inline-assembly blob
-// with `s_nop` behind it: no instruction the compiler schedules can reach the data registers earlier than 4 wait states after the issue.
-__device__ __forceinline__ void buffer_store_b128_sgpr_offset(u32x4 data, const float* base, unsigned voffset_bytes, unsigned soffset_bytes) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    // raw buffer descriptor (stride 0, 2^31 - 1 records, DATA_FORMAT = 32 as __builtin_amdgcn_make_buffer_rsrc(.., 0, 0x7fffffff, 0x00020000))
-    i32x4 rsrc = i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32) & 0xffff), 0x7fffffff, 0x00020000};
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 3" ::"v"(data), "v"(voffset_bytes), "s"(rsrc), "s"(soffset_bytes) : "memory");
-#else
-    (void)data, (void)base, (void)voffset_bytes, (void)soffset_bytes;
-#endif
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 struct W2dArgs {
     const float* x;
@@ -171,6 +110,25 @@ __host__ __device__ constexpr int w2d_pstride(int tn) {
 #endif
 constexpr int W2D_ODD_SHIFT = MAUA_W2D_ODD_SHIFT;
 __host__ __device__ constexpr int w2d_pbuf(int tn) { return W2D_CC * w2d_pstride(tn) + 4; }  // (+4: the last plane's shifted overrun)
+
+// THE LDS layout of modconv_w2d_kernel<TM, TN> (offsets in floats; the kernel takes its pointers from it, the launcher its byte count):
+// main loop As[2][A_FLOATS] | Ps[2][PBUF] | Ss[Cin] styles, reused by the epilogue as Z[4 fy][16 ch][NPOS][4] | Rr[CG][2 NPOS][12];
+// the per-channel constants E[BM][8] live behind whichever of the two is larger
+struct W2dLds {
+    int ps, ss, rr, e, floats;
+    constexpr size_t bytes() const { return sizeof(float) * (size_t)floats; }
+};
+__host__ __device__ constexpr W2dLds w2d_lds(int tm, int tn, int cin) {
+    const int bm = 16 * tm, npos = 16 * tn, a_floats = 24 * W2D_CC * bm, cg = 256 / (2 * npos);
+    W2dLds l{};
+    l.ps = 2 * a_floats;
+    l.ss = l.ps + 2 * w2d_pbuf(tn);
+    l.rr = 4 * 16 * npos * 4;
+    const int main_loop = l.ss + cin, epilogue = l.rr + cg * 2 * npos * 12;
+    l.e = main_loop > epilogue ? main_loop : epilogue;
+    l.floats = (l.e + 8 * bm + 3) & ~3;
+    return l;
+}
 
 // physical column of (m-tile mt, row i16) inside a weight row of BM = 16 TM floats: m-tile pairs interleaved so that one
 // 8-byte LDS read feeds two MFMAs; for BM = 64 odd K lanes are rotated by half a row (their 256-byte row stride would put
@@ -226,17 +184,12 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
     constexpr int A_PER_WAVE = A_INSTR / 4;
     constexpr int PBUF = w2d_pbuf(TN);
     static_assert(A_INSTR % 4 == 0, "weight tile must split evenly over the four waves");
-    (void)A_PER_WAVE;
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
-    // per-channel constants of the epilogue live behind whatever is larger, the main loop's buffers or the epilogue's exchange buffers
-    constexpr int EPI_FLOATS = 4 * 16 * NPOS * 4 + (256 / (2 * NPOS)) * 2 * NPOS * 12;
-    const int main_floats = 2 * A_FLOATS + 2 * PBUF + p.Cin;
-    const int e_off = main_floats > EPI_FLOATS ? main_floats : EPI_FLOATS;
+    const W2dLds L = w2d_lds(TM, TN, p.Cin);
     float* lds = lds_all;
     float* As = lds;                      // [2][A_FLOATS]
-    (void)As;
-    float* Ps = lds + 2 * A_FLOATS;       // [2][PBUF]
-    float* Ss = Ps + 2 * PBUF;            // [Cin] styles of this image
+    float* Ps = lds + L.ps;               // [2][PBUF]
+    float* Ss = lds + L.ss;               // [Cin] styles of this image
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -269,27 +222,22 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
         const int pr = W2D_ROWS_PER_DMA * q + lane / 12, sg = lane % 12;
         const int yy = ty0 + pr - 1, xx = tx0 - 4 + 4 * sg;
         const bool ok = sg < W2D_SEGS && pr < PH && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        rel_bytes[g] = ok ? (unsigned)(yy * p.W + xx) * 4u : 0x80000000u;
+        rel_bytes[g] = ok ? (unsigned)(yy * p.W + xx) * 4u : kOutOfRange;
     }
     if constexpr (!PRE)
         for (int e = tid; e < p.Cin; e += 256) Ss[e] = p.s[(size_t)b0 * p.s_stride + e];
     const char* ximg = reinterpret_cast<const char*>(p.x + (size_t)b0 * p.Cin * plane);
     const size_t plane_bytes = plane * sizeof(float);
-    (void)ximg, (void)plane_bytes, (void)Ss;
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ximg), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wq), 0, 0x7fffffff, 0x00020000);
-#endif
+    (void)Ss;
+    const buffer_rsrc_t x_rsrc = raw_buffer(ximg), w_rsrc = raw_buffer(p.wq);
     auto issue = [&](int chunk, int buf) {
-#ifdef MAUA_DEVICE_PASS
         // weight tile: linear copy of A_FLOATS floats, 1 KiB per wave instruction
         const int wbase = (int)(((size_t)mt_id * p.n_chunks + chunk) * A_FLOATS * sizeof(float));
 #pragma unroll
         for (int k = 0; k < A_PER_WAVE; ++k) {
             const int i = fy + 4 * k;
             if (W2D_ABL(128) && (k & 1) && chunk) continue;  // (ablation: half the weight pieces)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(As + buf * A_FLOATS + i * 256),
-                                                     16, (i * 256 + lane * 4) * 4, wbase, 0, 0);
+            lds_dma16(w_rsrc, As + buf * A_FLOATS + i * 256, (i * 256 + lane * 4) * 4, wbase);
         }
 #pragma unroll
         for (int k = 0; k < (4 * NQ + 3) / 4; ++k) {
@@ -297,20 +245,16 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
             if (id < W2D_CC * NQ && !(W2D_ABL(1024) && chunk)) {  // (ablation 1024: no patch DMA after the first chunk)
                 const int c = id / NQ, q = id % NQ;
                 float* dst = Ps + buf * PBUF + c * PSTRIDE + (c & 1) * W2D_ODD_SHIFT + q * (W2D_ROWS_PER_DMA * W2D_PWS);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (__attribute__((address_space(3))) void*)dst, 16,
-                                                         (int)rel_bytes[(NQ % 4 == 0) ? (k % (NQ / 4 > 0 ? NQ / 4 : 1)) : 0],
-                                                         (int)((size_t)(chunk * W2D_CC + c) * plane_bytes), 0, 0);
+                lds_dma16(x_rsrc, dst, (int)rel_bytes[(NQ % 4 == 0) ? (k % (NQ / 4 > 0 ? NQ / 4 : 1)) : 0],
+                          (int)((size_t)(chunk * W2D_CC + c) * plane_bytes));
             }
         }
-#else
-        (void)chunk, (void)buf;
-#endif
     };
 
     // per-output-channel constants of the epilogue, [BM][8] = gain, bias, the three modulated ToRGB weights: fetched here, under the
     // first DMA wait, into LDS that neither the main loop nor the exchange buffers of the epilogue touch (loaded after the main loop
     // their ~1 us round trip was exposed in every workgroup)
-    float* E = lds + e_off;
+    float* E = lds + L.e;
     const bool act = p.fuse_act != 0;
     const float act_gain = act ? kSqrt2 : 1.f;
     const float* noise_base = p.noise;
@@ -588,7 +532,7 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
     // then, 16 output channels (one m-tile) per pass, the four waves' 1x4 partial rows meet in LDS:
     //   output row 0 = Z0 + Z1 + Z2,  row 1 = Z1 - Z2 - Z3     (A_y^T of F(2,3))
     float* Z = lds;                               // [4 fy][16 ch][NPOS][4]
-    float* Rr = lds + 4 * 16 * NPOS * 4;          // [CG][2 * NPOS][12] ToRGB partial sums
+    float* Rr = lds + L.rr;                       // [CG][2 * NPOS][12] ToRGB partial sums
     // combine-phase role of this thread: position cp, output row cr of the 2-row block, channel group cg of every pass
     constexpr int CG = 256 / (2 * NPOS);        // channel groups (4 for TN = 2, 2 for TN = 4)
     static_assert(2 * NPOS >= 64, "the combine phase reads its channel index as a wave-uniform scalar: a wave must not span channel groups");
@@ -610,7 +554,6 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
     const float slope = act ? 0.2f : 1.f;        // leaky ReLU as max(t, slope t); slope 1 = no activation
     const unsigned plane_b = (unsigned)plane * 4u;
     const float* y_base = p.y + ((size_t)b0 * p.Cout + m0) * plane;  // (uniform: the store builds its buffer descriptor from it)
-    (void)y_base;
     const float* zbase = Z + cp * 4;
     const int zo_off = (cr ? 3 : 0) * 16 * NPOS * 4;
 
@@ -679,10 +622,8 @@ __global__ __launch_bounds__(256, MINB) void modconv_w2d_kernel(W2dArgs p) {
                 rgbv[1] = v4 * e[3] + rgbv[1];
                 rgbv[2] = v4 * r2 + rgbv[2];
             }
-#ifdef MAUA_DEVICE_PASS
             if (store_feat)
                 buffer_store_b128_sgpr_offset(__builtin_bit_cast(u32x4, v4 * r2ps.y), y_base, pix_off * 4u, (unsigned)ol * plane_b);
-#endif
         }
     }
     if (!p.rgb || W2D_ABL(256)) return;
@@ -773,6 +714,12 @@ __device__ __forceinline__ void ww_transform(const f32x2 (&a)[4], const f32x2 (&
     bv[1] = b12.x, bv[2] = b12.y, bv[3] = b34.x, bv[4] = b34.y;
 }
 
+// Dynamic LDS of modconv_w2dw_kernel: As[2][A_FLOATS] | Ps[2][PBUF] | Ss[Cin] | E.  (The kernel spells the same offsets out itself: taking
+// them from a shared function moved an instruction of its K loop.)
+constexpr size_t w2dw_lds_bytes(int cin) {
+    return sizeof(float) * ((size_t)2 * WW_A_FLOATS + (size_t)2 * w2d_pbuf(WW_TN) + (size_t)((cin + 3) & ~3) + (size_t)8 * WW_BM);
+}
+
 template <bool PRE = false>
 __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
     constexpr int TN = WW_TN, BM = WW_BM;
@@ -812,33 +759,23 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
         const int pr = W2D_ROWS_PER_DMA * wv + lane / 12, sg = lane % 12;
         const int yy = ty0 + pr - 1, xx = tx0 - 4 + 4 * sg;
         const bool ok = sg < W2D_SEGS && pr < PH && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
-        rel_bytes = ok ? (unsigned)(yy * p.W + xx) * 4u : 0x80000000u;
+        rel_bytes = ok ? (unsigned)(yy * p.W + xx) * 4u : kOutOfRange;
     }
     const char* ximg = reinterpret_cast<const char*>(p.x + (size_t)b0 * p.Cin * plane);
     const size_t plane_bytes = plane * sizeof(float);
-    (void)ximg, (void)plane_bytes, (void)rel_bytes;
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ximg), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wq), 0, 0x7fffffff, 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(ximg), w_rsrc = raw_buffer(p.wq);
     auto issue = [&](int chunk, int buf) {
-#ifdef MAUA_DEVICE_PASS
         const int wbase = (int)(((size_t)mt_id * p.n_chunks + chunk) * A_FLOATS * sizeof(float));
 #pragma unroll
         for (int k = 0; k < A_PER_WAVE; ++k) {
             const int i = wv + 4 * k;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(lds + buf * A_FLOATS + i * 256), 16,
-                                                     (i * 256 + lane * 4) * 4, wbase, 0, 0);
+            lds_dma16(w_rsrc, lds + buf * A_FLOATS + i * 256, (i * 256 + lane * 4) * 4, wbase);
         }
 #pragma unroll
         for (int c = 0; c < W2D_CC; ++c) {
             float* dst = Ps + buf * PBUF + c * PSTRIDE + (c & 1) * W2D_ODD_SHIFT + wv * (W2D_ROWS_PER_DMA * W2D_PWS);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (__attribute__((address_space(3))) void*)dst, 16, (int)rel_bytes,
-                                                     (int)((size_t)(chunk * W2D_CC + c) * plane_bytes), 0, 0);
+            lds_dma16(x_rsrc, dst, (int)rel_bytes, (int)((size_t)(chunk * W2D_CC + c) * plane_bytes));
         }
-#else
-        (void)chunk, (void)buf;
-#endif
     };
 
     // the first chunk's operands are requested BEFORE the per-image tables below are fetched: their global round trip (styles, demod,
@@ -987,9 +924,7 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
     const bool store_feat = p.rgb != 2;
     const unsigned plane_b = (unsigned)plane * 4u;
     const float* y_base = p.y + ((size_t)b0 * p.Cout + m0) * plane;  // (uniform: the store builds its buffer descriptor from it)
-    (void)y_base;
     const unsigned y_voff = pix0 * 4u + (unsigned)(4 * kq) * plane_b;
-    (void)y_voff;
     const float* Elane = E + 12 * (2 * kq);
     // The arithmetic runs on CHANNEL PAIRS (v = 2 vp, 2 vp + 1 of an accumulator tile are neighbouring registers): v_pk_* instructions do
     // two channels per issue slot.  ToRGB partial sums per pair member; the members are added before the butterfly.
@@ -1103,7 +1038,6 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
                         }
                     }
             }
-#ifdef MAUA_DEVICE_PASS
             if (store_feat) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -1115,7 +1049,6 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
                     }
                 }
             }
-#endif
         }
     }
     if constexpr (W2D_ABL(4096)) {
@@ -1158,10 +1091,6 @@ __global__ __launch_bounds__(256, 2) void modconv_w2dw_kernel(W2dArgs p) {
     for (int c = 0; c < 3; ++c) *reinterpret_cast<f32x4*>(rgb_img + (size_t)c * plane + pix_off) = outc[c];
 }
 
-size_t w2dw_lds_bytes(int cin) {
-    return sizeof(float) * ((size_t)2 * WW_A_FLOATS + (size_t)2 * w2d_pbuf(WW_TN) + (size_t)((cin + 3) & ~3) + (size_t)8 * WW_BM);
-}
-
 // wq (the LDS tile image): [m_tile][chunk][fy 4][xf 6][kq 4][BM physical column]
 __global__ __launch_bounds__(256) void pack_weight_wino2d_kernel(const float* __restrict__ w, float* __restrict__ wq, int cout,
                                                                  int cin, int tm) {
@@ -1200,42 +1129,23 @@ __global__ __launch_bounds__(256) void pack_weight_wino2d_kernel(const float* __
     }
 }
 
-size_t w2d_lds_bytes(int tm, int tn, int cin) {
-    const int bm = 16 * tm, npos = 16 * tn;
-    const size_t main_loop = (size_t)2 * 24 * W2D_CC * bm + (size_t)2 * w2d_pbuf(tn) + (size_t)cin;
-    const int cg = 256 / (2 * npos);
-    const size_t epilogue = (size_t)4 * 16 * npos * 4 + (size_t)cg * 2 * npos * 12;
-    return sizeof(float) * (((main_loop > epilogue ? main_loop : epilogue) + (size_t)8 * bm + 3) & ~(size_t)3);  // + the channel-constant table
-}
-
-char g_w2d_instance[64] = "";
-
 template <int TM, int TN, int MINB = 2, bool PRE = false>
 int w2d_launch_t(const W2dArgs& a, hipStream_t st) {
-    auto kern = modconv_w2d_kernel<TM, TN, MINB, PRE>;
-    static unsigned long long lds_ok = 0;  // per launcher: devices on which the attribute has been set (common.h)
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(kern), &lds_ok, 160 * 1024)) return rc;
-    snprintf(g_w2d_instance, sizeof(g_w2d_instance), PRE ? "modconv_w2d_kernel<%d, %d, %d, true>" : "modconv_w2d_kernel<%d, %d, %d, false>", TM, TN, MINB);
-    const int64_t blocks = (int64_t)a.B * a.tiles_y * a.tiles_x * a.m_tiles;
+    char name[64];
+    snprintf(name, sizeof(name), "modconv_w2d_kernel<%d, %d, %d, %s>", TM, TN, MINB, PRE ? "true" : "false");
 #ifdef MAUA_EXPERIMENTS  // occupancy probe (MAUA_W2D_LDS_PAD with an experiments build): extra dynamic LDS so that a CU holds one workgroup instead of two
     static const size_t lds_pad = getenv("MAUA_W2D_LDS_PAD") ? (size_t)atoi(getenv("MAUA_W2D_LDS_PAD")) : 0;
 #else
     constexpr size_t lds_pad = 0;
 #endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), w2d_lds_bytes(TM, TN, a.Cin) + lds_pad, st, a);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    return maua_launch_conv<modconv_w2d_kernel<TM, TN, MINB, PRE>>(name, (int64_t)a.B * a.tiles_y * a.tiles_x * a.m_tiles,
+                                                                   w2d_lds(TM, TN, a.Cin).bytes() + lds_pad, st, a);
 }
 
 template <bool PRE>
 int w2dw_launch(const W2dArgs& a, hipStream_t st) {
-    static unsigned long long lds_ok = 0;  // per launcher: devices on which the attribute has been set (common.h)
-    if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(modconv_w2dw_kernel<PRE>), &lds_ok, 160 * 1024)) return rc;
-    snprintf(g_w2d_instance, sizeof(g_w2d_instance), PRE ? "modconv_w2dw_kernel<true>" : "modconv_w2dw_kernel<false>");
-    const int64_t blocks = (int64_t)a.B * a.tiles_y * a.tiles_x * a.m_tiles;
-    hipLaunchKernelGGL(modconv_w2dw_kernel<PRE>, dim3((unsigned)blocks), dim3(256), w2dw_lds_bytes(a.Cin), st, a);
-    MAUA_LAUNCH_CHECK();
-    return 0;
+    return maua_launch_conv<modconv_w2dw_kernel<PRE>>(PRE ? "modconv_w2dw_kernel<true>" : "modconv_w2dw_kernel<false>",
+                                                      (int64_t)a.B * a.tiles_y * a.tiles_x * a.m_tiles, w2dw_lds_bytes(a.Cin), st, a);
 }
 
 }  // namespace
@@ -1258,14 +1168,12 @@ int maua_w2d_tiles(int cin, int cout, int h, int w, int* tm, int* tn) {
     return 1;
 }
 
-const char* maua_w2d_last_instance() { return g_w2d_instance; }
-
 int maua_w2d_launch(const float* x, const float* wq, const float* s, int s_stride, const float* d, float* y, int batch, int cin,
                     int cout, int h, int w, float wscale, int fuse_act, const TailArgs& tail, const RgbArgs* rgb, const float* post_s,
                     void* stream) {
     int tm = 0, tn = 0;
     if (!maua_w2d_tiles(cin, cout, h, w, &tm, &tn)) return MAUA_EINVAL;
-    if ((int64_t)cin * h * w * 4 > 0x7fffffffLL || (int64_t)24 * cin * cout * 4 > 0x7fffffffLL) return MAUA_EINVAL;  // descriptor ranges
+    if (!fits_raw_descriptor((int64_t)cin * h * w * 4) || !fits_raw_descriptor((int64_t)24 * cin * cout * 4)) return MAUA_EINVAL;  // one image, the packed weight
     W2dArgs a{};
     a.x = x, a.wq = wq, a.s = s, a.d = d, a.y = y, a.post_s = post_s;
     a.noise = tail.noise, a.noise_w = tail.noise_w, a.bias = tail.bias, a.noise_batch_stride = tail.noise_batch_stride;
@@ -1296,10 +1204,7 @@ extern "C" int maua_pack_weight_wino2d_f32(const float* w, float* wq, int cout, 
     if (!w || !wq || cout <= 0 || cin <= 0) return MAUA_EINVAL;
     int tm = 0, tn = 0;
     if (!maua_w2d_tiles(cin, cout, 32, 32, &tm, &tn)) return MAUA_EINVAL;
-    const int64_t total = (int64_t)cout * cin;
-    const int64_t blocks = ceil_div64(total, 256);
-    hipLaunchKernelGGL(pack_weight_wino2d_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
-                       w, wq, cout, cin, tm);
+    hipLaunchKernelGGL(pack_weight_wino2d_kernel, dim3(pack_grid((int64_t)cout * cin)), dim3(256), 0, (hipStream_t)stream, w, wq, cout, cin, tm);
     MAUA_LAUNCH_CHECK();
     return 0;
 }

@@ -191,13 +191,11 @@ extern "C" int maua_frames_to_u8(const float* img, uint8_t* out, int batch, int 
     hipStream_t st = (hipStream_t)stream;
     if (plane % 4 == 0 && (((uintptr_t)img) & 15) == 0 && (((uintptr_t)out) & 3) == 0) {
         const int64_t total = (int64_t)batch * plane / 4;
-        const int64_t blocks = ceil_div64(total, 256);
-        hipLaunchKernelGGL(frames_to_u8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, img,
+        hipLaunchKernelGGL(frames_to_u8_kernel, dim3(pack_grid(total)), dim3(256), 0, st, img,
                            out, plane / 4, plane, total);
     } else {
         const int64_t total = (int64_t)batch * plane * 3;
-        const int64_t blocks = ceil_div64(total, 256);
-        hipLaunchKernelGGL(frames_to_u8_scalar_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st,
+        hipLaunchKernelGGL(frames_to_u8_scalar_kernel, dim3(pack_grid(total)), dim3(256), 0, st,
                            img, out, plane, total);
     }
     MAUA_LAUNCH_CHECK();

@@ -729,8 +729,7 @@ extern "C" int maua_istft_f32(const float* in_re, const float* in_im, const floa
     hipLaunchKernelGGL(istft_frames_kernel, dim3(n_frames), dim3(256), (size_t)3 * n_fft * sizeof(float), st, in_re, in_im, window,
                        n_fft, log2n, n_frames, frames_ws);
     MAUA_LAUNCH_CHECK();
-    const int64_t blocks = ceil_div64(n_samples, 256);
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, frames_ws, window, n_fft,
+    hipLaunchKernelGGL(istft_ola_kernel, dim3(pack_grid(n_samples)), dim3(256), 0, st, frames_ws, window, n_fft,
                        hop, n_frames, y, n_samples);
     MAUA_LAUNCH_CHECK();
     return 0;
@@ -756,8 +755,7 @@ extern "C" int maua_median_filter_f32(const float* x, float* y, int rows, int co
 extern "C" int maua_softmask_apply_f32(const float* re, const float* im, const float* x, const float* x_ref, float margin,
                                        float power, int split_zeros, float* out_re, float* out_im, int64_t n, void* stream) {
     if (!re || !im || !x || !x_ref || !out_re || !out_im || n <= 0) return MAUA_EINVAL;
-    const int64_t blocks = ceil_div64(n, 256);
-    hipLaunchKernelGGL(softmask_apply_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, re,
+    hipLaunchKernelGGL(softmask_apply_kernel, dim3(pack_grid(n)), dim3(256), 0, (hipStream_t)stream, re,
                        im, x, x_ref, margin, power, split_zeros, out_re, out_im, n);
     MAUA_LAUNCH_CHECK();
     return 0;

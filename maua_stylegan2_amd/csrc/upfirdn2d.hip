@@ -19,7 +19,7 @@
 //  * fir_up2_kernel (up = 2, down = 1, taps <= 4 x 4: the Upsample module as a standalone op): polyphase, store-bound; see the kernel.
 //  * fir_down2_kernel (up = 1, down = 2, taps <= 4 x 4: the Downsample module / the backward of Upsample; off the inference path): load-bound.
 //  * fir_generic_kernel: any up/down/pad/minor, one thread per output, polyphase tap skipping.
-#include "common.h"
+#include "conv_device.h"
 
 #include <hip/hip_fp16.h>
 
@@ -60,10 +60,6 @@ constexpr int FIR_TAIL_SMALL_MAX_H = 512;
 constexpr int FIR_DOWN2_ROWS = MAUA_FIR_DOWN2_ROWS;  // output rows per wave strip of fir_down2_kernel
 constexpr int FIR_UP2_ROWS = MAUA_FIR_UP2_ROWS;  // output rows per wave strip of fir_up2_kernel ([8,32,512,512] -> 1024^2: 16 rows 0.239 ms, 32 0.267, 64 0.257)
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MAUA_DEVICE_PASS 1
-#endif
-constexpr unsigned FIR_OOB = 0x80000000u;  // a voffset beyond every descriptor range: loads return 0, stores are dropped
 
 // up = down = 1 FIR of one (WY*32) x (WX*64) output tile per 256-thread workgroup (the Blur after an up-convolution and its fused
 // tail).  Round 4 form: every global access is a raw BUFFER instruction whose row offset is a SCALAR (soffset) and whose column
@@ -123,15 +119,11 @@ __global__ __launch_bounds__(256) void fir_tile_kernel(const float* __restrict__
     const int tx = (wave % WX) * 64 + lane;
     const int ty = wave / WX;  // (scalar)
     const int ixm = ix0 + tx;
-    const unsigned in_voff = (ixm >= 0 && ixm < in_w) ? (unsigned)ixm * 4u : FIR_OOB;
+    const unsigned in_voff = (ixm >= 0 && ixm < in_w) ? (unsigned)ixm * 4u : kOutOfRange;
     const unsigned in_row_bytes = (unsigned)in_w * 4u, out_row_bytes = (unsigned)out_w * 4u;
-#ifdef MAUA_DEVICE_PASS
     // one descriptor per plane: offsets stay below 2^31 (checked by the launcher), anything past the plane's end is out of range
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(x) + (size_t)plane * in_h * in_w, 0, (int)((unsigned)in_h * in_row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t y_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(y + (size_t)plane * out_h * out_w, 0, (int)((unsigned)out_h * out_row_bytes), 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(x + (size_t)plane * in_h * in_w, (int)((unsigned)in_h * in_row_bytes));
+    const buffer_rsrc_t y_rsrc = raw_buffer(y + (size_t)plane * out_h * out_w, (int)((unsigned)out_h * out_row_bytes));
     float v[NR], vh[NH];
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
@@ -154,7 +146,7 @@ __global__ __launch_bounds__(256) void fir_tile_kernel(const float* __restrict__
         vh[h] = 0.f;
 #ifdef MAUA_DEVICE_PASS
         vh[h] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                              x_rsrc, ok ? ((unsigned)iy * (unsigned)in_w + (unsigned)ix) * 4u : FIR_OOB, 0, 0));
+                                              x_rsrc, ok ? ((unsigned)iy * (unsigned)in_w + (unsigned)ix) * 4u : kOutOfRange, 0, 0));
 #endif
     }
     // compute map: wave (wx, wy), lane = column
@@ -162,7 +154,7 @@ __global__ __launch_bounds__(256) void fir_tile_kernel(const float* __restrict__
     const int col = wx * 64 + lane;
     const int ox = ox0 + col;
     const int row0 = wy * TH;
-    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : FIR_OOB;
+    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : kOutOfRange;
 
     // tail operands: this lane's 32 noise values are fetched now, in flight together with the input tile
     float g = 1.f, nw = 0.f, bs = 0.f, post = 1.f;
@@ -182,8 +174,7 @@ __global__ __launch_bounds__(256) void fir_tile_kernel(const float* __restrict__
         if (noise) {
             nw = tail.noise_w[0] * kSqrt2;
 #ifdef MAUA_DEVICE_PASS
-            const __amdgpu_buffer_rsrc_t n_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>(noise) + (size_t)b * nstride, 0, (int)((unsigned)out_h * out_row_bytes), 0x00020000);
+            const buffer_rsrc_t n_rsrc = raw_buffer(noise + (size_t)b * nstride, (int)((unsigned)out_h * out_row_bytes));
 #pragma unroll
             for (int o = 0; o < TH; ++o) {
                 const int oy = oy0 + row0 + o;  // (scalar)
@@ -284,19 +275,15 @@ __global__ __launch_bounds__(256) void fir_up2_kernel(const float* __restrict__ 
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) ka[i][tt] = tap(i, jx + 2 * tt), kb[i][tt] = tap(i, 1 - jx + 2 * tt);
     const unsigned in_row_bytes = (unsigned)in_w * 4u, out_row_bytes = (unsigned)out_w * 4u;
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(x) + (size_t)plane * in_h * in_w, 0, (int)((unsigned)in_h * in_row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t y_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(y + (size_t)plane * out_h * out_w, 0, (int)((unsigned)out_h * out_row_bytes), 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(x + (size_t)plane * in_h * in_w, (int)((unsigned)in_h * in_row_bytes));
+    const buffer_rsrc_t y_rsrc = raw_buffer(y + (size_t)plane * out_h * out_w, (int)((unsigned)out_h * out_row_bytes));
     // staging: wave w takes rows w, w + 4, ...; a row is WX dense 64-float segments + 2 more columns (lanes 0, 1 of one more load)
     constexpr int NR = (RH + 3) / 4;
     unsigned voff[WX + 1];
 #pragma unroll
     for (int sgm = 0; sgm <= WX; ++sgm) {
         const int ix = ix0 + sgm * 64 + lane;
-        voff[sgm] = (ix >= 0 && ix < in_w && (sgm < WX || lane < 2)) ? (unsigned)ix * 4u : FIR_OOB;
+        voff[sgm] = (ix >= 0 && ix < in_w && (sgm < WX || lane < 2)) ? (unsigned)ix * 4u : kOutOfRange;
     }
     float v[NR][WX + 1];
 #pragma unroll
@@ -328,7 +315,7 @@ __global__ __launch_bounds__(256) void fir_up2_kernel(const float* __restrict__ 
     const int strip_lo = oy0 + wy * TH;
     const int ox = ox0 + wx * 128 + 2 * lane;
     // 8-byte stores; a lone last column (odd out_w) goes out as 4 bytes
-    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : FIR_OOB;
+    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : kOutOfRange;
     const bool pair_ok = ox + 1 < out_w;
     typedef __attribute__((address_space(3))) float lds_float;
     const lds_float* lrow = (const lds_float*)lds + ((wy * (TH / 2)) * RW + wx * 64 + lane);
@@ -396,17 +383,13 @@ __global__ __launch_bounds__(256) void fir_down2_kernel(const float* __restrict_
         for (int j = 0; j < 4; ++j) kf[i][j] = tap(i, j);
 
     const unsigned in_row_bytes = (unsigned)in_w * 4u, out_row_bytes = (unsigned)out_w * 4u;
-#ifdef MAUA_DEVICE_PASS
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(x) + (size_t)plane * in_h * in_w, 0, (int)((unsigned)in_h * in_row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t y_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(y + (size_t)plane * out_h * out_w, 0, (int)((unsigned)out_h * out_row_bytes), 0x00020000);
-#endif
+    const buffer_rsrc_t x_rsrc = raw_buffer(x + (size_t)plane * in_h * in_w, (int)((unsigned)in_h * in_row_bytes));
+    const buffer_rsrc_t y_rsrc = raw_buffer(y + (size_t)plane * out_h * out_w, (int)((unsigned)out_h * out_row_bytes));
     unsigned voff[NSEG];
 #pragma unroll
     for (int sgm = 0; sgm < NSEG; ++sgm) {
         const int ix = ix0 + sgm * 64 + lane;
-        voff[sgm] = (ix >= 0 && ix < in_w && (sgm < 2 * WX || lane < 2)) ? (unsigned)ix * 4u : FIR_OOB;
+        voff[sgm] = (ix >= 0 && ix < in_w && (sgm < 2 * WX || lane < 2)) ? (unsigned)ix * 4u : kOutOfRange;
     }
     // staging in two halves (rows wave, wave + 4, ...): bounds the loads in flight per lane
     constexpr int NR = (RH + 3) / 4;
@@ -443,8 +426,7 @@ __global__ __launch_bounds__(256) void fir_down2_kernel(const float* __restrict_
     const int wx = wave % WX, wy = wave / WX;
     const int strip_lo = oy0 + wy * TH;
     const int ox = ox0 + wx * 64 + lane;
-    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : FIR_OOB;
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const unsigned out_voff = ox < out_w ? (unsigned)ox * 4u : kOutOfRange;
     typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
     const lds_f32x2* lrow = (const lds_f32x2*)((const __attribute__((address_space(3))) float*)lds + ((2 * wy * TH) * RW + wx * 128 + 2 * lane));
     float w[4][4];  // rolling window: input rows 2 o .. 2 o + 3, the lane's four columns

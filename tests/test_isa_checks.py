@@ -134,7 +134,7 @@ def test_wave_complete_kernel_k_step_composition(device_asm):
 
 @pytest.mark.parametrize("name", SOURCES + STREAMING)
 def test_wide_buffer_stores_carry_their_own_wait_states(device_asm, name):
-    """Round 6 finding (csrc/modconv_w2d.hip buffer_store_b128_sgpr_offset; profiles/r06_store_hazard.md): a MUBUF store of more than 64
+    """Round 6 finding (csrc/conv_device.h buffer_store_b128_sgpr_offset; profiles/r06_store_hazard.md): a MUBUF store of more than 64
     bits whose soffset is an SGPR is hazard-free in the compiler's model, which then lets the next instructions overwrite the data
     registers — on the MI355X the stored row carried the NEXT row's last dword in a quarter of the lanes.  Every buffer store of 3 or 4
     dwords in the hot kernels therefore sits in an inline-assembly blob with `s_nop` right behind it (global_store_* has no soffset and

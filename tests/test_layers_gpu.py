@@ -1042,3 +1042,108 @@ def test_prescaled_instances_equal_the_style_multiplying_ones(gpu, cin, cout, h,
     assert "false" in name_a and "true" in name_p and name_a.replace("false", "true") == name_p, (name_a, name_p)
     assert torch.isfinite(a).all() and torch.isfinite(p).all()
     assert float((a - p).abs().max()) <= 2e-5 * float(a.abs().max())
+
+
+# ---- which kernel instance every convolution entry reports (maua_modconv_last_instance) -----------------------------------------------------
+def _instance_launch(gpu, entry, cin, cout, h, w, mode=None, prescaled=False, seed=0):
+    """One launch of ``entry`` at batch 1 on seeded operands; returns every buffer the call writes.  maua_modconv3x3_f32 goes through
+    ModulatedConv2d.run(mode=...); the other entries are called as StyledConv.run's paths call them, but directly: which path StyledConv.run
+    takes for a shape depends on tuning thresholds that this table must not depend on."""
+    from maua_stylegan2_amd.models.stylegan2 import ModulatedConv2d
+
+    r = torch.Generator().manual_seed(seed)
+
+    def rn(*shape):
+        return torch.randn(*shape, generator=r).to(gpu)
+
+    lib, st = _lib.load(), _lib.stream_ptr(gpu)
+    up = entry in ("upconv_blur", "lowres") or mode in (1, 4, 6, 8)
+    m = ModulatedConv2d(cin, cout, 3, 512, upsample=up).to(gpu)
+    m.weight.copy_(rn(1, cout, cin, 3, 3))
+    x = rn(1, cin, h, w)
+    s = 1 + 0.1 * rn(1, cin + cout)      # this layer's styles, then the ToRGB's
+    d = 0.5 + rn(1, cout).abs()
+    oh, ow = (2 * h, 2 * w) if up else (h, w)
+    noise, noise_w, bias = rn(1, 1, oh, ow), rn(1), rn(cout)
+    s_ptr = None if prescaled else s.data_ptr()
+    dims = (1, cin, cout, h, w)
+    out = {}
+
+    def buf(name, *shape):
+        out[name] = torch.zeros(*shape, device=gpu)
+        return out[name]
+
+    def ws(name, floats):
+        return buf(name, max(int(floats), 1))
+
+    if entry == "modconv":
+        y = buf("y", 1, cout, 2 * h + 1, 2 * w + 1) if up else buf("y", 1, cout, h, w)
+        tail = {} if up else dict(fuse_act=True, noise=noise, noise_w=noise_w, bias=bias)  # (the transposed modes store the raw map)
+        m.run(x, s, 0, d, y, ws("ws", lib.maua_modconv_ws_floats(*dims, mode)), prescaled=prescaled, mode=mode, **tail)
+    elif entry == "lowres":
+        rc = lib.maua_upconv_blur_lowres_f32(
+            x.data_ptr(), m.weight_for(mode).data_ptr(), s_ptr, s.shape[1], d.data_ptr(), buf("y", 1, cout, oh, ow).data_ptr(),
+            ws("ws", lib.maua_lowres_ws_floats(*dims, mode)).data_ptr(), m.blur.kernel.data_ptr(), noise.data_ptr(), 0, noise_w.data_ptr(),
+            bias.data_ptr(), None, 0, *dims, mode, float(m.scale), None, st)
+        _lib.check(rc, "maua_upconv_blur_lowres_f32")
+    elif entry == "upconv_blur":
+        rc = lib.maua_upconv_blur_f32(
+            x.data_ptr(), m.weight_for(6).data_ptr(), s_ptr, s.shape[1], d.data_ptr(), buf("y", 1, cout, oh, ow).data_ptr(),
+            ws("ws", lib.maua_upconv_blur_ws_floats(*dims)).data_ptr(), m.blur.kernel.data_ptr(), noise.data_ptr(), 0, noise_w.data_ptr(),
+            bias.data_ptr(), None, 0, *dims, float(m.scale), None, st)
+        _lib.check(rc, "maua_upconv_blur_f32")
+    else:
+        rgb_w, rgb_bias, rgb_s = rn(3, cout), rn(3), s.data_ptr() + 4 * cin
+        head = (x.data_ptr(), m.weight_for(5).data_ptr(), s_ptr, s.shape[1], d.data_ptr(), buf("y", 1, cout, h, w).data_ptr(), *dims, 5,
+                float(m.scale), noise.data_ptr(), 0, noise_w.data_ptr(), bias.data_ptr(), rgb_w.data_ptr(), rgb_s, cout ** -0.5)
+        if entry == "torgb_partial":
+            m_tiles = lib.maua_modconv_w2d_mtiles(cin, cout, h, w)
+            rc = lib.maua_styledconv_torgb_partial_f32(*head, buf("rgb_partial", 1, 3 * m_tiles, h, w).data_ptr(), None, 0, None, st)
+        else:
+            assert entry == "torgb"
+            rc = lib.maua_styledconv_torgb_f32(*head, rgb_bias.data_ptr(), None, None, buf("rgb", 1, 3, h, w).data_ptr(), 1, None, None, 0, None, st)
+        _lib.check(rc, "maua_styledconv_" + entry + "_f32")
+    torch.cuda.synchronize(gpu)
+    return out
+
+
+# (label, entry, cin, cout, h, w, keywords of _instance_launch, the instance the entry reports).  The names are the ones the library gave
+# before its launch path was unified (taken from a run of this table against that build), except the two maua_upconv_blur_f32 rows, which
+# it did not record at all (it went on reporting the previous launch): theirs are the names bench.py and the tables under profiles/ use.
+_INSTANCE_TABLE = [
+    ("mode 0", "modconv", 8, 32, 16, 16, dict(mode=0), "modconv_mfma_kernel<32, 256, 1, 0, false, true, 2>"),
+    ("mode 1", "modconv", 8, 32, 8, 8, dict(mode=1), "modconv_mfma_kernel<32, 128, 1, 1, false, true, 1>"),
+    ("mode 2", "modconv", 8, 32, 16, 32, dict(mode=2), "modconv_mfma_kernel<32, 128, 1, 2, false, true, 2>"),
+    ("mode 3", "modconv", 8, 32, 16, 32, dict(mode=3), "modconv_mfma_kernel<32, 128, 1, 3, false, true, 3>"),
+    ("mode 4", "modconv", 8, 32, 16, 16, dict(mode=4), "modconv_mfma_kernel<32, 128, 1, 4, false, true, 3>"),  # flat runs need (h + 1)(w / 2 + 1) > 128
+    ("mode 5 w2dw", "modconv", 8, 32, 16, 32, dict(mode=5), "modconv_w2dw_kernel<false>"),
+    ("mode 5 w2dw prescaled", "modconv", 8, 32, 16, 32, dict(mode=5, prescaled=True), "modconv_w2dw_kernel<true>"),
+    ("mode 5 w2d<2>", "modconv", 8, 32, 8, 32, dict(mode=5), "modconv_w2d_kernel<2, 2, 3, false>"),
+    ("mode 5 w2d<2> prescaled", "modconv", 8, 32, 8, 32, dict(mode=5, prescaled=True), "modconv_w2d_kernel<2, 2, 3, true>"),
+    ("mode 5 w2d<4>", "modconv", 8, 64, 8, 32, dict(mode=5), "modconv_w2d_kernel<4, 2, 2, false>"),
+    ("mode 5 w2d<4> prescaled", "modconv", 8, 64, 8, 32, dict(mode=5, prescaled=True), "modconv_w2d_kernel<4, 2, 2, true>"),
+    ("mode 6 CC 4", "modconv", 4, 32, 8, 32, dict(mode=6), "modconv_up2d_kernel<4, 0, false, 32>"),
+    ("mode 6 CC 4 prescaled", "modconv", 4, 32, 8, 32, dict(mode=6, prescaled=True), "modconv_up2d_kernel<4, 0, true, 32>"),
+    ("mode 6 CC 8", "modconv", 8, 32, 8, 32, dict(mode=6), "modconv_up2d_kernel<8, 0, false, 32>"),
+    ("mode 6 CC 8 prescaled", "modconv", 8, 32, 8, 32, dict(mode=6, prescaled=True), "modconv_up2d_kernel<8, 0, true, 32>"),
+    ("mode 7", "modconv", 16, 128, 8, 32, dict(mode=7), "modconv_sbf16_kernel<-1>"),
+    ("mode 8", "modconv", 16, 32, 8, 32, dict(mode=8), "modconv_sbf16_up_kernel"),
+    ("lowres up 1", "lowres", 8, 32, 16, 16, dict(mode=1), "modconv_mfma_kernel<32, 128, 1, 1, false, true, 2>"),
+    ("lowres up 6", "lowres", 8, 32, 16, 16, dict(mode=6), "modconv_up2d_kernel<8, 0, false, 16>"),
+    ("upconv_blur", "upconv_blur", 8, 32, 8, 32, dict(), "modconv_up2d_kernel<8, 2, false, 32>"),
+    ("upconv_blur prescaled", "upconv_blur", 8, 32, 8, 32, dict(prescaled=True), "modconv_up2d_kernel<8, 2, true, 32>"),
+    ("torgb_partial", "torgb_partial", 8, 128, 8, 32, dict(), "modconv_w2d_kernel<4, 2, 2, false>"),
+    ("torgb", "torgb", 8, 32, 16, 32, dict(), "modconv_w2dw_kernel<false>"),
+]
+
+
+def test_last_instance_names_every_conv_entry(gpu):
+    """maua_modconv_last_instance after one launch of every convolution entry and kernel family, at the smallest shape each accepts: the
+    exact name of the template instance that ran (bench.py, tools/microbench.py and the tables under profiles/ join on these strings)."""
+    got = {}
+    for i, (label, entry, cin, cout, h, w, kw, want) in enumerate(_INSTANCE_TABLE):
+        _instance_launch(gpu, entry, cin, cout, h, w, seed=i, **kw)
+        got[label] = (_lib.last_modconv_instance(), want)
+        print(f"{label}: {got[label][0]}")
+    wrong = {k: v for k, v in got.items() if v[0] != v[1]}
+    assert not wrong, wrong
