@@ -37,7 +37,9 @@ int maua_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int 
                        int pad_x0, int pad_x1, int pad_y0, int pad_y1, void* stream);
 
 /* The same op for half / double tensors — the reference dispatches half, float and double (upfirdn2d_kernel.cu:313-359,
- * fused_bias_act_kernel.cu:79).  Generic kernels (fp32 accumulation for half); the fp32 entries above are the tuned path. */
+ * fused_bias_act_kernel.cu:79).  Generic kernels (fp32 accumulation for half); the fp32 entries above are the tuned path.
+ * major == 0 (an empty tensor) is a successful no-op in all three entries: 0 is returned and nothing is launched; a negative major
+ * is MAUA_EINVAL. */
 int maua_upfirdn2d_f16(const void* x, const void* k, void* y, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x,
                        int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, void* stream);
 int maua_upfirdn2d_f64(const void* x, const void* k, void* y, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x,
@@ -49,6 +51,8 @@ int maua_upfirdn2d_f64(const void* x, const void* k, void* y, int major, int in_
 int maua_fused_bias_act_f32(const float* x, const float* b, const float* ref, float* y, int64_t size_x,
                             int size_b, int step_b, int act, int grad, float alpha, float scale, void* stream);
 
+/* Half / double forms.  Half: arithmetic in fp32, and the last step — the multiply by `scale` and the rounding to half — is one
+ * mixed-precision instruction, so the stored half is the exact product rounded once (not its fp32 rounding rounded again). */
 int maua_fused_bias_act_f16(const void* x, const void* b, const void* ref, void* y, int64_t size_x, int size_b, int step_b,
                             int act, int grad, float alpha, float scale, void* stream);
 int maua_fused_bias_act_f64(const void* x, const void* b, const void* ref, void* y, int64_t size_x, int size_b, int step_b,
@@ -378,12 +382,20 @@ int maua_sg1_epilogue_f32(const float* x, const float* bias, const float* noise,
  * (Upsample :34-52, kernel k4 = 4x4 taps in device memory, pad (2,1)).  skip == NULL: no skip.
  *   y[b,c,Y,X] = sum_i (wscale * w[c,i] * s[b,i]) * x[b,i,Y,X] + bias[c] + up2(skip)[b,c,Y,X]
  * w == NULL and s == NULL: x holds per-tile partial ToRGB sums [B, cin = 3 M, H, W] (maua_styledconv_torgb_partial_f32), plane 3 m + c
- * feeding colour c:  y[b,c] = sum_m x[b, 3 m + c] + bias[c] + up2(skip)[b,c]  (wdt % 4 == 0; one round trip of independent loads). */
+ * feeding colour c:  y[b,c] = sum_m x[b, 3 m + c] + bias[c] + up2(skip)[b,c]  (wdt % 4 == 0; one round trip of independent loads).
+ * s is read as s[b * s_stride + i], s_stride >= cin (a window of a wider styles table).  A skip needs k4 and even h and wdt.
+ * Limit of the general form (w != NULL): the three modulated weight rows (3 cin floats, padded to a multiple of 4) and, when the channel
+ * loop is split into slices, 3072 floats of partial sums live in dynamic LDS, which must not exceed 64 KB.  The loop is split whenever
+ * the grid would otherwise have fewer than 512 workgroups of 256 pixel groups, so cin <= 4437 is served at every shape and cin <= 5461
+ * on maps large enough to run unsplit; MAUA_ENOSYS beyond that, before any launch. */
 int maua_torgb_f32(const float* x, const float* w, const float* s, int s_stride, const float* bias,
                    const float* skip, const float* k4, float* y, int batch, int cin, int h, int wdt,
                    float wscale, void* stream);
 
-/* Frame epilogue of render.py:40-43: [B,3,H,W] fp32 -> [B,H,W,3] uint8 via clamp(-1,1), (x+1)*127.5, truncation. */
+/* Frame epilogue of render.py:40-43: [B,3,H,W] fp32 -> [B,H,W,3] uint8 via clamp(-1,1), (x+1)*127.5, truncation — bit for bit the fp32
+ * statement ((clip(x, -1, 1) + 1) * 127.5).astype(uint8).  A NaN becomes 0: the clamp is fminf(fmaxf(x, -1), 1) and fmaxf returns its
+ * other operand for a NaN, hence -1 (numpy's clip would propagate it).  -inf gives 0, +inf 255.  The fused epilogues of the last layer
+ * share this quantiser. */
 int maua_frames_to_u8(const float* img, uint8_t* out, int batch, int h, int w, void* stream);
 /* Wide-output delivery of render.py:97-104 on the device: crop [y0, y0+crop_h) x [x0, x0+crop_w) of uint8 NHWC frames
  * in[B,in_h,in_w,3] and resize to out[B,out_h,out_w,3] as PIL's Image.resize(BILINEAR) does for an up-scale (2-tap triangle filter at

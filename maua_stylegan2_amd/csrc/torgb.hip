@@ -217,6 +217,7 @@ extern "C" int maua_torgb_f32(const float* x, const float* w, const float* s, in
         qpb >>= 1, ++ks_log2;
     const int ks = 1 << ks_log2;
     const size_t lds = ((size_t)((3 * cin + 3) & ~3) + (ks > 1 ? (size_t)ks * qpb * 12 : 0)) * sizeof(float);
+    if (lds > 64 * 1024) return MAUA_ENOSYS;  // (the three weight rows + the slice partials: cin <= 4437 with a split channel loop, 5461 without)
     if (vec == 4)
         hipLaunchKernelGGL(torgb_kernel<4>, dim3(ceil_div(quads, qpb), batch), dim3(256), lds, (hipStream_t)stream, x, w,
                            s, s_stride, bias, skip, k4, y, cin, h, wdt, wscale, ks_log2, qpb);

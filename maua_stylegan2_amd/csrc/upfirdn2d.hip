@@ -526,11 +526,12 @@ __global__ __launch_bounds__(256) void fir_generic_typed_kernel(const T* __restr
 template <typename T, typename A>
 int launch_fir_typed(const void* x, const void* k, void* y, int major, int in_h, int in_w, int minor, int kh, int kw, int up_x,
                      int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, void* stream) {
-    if (!x || !k || !y || major <= 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 ||
+    if (!x || !k || !y || major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 ||
         down_x <= 0 || down_y <= 0)
         return MAUA_EINVAL;
     const int num_h = in_h * up_y + pad_y0 + pad_y1 - kh, num_w = in_w * up_x + pad_x0 + pad_x1 - kw;
     if (num_h < 0 || num_w < 0) return MAUA_EINVAL;
+    if (major == 0) return 0;  // (an empty tensor: nothing to launch, as the fp32 entry)
     const int out_h = num_h / down_y + 1, out_w = num_w / down_x + 1;
     const int64_t total = (int64_t)major * out_h * out_w * minor;
     const int64_t blocks = ceil_div64(total, 256);

@@ -11,7 +11,7 @@ import torch
 RED = 4096
 CANARY_BITS = 0x7FC0BEEF  # a quiet NaN with a payload nothing computes
 _WIDE = (torch.float64, torch.int64)
-_DTYPES = (torch.float32, torch.uint8, torch.float64, torch.int32)
+_DTYPES = (torch.float32, torch.uint8, torch.float64, torch.int32, torch.float16)
 
 
 class Guard:
@@ -26,6 +26,8 @@ class Guard:
         assert dtype in _DTYPES
         if dtype == torch.uint8:
             n_f = (n + 3) // 4
+        elif dtype == torch.float16:
+            n_f = (n + 1) // 2
         elif dtype in _WIDE:
             n_f = 2 * n
         else:
@@ -37,7 +39,7 @@ class Guard:
         """A copy of ``t`` (any shape; a tensor or an array) as ``dtype`` in a guarded window."""
         t = torch.as_tensor(t).to(self.dev, dtype).contiguous()
         raw, n_f = self._alloc(t.numel(), dtype)
-        view = raw[RED: RED + n_f].view(dtype)
+        view = raw[RED: RED + n_f].view(dtype)[:t.numel()]
         view.copy_(t.reshape(-1))
         self.items.append((name, raw, n_f, False))
         self.dtypes[name] = dtype
@@ -49,8 +51,8 @@ class Guard:
         raw, n_f = self._alloc(n, dtype)
         self.items.append((name, raw, n_f, True))
         self.dtypes[name] = dtype
-        if dtype == torch.uint8:
-            return raw[RED: RED + n_f].view(torch.uint8)[:n].view(shape)
+        if dtype in (torch.uint8, torch.float16):  # (n need not fill the last dword)
+            return raw[RED: RED + n_f].view(dtype)[:n].view(shape)
         return raw[RED: RED + n_f].view(dtype).view(shape)
 
     def untouched(self, name):
@@ -76,5 +78,9 @@ class Guard:
                 assert not bool(stale.any()), f"{name}: {int(stale.sum())} elements never written"
                 if name in nonfinite_ok or dtype == torch.int32:
                     continue
-                fl = body.view(torch.float64) if dtype == torch.float64 else body.view(torch.float32)
+                if dtype == torch.float16:  # (half a dword of canary stays behind an odd count: a NaN by design)
+                    halves = body.view(torch.float16)
+                    fl = halves if bool((halves.view(torch.int16)[-1:] != (CANARY_BITS >> 16)).all()) else halves[:-1]
+                else:
+                    fl = body.view(torch.float64) if dtype == torch.float64 else body.view(torch.float32)
                 assert bool(torch.isfinite(fl).all()), f"{name}: non-finite output (an operand was read outside its buffer?)"
