@@ -8,16 +8,22 @@ with ``input_is_latent=True``), different machinery:
   pin + H2D of latents and up to 17 noise maps / batch    inputs are uploaded ONCE and stay resident in HBM (288 GB)
   eager generator call, ~200 launches per batch           hipGraph replay per batch (eager only when bends / rewrites /
                                                           randomize_noise make the batch non-capturable, or a tail batch)
-  clamp/scale/permute on device, per-FRAME .cpu()         uint8 NHWC written by the last layer's epilogue, one async D2H per BATCH into
-  .numpy().astype(uint8), two Python threads + queues     pinned double buffers on a copy stream, ordered sink
+  clamp/scale/permute on device, per-FRAME .cpu()         uint8 NHWC written by the last layer's epilogue, one async D2H per BATCH on a copy
+  .numpy().astype(uint8), two Python threads + queues     stream into a 6-slot pinned ring (from its device-side twin), ordered sink thread
   DataParallel replicate/scatter/gather per forward       one process per GPU, contiguous frame shards, RCCL gather of
                                                           uint8 frames to rank 0 (maua_stylegan2_amd/sharding.py)
+
+``render_shard`` runs ONE frame loop whatever carries the frames to the sink: a delivery object per transport (_LocalRing on one GPU;
+_HostStore / _GatherStream under a process group) with ``push(u8)`` — one deliverable batch, the producing stream current —,
+``finish(frame_shape)`` — end of this rank's frames, also when it had none — and ``close()`` — safe after a failure, and twice.
 
 Sinks: ffmpeg rawvideo pipe (same pixel format / codec arguments as render.py:58-91) when an ``ffmpeg`` binary exists,
 otherwise raw rgb24 bytes to ``output_file`` (+ ".rgb24"), or a null sink for benchmarking (``output_file=None``).
 Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to planar YUV 4:2:0 on the device (frames_to_yuv420p) before
 they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
 """
+import collections
+import contextlib
 import gc
 import os
 import queue
@@ -269,7 +275,6 @@ def _deliverable(u8, out_size, pix_fmt, scratch):
     return frames_to_yuv420p(u8, scratch) if pix_fmt == "yuv420p" else u8
 
 
-_LANE_STREAMS = {}
 class parked_heap:
     """``with parked_heap():`` — no generation-2 collection on the thread that launches the graph replays: everything alive at entry moves
     to the collector's permanent generation (gc.freeze) and comes back at exit.  Re-entrant and shared between threads: the freeze is
@@ -304,6 +309,8 @@ class parked_heap:
 _RING_LOCKS = {}  # device index -> lock held by the single-GPU render loop while it uses that device's rings (two renders in two threads)
 _PINNED_RING = {}  # device index -> pinned staging slots of the single-GPU render loop (reallocated when the frame shape changes)
 _DEVICE_RING = {}  # device index -> their device-side twins (a batch leaves its lane's frame buffer before it crosses PCIe)
+_RING_SLOTS = 6
+_LANE_STREAMS = {}  # (device index, lane number) -> the stream that lane's forwards run on (_lane_stream)
 
 
 def release_rings(device=None):
@@ -329,6 +336,16 @@ def _lane_stream(dev, k):
 UNSEEDED_GRAPH_MIN_FRAMES = 2048  # randomised renders without generator.noise_seed below this length keep the eager path (synthesize)
 
 
+def _lane_is_stale(lane, weights_key, slots, seed, offset, synth_slots, synth_offset):
+    """Whether a cached lane has to be captured again: its weights changed, or a kernel argument of one of its captured noise launches
+    differs from what this render asks for — (seed, frame offset) of the random slots, the frame offset of the synthesised ones."""
+    if lane.weights_key != weights_key:
+        return True
+    if slots and (lane.noise_seed, lane.noise_frame_offset) != (seed, offset):
+        return True
+    return bool(synth_slots) and lane.synth_frame_offset != synth_offset
+
+
 def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=None):
     """``n_lanes`` captured forwards (GraphLane) of ``batch_size`` frames with uint8 frame output, each on its own stream.
     Without bends they are cached on the generator and reused by every later render (a captured forward reads its inputs
@@ -343,6 +360,12 @@ def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=Non
     slots, seed, offset = random if random else ((), 0, 0)
     slots = tuple(slots)
     synth_slots, synth_offset = (tuple(synth[0]), int(synth[1])) if synth else ((), 0)
+    # only what the render asks for is passed on: StyleGAN1's capture_graph takes (batch, lane, frames_u8, bends) and nothing else
+    extra = {}
+    if slots:
+        extra.update(random_slots=slots, noise_seed=seed, noise_frame_offset=offset)
+    if synth_slots:
+        extra.update(synth_slots=synth_slots, synth_frame_offset=synth_offset)
     key = generator.weights_key()
     cache = generator.__dict__.setdefault("_graph_lanes", {})
     lanes = []
@@ -351,21 +374,10 @@ def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=Non
         stream = _lane_stream(dev, k)
         cache_key = (batch_size, k, tap) + ((slots,) if slots else ()) + ((("synth",) + synth_slots,) if synth_slots else ())
         lane = None if bends else cache.get(cache_key)
-        if lane is not None and (lane.weights_key != key or (slots and (lane.noise_seed, lane.noise_frame_offset) != (seed, offset))):
-            lane = None
-        if lane is not None and synth_slots and lane.synth_frame_offset != synth_offset:
-            lane = None
-        if lane is None:
+        if lane is None or _lane_is_stale(lane, key, slots, seed, offset, synth_slots, synth_offset):
             stream.wait_stream(th.cuda.current_stream(dev))
             with th.cuda.stream(stream):
-                if synth_slots:
-                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, random_slots=slots, noise_seed=seed,
-                                                   noise_frame_offset=offset, synth_slots=synth_slots, synth_frame_offset=synth_offset)
-                elif slots:
-                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, random_slots=slots, noise_seed=seed,
-                                                   noise_frame_offset=offset)
-                else:
-                    lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends)
+                lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, **extra)
             stream.synchronize()
             if not bends:
                 cache[cache_key] = lane
@@ -408,16 +420,15 @@ def _sequence_bends(bends, n_frames=None):
     return out, capturable
 
 
-def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), rewrites=None, randomize_noise=False,
-               use_graph=True, frame_range=None, lanes=3):
-    """Generator -> uint8 frames for ``frame_range`` (default: all) of the sequence.  Yields (first_frame_index,
-    uint8 device tensor [b, H, W, 3]) per batch, in order, with the producing stream current; the tensor stays valid
-    until ``lanes`` further batches have been requested.
+# What a render's inputs decide before its first batch (_plan_render).  random / synth: graph_lanes' arguments of those names, or None;
+# trunc_t: the per-frame truncation sequence, None for the exact identity; seq_bends: the bends as the graph lanes capture them
+_Plan = collections.namedtuple("_Plan", "dev lo hi latents noise recipes synth truncation trunc_t bends rewrites original_weights random "
+                                        "randomize_noise capturable seq_bends")
 
-    hipGraph path: ``lanes`` graphs of ``batch_size`` frames (same weights, private activations) are replayed round-robin
-    on their own streams, so consecutive batches overlap on the device — the small, latency-bound 4^2..32^2 layers and
-    the last partial wave of every big launch of one batch run underneath the other batch's MFMA-bound layers.  The
-    sequences (latents, noise maps, truncation, bend modulations) stay resident in HBM; a replay moves one frame index."""
+
+def _plan_render(generator, latents, noise, truncation, bends, rewrites, randomize_noise, use_graph, frame_range):
+    """The part of ``synthesize`` that runs once: inputs made resident on the device, recipes and rewrites checked, and the decision
+    between graph lanes and the eager path."""
     dev = device_of(generator)
     n_total = len(latents)
     lo, hi = frame_range if frame_range is not None else (0, n_total)
@@ -477,76 +488,84 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
     seq_bends = []
     if capturable and bends:
         seq_bends, capturable = _sequence_bends(bends, n_total) if getattr(generator, "capturable_bends", True) else (None, False)
-    n_lanes = max(1, int(lanes)) if capturable else 1
-    caller_stream = th.cuda.current_stream(dev)
-    lane_state = []  # (stream, GraphLane or None)
-    if capturable and hi - lo >= batch_size:
-        if synth is None:
-            lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random)
-        else:
-            lane_state = graph_lanes(generator, batch_size, min(n_lanes, (hi - lo) // batch_size), seq_bends, random, synth)
-        n_lanes = len(lane_state)
-        for stream, lane in lane_state:
-            lane.bind(latents, noise, trunc_t)  # once per render: the pointers of the HBM-resident sequences
-            stream.wait_stream(caller_stream)
-    else:
-        stream = _lane_stream(dev, 0)
-        stream.wait_stream(caller_stream)
-        lane_state = [(stream, None)]
-        n_lanes = 1
-    eager_u8 = None
+    return _Plan(dev, lo, hi, latents, noise, recipes, synth, truncation, trunc_t, bends, rewrites, original_weights, random,
+                 randomize_noise, capturable, seq_bends)
 
+
+def _set_parameter(generator, dotted_name, tensor):
+    """``generator.<dotted_name> = Parameter(tensor)``: how a rewrite is applied to the module tree, and how it is taken back."""
+    module = generator
+    *path, leaf = dotted_name.split(".")
+    for attr in path:
+        module = getattr(module, attr)
+    setattr(module, leaf, th.nn.Parameter(tensor, requires_grad=False))
+
+
+def _eager_batch(generator, plan, n, m, stream, lane_streams, out):
+    """Frames [n, m) by one eager forward on ``stream`` (the current one): every batch of a render that is not capturable, the ragged tail
+    batch of one that is.  ``lane_streams``: the captured lanes' streams, drained first.  Returns the uint8 frames, in ``out`` when it fits."""
+    b = m - n
+    noise_batch = [None if nz is None or isinstance(nz, NoiseSynth) else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in plan.noise]  # [1, ...] = one map for every frame
+    for i, recipe in plan.recipes.items():  # the launch a graph lane makes for these frames, without a frame source
+        noise_batch[i] = recipe.frames(n, b, i)
+    if plan.random is not None:  # the same maps a graph lane generates for these frames
+        slots, seed, offset = plan.random
+        for i, nz in zip(slots, generator.random_noise(offset + n, b, seed, slots)):
+            noise_batch[i] = nz
+    bend_batch = []
+    for bend in plan.bends:
+        transform = bend["transform"](bend["modulation"][n:m]) if "modulation" in bend else bend["transform"]
+        bend_batch.append({"layer": bend["layer"], "transform": transform})
+    for name, (rewrite, modulation) in plan.rewrites.items():
+        new_weight = rewrite(modulation[n:m])(plan.original_weights[name]).to(plan.dev, th.float32).contiguous()
+        _set_parameter(generator, name, new_weight)
+    for other in lane_streams:  # the eager tail batch shares lane 0's activations: let every lane drain first
+        stream.wait_stream(other)
+    images, _ = generator(styles=plan.latents[n:m], noise=noise_batch,
+                          truncation=plan.truncation if plan.trunc_t is None else plan.trunc_t[n:m],
+                          transform_dict_list=bend_batch, randomize_noise=plan.randomize_noise, input_is_latent=True)
+    if out is None or out.shape[0] != b or out.shape[1:3] != images.shape[2:]:
+        out = th.empty((b, images.shape[2], images.shape[3], 3), dtype=th.uint8, device=plan.dev)
+    return frames_to_uint8(images, out)
+
+
+def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), rewrites=None, randomize_noise=False,
+               use_graph=True, frame_range=None, lanes=3):
+    """Generator -> uint8 frames for ``frame_range`` (default: all) of the sequence.  Yields (first_frame_index,
+    uint8 device tensor [b, H, W, 3]) per batch, in order, with the producing stream current; the tensor stays valid
+    until ``lanes`` further batches have been requested.
+
+    hipGraph path: ``lanes`` graphs of ``batch_size`` frames (same weights, private activations) are replayed round-robin
+    on their own streams, so consecutive batches overlap on the device — the small, latency-bound 4^2..32^2 layers and
+    the last partial wave of every big launch of one batch run underneath the other batch's MFMA-bound layers.  The
+    sequences (latents, noise maps, truncation, bend modulations) stay resident in HBM; a replay moves one frame index."""
+    plan = _plan_render(generator, latents, noise, truncation, bends, rewrites, randomize_noise, use_graph, frame_range)
+    caller_stream = th.cuda.current_stream(plan.dev)
+    full_batches = (plan.hi - plan.lo) // batch_size
+    if plan.capturable and full_batches >= 1:
+        lane_state = graph_lanes(generator, batch_size, min(max(1, int(lanes)), full_batches), plan.seq_bends, plan.random, plan.synth)
+        for stream, lane in lane_state:
+            lane.bind(plan.latents, plan.noise, plan.trunc_t)  # once per render: the pointers of the HBM-resident sequences
+            stream.wait_stream(caller_stream)
+    else:  # the eager path has lane 0's stream to itself
+        lane_state = [(_lane_stream(plan.dev, 0), None)]
+        lane_state[0][0].wait_stream(caller_stream)
+    captured_streams = [stream for stream, lane in lane_state if lane is not None]
+    eager_u8 = None
     try:
-        k = 0
-        for n in range(lo, hi, batch_size):
-            m = min(n + batch_size, hi)
-            b = m - n
-            stream, lane = lane_state[k % n_lanes]
+        for k, n in enumerate(range(plan.lo, plan.hi, batch_size)):
+            m = min(n + batch_size, plan.hi)
+            stream, lane = lane_state[k % len(lane_state)]
             with th.cuda.stream(stream):
-                if lane is not None and b == batch_size:
+                if lane is not None and m - n == batch_size:
                     lane.replay(n)
                     yield n, lane.u8  # the frame epilogue is part of the captured forward (fused into the last ToRGB)
-                    k += 1
-                    continue
-                noise_batch = [None if nz is None or isinstance(nz, NoiseSynth) else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in noise]  # [1, ...] = one map for every frame
-                for i, recipe in recipes.items():  # the launch a graph lane makes for these frames, without a frame source
-                    noise_batch[i] = recipe.frames(n, b, i)
-                if random is not None:  # the same maps a graph lane generates for these frames
-                    for i, nz in zip(random[0], generator.random_noise(random[2] + n, b, random[1], random[0])):
-                        noise_batch[i] = nz
-                bend_batch = []
-                for bend in bends:
-                    if "modulation" in bend:
-                        transform = bend["transform"](bend["modulation"][n:m])
-                        bend_batch.append({"layer": bend["layer"], "transform": transform})
-                    else:
-                        bend_batch.append({"layer": bend["layer"], "transform": bend["transform"]})
-                for name, (rewrite, modulation) in rewrites.items():
-                    new_weight = rewrite(modulation[n:m])(original_weights[name]).to(dev, th.float32).contiguous()
-                    module = generator
-                    *path, leaf = name.split(".")
-                    for attr in path:
-                        module = getattr(module, attr)
-                    setattr(module, leaf, th.nn.Parameter(new_weight, requires_grad=False))
-                if n_lanes > 1 or lane is not None:  # the eager tail batch shares lane 0's activations: let every lane drain first
-                    for other, _ in lane_state:
-                        stream.wait_stream(other)
-                images, _ = generator(styles=latents[n:m], noise=noise_batch,
-                                      truncation=truncation if trunc_t is None else trunc_t[n:m],
-                                      transform_dict_list=bend_batch, randomize_noise=randomize_noise,
-                                      input_is_latent=True)
-                if eager_u8 is None or eager_u8.shape[0] != b or eager_u8.shape[1:3] != images.shape[2:]:
-                    eager_u8 = th.empty((b, images.shape[2], images.shape[3], 3), dtype=th.uint8, device=dev)
-                frames_to_uint8(images, eager_u8)
-                yield n, eager_u8
-            k += 1
+                else:
+                    eager_u8 = _eager_batch(generator, plan, n, m, stream, captured_streams, eager_u8)
+                    yield n, eager_u8
     finally:  # also when the consumer stops early (sink error, generator closed)
-        for name, w in original_weights.items():  # leave the generator as it was found
-            module = generator
-            *path, leaf = name.split(".")
-            for attr in path:
-                module = getattr(module, attr)
-            setattr(module, leaf, th.nn.Parameter(w, requires_grad=False))
+        for name, weight in plan.original_weights.items():  # leave the generator as it was found
+            _set_parameter(generator, name, weight)
         for stream, lane in lane_state:
             caller_stream.wait_stream(stream)
             if lane is not None:
@@ -562,6 +581,141 @@ def render(generator, latents, noise, offset, duration, batch_size, out_size, ou
                         truncation, bends, rewrites, randomize_noise, ffmpeg_preset, None)
 
 
+def _drain_quietly(worker):
+    """``worker.close()`` while a render unwinds: whatever was submitted is written or dropped before the buffers it reads are let go."""
+    with contextlib.suppress(BaseException):  # (a second failure while unwinding must not mask the first)
+        worker.close()
+
+
+class _LocalRing:
+    """Single-GPU delivery.  Pinned staging ring: the D2H of batch k overlaps the replays of the next batches; the sink thread writes a
+    slot and hands it back through ``free`` (the launch thread blocks in ``push`` only when the sink is _RING_SLOTS batches behind).  Holds the
+    device's ring lock from construction to ``close``."""
+
+    def __init__(self, dev, batch_size, worker):
+        self.dev, self.batch_size, self.worker = dev, batch_size, worker
+        self.copy_stream = th.cuda.Stream(dev)
+        index = dev.index if dev.index is not None else th.cuda.current_device()  # torch.device("cuda") carries no index
+        self.lock = _RING_LOCKS.setdefault(index, threading.Lock())
+        self.lock.acquire()  # the rings are per device, not per render: a second render on this device (another thread) waits
+        self.pinned = _PINNED_RING.setdefault(index, [None] * _RING_SLOTS)  # kept across renders: pinning 6 x 25 MB is ~40 ms
+        self.staged = _DEVICE_RING.setdefault(index, [None] * _RING_SLOTS)
+        self.free = queue.Queue()
+        for i in range(_RING_SLOTS):
+            self.free.put(i)
+
+    def push(self, u8):
+        slot = self.free.get()
+        count = u8.shape[0]
+        # slots hold a FULL batch; the tail batch of a render uses a prefix (re-pinning per shape cost 2 x 6.5 ms per render)
+        if self.pinned[slot] is None or self.pinned[slot].shape[1:] != u8.shape[1:] or self.pinned[slot].shape[0] < max(count, self.batch_size):
+            shape = (max(count, self.batch_size),) + tuple(u8.shape[1:])
+            self.pinned[slot] = th.empty(shape, dtype=th.uint8).pin_memory()
+            self.staged[slot] = th.empty(shape, dtype=th.uint8, device=self.dev)
+        host, held = self.pinned[slot][:count], self.staged[slot][:count]
+        # the lane's frame buffer is overwritten by its next replay: the batch moves to a device-side slot on the lane's own
+        # stream (25 MB inside HBM: ~20 us) and crosses PCIe from there, so that no lane ever waits for a host copy
+        # (waiting for it — 0.5 ms per batch on the lane — cost the render loop the whole gain of the three lanes)
+        held.copy_(u8, non_blocking=True)
+        produced = th.cuda.current_stream(self.dev).record_event()
+        with th.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(produced)
+            host.copy_(held, non_blocking=True)
+            copied = self.copy_stream.record_event()
+        self.worker.submit(copied.synchronize, host.numpy(), count, lambda s=slot: self.free.put(s))
+
+    def finish(self, frame_shape):
+        pass  # (the caller's worker.close() waits for the slots in flight)
+
+    def close(self):
+        if self.lock is not None:
+            # the lock goes back only once the worker has drained: a ring slot must not reach the next render while the sink thread reads it
+            _drain_quietly(self.worker)
+            self.lock.release()
+            self.lock = None
+
+
+class _HostStore:
+    """Transport "host": every rank copies its rounds to a pinned shared-memory segment over its own PCIe link; rank 0's sink thread
+    reads the segments in global order (sharding.HostFrameStore) — no xGMI traffic, no funnel through rank 0's link."""
+
+    def __init__(self, n_frames, batch_size, dev, rank, worker):
+        self.n_frames, self.batch_size, self.dev, self.rank, self.worker = n_frames, batch_size, dev, rank, worker
+        self.token = sharding.broadcast_object(f"{os.getpid():x}{int.from_bytes(os.urandom(4), 'little'):08x}" if rank == 0 else None)
+        self.store = self.reader = None
+        self.stop_reader = threading.Event()  # set when this rank's launch loop fails: the reader must not outlive the store
+        self.pushed = 0
+
+    def _opened(self, frame_shape):
+        if self.store is None:
+            self.store = sharding.HostFrameStore(self.n_frames, self.batch_size, tuple(frame_shape), self.dev, self.token)
+            if self.rank == 0:
+                self.reader = threading.Thread(target=self._read, args=(self.store,), name="maua-host-gather", daemon=True)
+                self.reader.start()
+        return self.store
+
+    def _read(self, store):
+        # (worker.feed, not submit: a sink error must stay on the worker for the LAUNCH thread — popped here it would end
+        # this thread, clear itself, and the render would return a truncated video without an exception)
+        for _, count, host in store.rounds_in_order(stop=self.stop_reader.is_set):
+            if not self.worker.feed(None, host.numpy(), count, None):
+                return
+
+    def push(self, u8):
+        self._opened(u8.shape[1:]).push(self.pushed, u8)
+        self.pushed += 1
+
+    def finish(self, frame_shape):
+        self._opened(frame_shape).finish()
+        if self.reader is not None:
+            self.reader.join()
+            self.worker.close()  # re-raises a sink error on the launch thread
+
+    def close(self):
+        if self.reader is not None and self.reader.is_alive():  # the launch loop failed: stop the reader BEFORE its segments go away
+            self.stop_reader.set()
+            self.reader.join()
+        if self.store is not None:
+            self.store.close()
+            self.store = None
+
+
+class _GatherStream:
+    """Transport "gather" (sharding.FrameStream): one asynchronous gather per batch-round, issued as soon as the round's frames exist:
+    the transfer of round k runs under the compute of rounds k+1.., rank 0 hands rounds to its sink thread as they land (its own block
+    first — the blocks are contiguous — while the peers' frames accumulate in its HBM store)."""
+
+    def __init__(self, n_frames, batch_size, dev, rank, worker):
+        self.n_frames, self.batch_size, self.dev, self.rank, self.worker = n_frames, batch_size, dev, rank, worker
+        self.stream = None
+        self.pushed = 0
+
+    def _opened(self, frame_shape):  # the frame shape is whatever the generator (and its layer-0 bends) produce
+        if self.stream is None:
+            self.stream = sharding.FrameStream(self.n_frames, self.batch_size, tuple(frame_shape), self.dev)
+        return self.stream
+
+    def _deliver(self, block):
+        for _, count, host, release in self.stream.drain_rounds(block=block):
+            self.worker.submit(None, host.numpy(), count, release)
+
+    def push(self, u8):
+        self._opened(u8.shape[1:]).push(self.pushed, u8)
+        self.pushed += 1
+        if self.rank == 0:
+            self._deliver(False)
+
+    def finish(self, frame_shape):
+        self._opened(frame_shape).finish()  # a rank whose block is empty (more ranks than frames) still takes part in every round
+        if self.rank == 0:
+            self._deliver(True)
+        else:
+            self.stream.wait_all()
+
+    def close(self):
+        self.stream = None
+
+
 def render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
     """``render`` with an optional ``_shard = (lo, hi, n_frames)``: set by generate() after sharding.scatter_frames, it says
@@ -571,165 +725,48 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     width, height = _output_dims(out_size)
     pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
     rank, world = sharding.rank_world()
-    # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM, sharding.FrameStream) or "host"
-    # (per-rank D2H into shared memory, sharding.HostFrameStore)
+    # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM) or "host" (per-rank D2H into shared memory)
     transport = transport or os.environ.get("MAUA_FRAME_TRANSPORT", "gather")
     if transport not in ("gather", "host"):
         raise ValueError(f"unknown frame transport {transport!r} (gather | host)")
     if _shard is None:
         n_frames = len(latents)
-        lo, hi = sharding.shard_bounds(n_frames, rank, world)
+        lo, hi = sharding.shard_bounds(n_frames, rank, world)  # (no process group: rank 0 of 1, every frame)
         frame_range = (lo, hi)
     else:
         lo, hi, n_frames = _shard
         frame_range = (0, hi - lo)
-    # the sequences of a scattered shard start at the job's frame `lo`: seeded noise is a function of the absolute frame
-    shifted = _shard is not None and hasattr(generator, "random_noise")
-    if shifted:
-        generator.noise_frame_offset = lo
     dev = device_of(generator)
-    sink = None
-    if rank == 0:
-        sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt)
-
-    worker = SinkWorker(sink) if sink is not None else None
-    locked = False
-    # The frame loop runs on the Python thread that launches every graph replay.  A generation-2 collection walks the ~170 k long-lived
-    # objects of a process that has torch imported: 45-90 ms, i.e. 8-15 batches during which no replay is launched (measured: tools/gather_probe.py,
-    # and as a 9 % hole in a 150-batch gathered bench region).  Park everything that is alive now in the permanent generation for the
-    # duration of the loop: what the loop allocates is then all the collector ever walks.  (No full gc.collect() here: it would cost the same
-    # 45-90 ms up front, as much as it saves on a 900-frame job; generate() has just run one, as the reference does.)
-    parked = parked_heap()
-    parked.__enter__()
-    try:
-        if not sharding.grouped():
-            # pinned staging ring: the D2H of batch k overlaps the replays of the next batches; the sink thread writes a slot and
-            # hands it back through `free` (the launch thread blocks here only when the sink is `n_slots` batches behind)
-            n_lanes, n_slots = 3, 6
-            copy_stream = th.cuda.Stream(dev)
-            index = dev.index if dev.index is not None else th.cuda.current_device()  # torch.device("cuda") carries no index
-            ring_lock = _RING_LOCKS.setdefault(index, threading.Lock())
-            ring_lock.acquire()  # the rings are per device, not per render: a second render on this device (another thread) waits
-            locked = True
-            pinned = _PINNED_RING.setdefault(index, [None] * n_slots)  # kept across renders: pinning 6 x 25 MB is ~40 ms
-            staged = _DEVICE_RING.setdefault(index, [None] * n_slots)
-            free = queue.Queue()
-            for i in range(n_slots):
-                free.put(i)
-            resized = {}
-            for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
-                                        randomize_noise, lanes=n_lanes):
-                u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)  # 2048-px frames leave the device as 1920x1080 already
-                slot = free.get()
-                count = u8.shape[0]
-                # slots hold a FULL batch; the tail batch of a render uses a prefix (re-pinning per shape cost 2 x 6.5 ms per render)
-                if pinned[slot] is None or pinned[slot].shape[1:] != u8.shape[1:] or pinned[slot].shape[0] < max(count, batch_size):
-                    shape = (max(count, batch_size),) + tuple(u8.shape[1:])
-                    pinned[slot] = th.empty(shape, dtype=th.uint8).pin_memory()
-                    staged[slot] = th.empty(shape, dtype=th.uint8, device=dev)
-                host, held = pinned[slot][:count], staged[slot][:count]
-                # the lane's frame buffer is overwritten by its next replay: the batch moves to a device-side slot on the lane's own
-                # stream (25 MB inside HBM: ~20 us) and crosses PCIe from there, so that no lane ever waits for a host copy
-                # (waiting for it — 0.5 ms per batch on the lane — cost the render loop the whole gain of the three lanes)
-                held.copy_(u8, non_blocking=True)
-                produced = th.cuda.Event()
-                produced.record(th.cuda.current_stream(dev))
-                with th.cuda.stream(copy_stream):
-                    copy_stream.wait_event(produced)
-                    host.copy_(held, non_blocking=True)
-                    copied = th.cuda.Event()
-                    copied.record(copy_stream)
-                worker.submit(copied.synchronize, host.numpy(), count, lambda s=slot: free.put(s))
-        elif transport == "host":
-            # every rank copies its rounds to a pinned shared-memory segment over its own PCIe link; rank 0's sink thread reads the
-            # segments in global order (sharding.HostFrameStore) — no xGMI traffic, no funnel through rank 0's link
-            token = sharding.broadcast_object(f"{os.getpid():x}{int.from_bytes(os.urandom(4), 'little'):08x}" if rank == 0 else None)
-            store = None
-            reader = None
-            k = 0
-            resized = {}
-
-            stop_reader = threading.Event()  # set when this rank's launch loop fails: the reader must not outlive the store
-
-            def start_reader():
-                def run():
-                    # (worker.feed, not submit: a sink error must stay on the worker for the LAUNCH thread — popped here it would end
-                    # this thread, clear itself, and the render would return a truncated video without an exception)
-                    for _, count, host in store.rounds_in_order(stop=stop_reader.is_set):
-                        if not worker.feed(None, host.numpy(), count, None):
-                            return
-
-                t = threading.Thread(target=run, name="maua-host-gather", daemon=True)
-                t.start()
-                return t
-
-            try:
-                for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
-                                            randomize_noise, frame_range=frame_range):
-                    u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)
-                    if store is None:
-                        store = sharding.HostFrameStore(n_frames, batch_size, tuple(u8.shape[1:]), dev, token)
-                        if rank == 0:
-                            reader = start_reader()
-                    store.push(k, u8)
-                    k += 1
-                if store is None:
-                    store = sharding.HostFrameStore(n_frames, batch_size, _stream_frame_shape(generator, out_size, pipe_pix_fmt), dev, token)
-                    if rank == 0:
-                        reader = start_reader()
-                store.finish()
-                if reader is not None:
-                    reader.join()
-                    worker.close()  # re-raises a sink error on the launch thread
-            finally:
-                if reader is not None and reader.is_alive():  # the launch loop failed: stop the reader BEFORE its segments go away
-                    stop_reader.set()
-                    reader.join()
-                if store is not None:
-                    store.close()
-        else:
-            # One asynchronous gather per batch-round, issued as soon as the round's frames exist: the transfer of round k
-            # runs under the compute of rounds k+1.., rank 0 hands rounds to its sink thread as they land (its own block
-            # first — the blocks are contiguous — while the peers' frames accumulate in its HBM store).
-            stream = None
-            k = 0
-            resized = {}
-
-            def deliver(block):
-                for _, count, host, release in stream.drain_rounds(block=block):
-                    worker.submit(None, host.numpy(), count, release)
-
-            for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites,
-                                        randomize_noise, frame_range=frame_range):
-                u8 = _deliverable(u8, out_size, pipe_pix_fmt, resized)
-                if stream is None:  # the frame shape is whatever the generator (and its layer-0 bends) produce
-                    stream = sharding.FrameStream(n_frames, batch_size, tuple(u8.shape[1:]), dev)
-                stream.push(k, u8)
-                k += 1
-                if rank == 0:
-                    deliver(False)
-            if stream is None:  # a rank whose block is empty (more ranks than frames) still takes part in every round
-                stream = sharding.FrameStream(n_frames, batch_size, _stream_frame_shape(generator, out_size, pipe_pix_fmt), dev)
-            stream.finish()
-            if rank == 0:
-                deliver(True)
+    sink = worker = None
+    with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
+        if rank == 0:
+            sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt)
+            unwind.callback(sink.close)  # the encoder process / output file must not outlive a failed render: closed last, and always
+            worker = SinkWorker(sink)
+            unwind.callback(_drain_quietly, worker)
+        if _shard is not None and hasattr(generator, "random_noise"):
+            # the sequences of a scattered shard start at the job's frame `lo`: seeded noise is a function of the absolute frame
+            generator.noise_frame_offset = lo
+            unwind.callback(setattr, generator, "noise_frame_offset", 0)
+        # The frame loop runs on the Python thread that launches every graph replay.  A generation-2 collection walks the ~170 k long-lived
+        # objects of a process that has torch imported: 45-90 ms, i.e. 8-15 batches during which no replay is launched (measured: tools/gather_probe.py,
+        # and as a 9 % hole in a 150-batch gathered bench region).  Park everything that is alive now in the permanent generation for the
+        # duration of the loop: what the loop allocates is then all the collector ever walks.  (No full gc.collect() here: it would cost the same
+        # 45-90 ms up front, as much as it saves on a 900-frame job; generate() has just run one, as the reference does.)
+        with parked_heap():
+            if not sharding.grouped():
+                delivery = _LocalRing(dev, batch_size, worker)
             else:
-                stream.wait_all()
-        if worker is not None:
-            worker.close()
-    finally:  # the encoder process / output file must not outlive a failed render
-        parked.__exit__(None, None, None)
-        if shifted:
-            generator.noise_frame_offset = 0
-        if worker is not None:
-            try:
-                worker.close()  # (also: every ring slot has been written before the rings are handed to the next render)
-            except BaseException:  # noqa: BLE001 - (a second failure while unwinding must not mask the first)
-                pass
-        if locked:
-            ring_lock.release()
-        if sink is not None:
-            sink.close()
+                delivery = (_HostStore if transport == "host" else _GatherStream)(n_frames, batch_size, dev, rank, worker)
+            with contextlib.closing(delivery):
+                scratch = {}  # the reusable output buffers of the device-side crop / resize / conversion
+                # (lanes: synthesize's default, 3, on every path)
+                for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
+                                        frame_range=frame_range):
+                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch))  # 2048-px frames leave the device as 1920x1080 already
+                delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt))
+                if worker is not None:
+                    worker.close()  # every frame is written; re-raises a sink error on the launch thread
     return sink.count if sink is not None else 0
 
 

@@ -1193,3 +1193,122 @@ def test_generator_is_kept_across_generate_calls_and_follows_the_checkpoint_file
     fourth = job("4.mp4")
     assert len(loads) == 3 and np.array_equal(third, fourth)
     gav._GENERATOR_CACHE.clear()
+
+
+# ---- failure handling of the single-GPU frame loop: what a sink error or an abandoned synthesize must leave behind ----
+
+PIN_SIZE, PIN_FRAMES, PIN_BATCH = 32, 7, 2  # three captured batches (one per graph lane) + an eager tail batch of one frame
+
+
+class _SinkBroke(Exception):
+    pass
+
+
+@pytest.fixture(scope="module")
+def pinned_job(gpu):
+    """A seeded 32-px generator, its sequences and the frames of one complete ``synthesize`` (computed once, read-only)."""
+    from maua_stylegan2_amd import render
+
+    g = build(PIN_SIZE, gpu, 4)
+    lat = seeding.seeded_latents(PIN_FRAMES, g.n_latent, seed=6)
+    noise = seeding.seeded_noise(PIN_FRAMES, PIN_SIZE, seed=7)
+    noise[-1] = None
+    want = _synthesized(render, g, lat, noise)
+    want.setflags(write=False)
+    return g, lat, noise, want
+
+
+def _synthesized(render, g, lat, noise, **kw):
+    frames = np.zeros((PIN_FRAMES, PIN_SIZE, PIN_SIZE, 3), np.uint8)
+    for first, u8 in render.synthesize(g, lat, noise, PIN_BATCH, **kw):
+        frames[first: first + u8.shape[0]] = u8.cpu().numpy()
+    return frames
+
+
+def test_failing_sink_on_the_single_gpu_path_leaves_the_device_usable(gpu, pinned_job, monkeypatch):
+    """A sink whose ``write`` raises at the fourth frame: render() raises that exception on the calling thread, and straight afterwards
+    the heap is thawed, the generator's noise frame offset is 0, the device's ring lock is free; the next render of the same inputs
+    delivers the 7 frames of a clean render made before, byte for byte, on the graph lanes that were cached before the failure."""
+    import gc
+
+    from maua_stylegan2_amd import render
+
+    g, lat, noise, want = pinned_job
+    written = []
+
+    class Sink(render.FrameSink):
+        fail_at = None
+
+        def __init__(self, *a, **k):
+            self.count = 0
+
+        def write(self, frame):
+            if self.count == self.fail_at:
+                raise _SinkBroke(f"frame {self.count}")
+            written.append(np.array(frame, copy=True))
+            self.count += 1
+
+        def close(self):
+            pass
+
+    monkeypatch.setattr(render, "FrameSink", Sink)
+    monkeypatch.setattr(render, "_output_dims", lambda out_size: (PIN_SIZE, PIN_SIZE))
+    monkeypatch.delenv("MAUA_PIPE_PIX_FMT", raising=False)
+
+    def run():
+        del written[:]
+        return render.render(g, lat, noise, 0, PIN_FRAMES / 30, PIN_BATCH, PIN_SIZE, None)
+
+    assert run() == PIN_FRAMES
+    clean = np.stack(written)
+    assert np.array_equal(clean, want)
+    lanes_before = dict(g._graph_lanes)
+    assert len(lanes_before) == 3
+    Sink.fail_at = 3
+    with pytest.raises(_SinkBroke, match="frame 3"):
+        run()
+    assert len(written) == 3
+    assert gc.get_freeze_count() == 0
+    assert getattr(g, "noise_frame_offset", 0) == 0
+    ring_lock = render._RING_LOCKS[gpu.index]
+    assert ring_lock.acquire(blocking=False), "the failed render kept the device's ring lock"
+    ring_lock.release()
+    Sink.fail_at = None
+    assert run() == PIN_FRAMES
+    assert np.array_equal(np.stack(written), clean)
+    assert len(g._graph_lanes) == 3 and all(g._graph_lanes[k] is v for k, v in lanes_before.items()), "the lanes were captured again"
+
+
+def test_abandoned_synthesize_releases_its_lanes_and_restores_rewritten_weights(gpu, pinned_job):
+    """``synthesize`` closed after its first batch: a complete run of the same inputs afterwards gives the frames of a complete run made
+    before, on the same cached lanes.  And the eager path's half: abandoned after one batch with a rewrite of one conv weight applied,
+    it leaves the named parameter bit-equal to the original."""
+    from maua_stylegan2_amd import render
+
+    g, lat, noise, want = pinned_job
+    assert np.array_equal(_synthesized(render, g, lat, noise), want)
+    lanes_before = dict(g._graph_lanes)
+    assert len(lanes_before) == 3
+    run = render.synthesize(g, lat, noise, PIN_BATCH)
+    first, u8 = next(run)
+    assert first == 0 and u8 is lanes_before[(PIN_BATCH, 0, False)].u8
+    run.close()
+    assert np.array_equal(_synthesized(render, g, lat, noise), want)
+    assert len(g._graph_lanes) == 3 and all(g._graph_lanes[k] is v for k, v in lanes_before.items()), "the lanes were captured again"
+
+    class Scale(torch.nn.Module):
+        def __init__(self, m):
+            super().__init__()
+            self.m = float(m.mean())
+
+        def forward(self, w):
+            return w * self.m
+
+    original = g.convs[2].conv.weight.detach().clone()
+    mod = torch.linspace(1.5, 3.0, PIN_FRAMES)
+    run = render.synthesize(g, lat, noise, PIN_BATCH, rewrites={"convs.2.conv.weight": [lambda m: Scale(m), mod]})
+    first, u8 = next(run)
+    assert first == 0 and not torch.equal(g.convs[2].conv.weight, original)  # the first batch's rewrite is in place
+    run.close()
+    assert torch.equal(g.convs[2].conv.weight, original)
+    assert np.array_equal(_synthesized(render, g, lat, noise), want)
