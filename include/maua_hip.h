@@ -289,7 +289,11 @@ int maua_modconv_w2d_mtiles(int cin, int cout, int h, int w);
  * pre-scaled, see THE STYLE FOLD above);
  * d = demod [B,cout] (NULL = 1).  `ws` is a caller-owned fp32 workspace of at least maua_modconv_ws_floats()
  * floats used for split-K partial sums on small feature maps and, for up == 6, for the exported last input column [B, cin, H]
- * (may be NULL when that returns 0). */
+ * (may be NULL when that returns 0).
+ * MAUA_EINVAL besides null / non-positive arguments and the width rules above: a map whose staged patch fits no tile of the mode —
+ * up == 3 with W == 4, or with H <= 4 and W >= 20 (run up == 2 or 0 there); up == 4 where the (H+1) x (W/2+1) grid of position pairs
+ * is a single run (at most 128 pairs up to 32 output channels, 64 above: run up == 1).  Nothing is launched.  ModulatedConv2d.conv_mode
+ * never picks these; the low-resolution entries below pass the code on. */
 int64_t maua_modconv_ws_floats(int batch, int cin, int cout, int h, int w, int up);
 /* Name of the kernel template instance launched by the last modconv call of this process, as rocprofv3 prints it
  * ("modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP>") — the key of the per-instance PMC tables in profiles/. */

@@ -251,8 +251,17 @@ void modconv_mfma_kernel(ConvGeom g, ConvPtrs p) {
             const int tap = row / CC, c = row - tap * CC;
             const int ch = c0 + c, o = m0 + col;
             av[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (f < A_FLOATS / 4 && ch < g.Cin && o < g.CoutPad)
+            if (WINO && TM == 2 && g.CoutPad < 64) {
+                // A layer of <= 32 channels on a two-M-tile config (the fallback plan of a map too flat or too narrow for the 32-row
+                // tile's patch): its pack has 32 plain columns (wino_cout_pad), while the A reads below expect the [lane][m-tile]
+                // interleave.  Interleave here: tile column 2 l holds channel l, the odd columns (m-tile 1) are padding.
+                if (f < A_FLOATS / 4 && ch < g.Cin && col < 64) {
+                    const float* rowp = p.wp + ((size_t)tap * g.Cin + ch) * g.CoutPad;
+                    av[it] = f32x4{rowp[col >> 1], 0.f, rowp[(col >> 1) + 1], 0.f};
+                }
+            } else if (f < A_FLOATS / 4 && ch < g.Cin && o < g.CoutPad) {
                 av[it] = *reinterpret_cast<const f32x4*>(p.wp + ((size_t)tap * g.Cin + ch) * g.CoutPad + o);
+            }
         }
 #pragma unroll
         for (int i = 0; i < MAX_POS; ++i)
@@ -1232,7 +1241,8 @@ __global__ __launch_bounds__(256) void pack_weight_wino43_kernel(const float* __
                                 (g0 + 2.f * g1 + 4.f * g2) * (1.f / 24.f),
                                 (g0 - 2.f * g1 + 4.f * g2) * (1.f / 24.f),
                                 g2};
-            for (int xi = 0; xi < 6; ++xi) wq[((size_t)(ky * 6 + xi) * cin + i) * cout_pad + od] = u[xi];
+            // (padded columns hold +0.0, not the -0.0 that the negated sums of zeros would give)
+            for (int xi = 0; xi < 6; ++xi) wq[((size_t)(ky * 6 + xi) * cin + i) * cout_pad + od] = o < cout ? u[xi] : 0.f;
         }
     }
 }

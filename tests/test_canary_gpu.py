@@ -18,19 +18,11 @@ import pytest
 import torch
 
 from maua_stylegan2_amd import _lib, seeding
+from conv_ref import _direct_conv, _layer  # noqa: F401  (tests/test_frame_source_entries_gpu.py imports _layer from here)
 from redzone import Guard
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-
-
-def _layer(cin, cout, up, seed, dev):
-    from maua_stylegan2_amd.models.stylegan2 import ModulatedConv2d
-
-    r = np.random.default_rng(seed)
-    m = ModulatedConv2d(cin, cout, 3, 512, upsample=up)
-    m.weight.copy_(torch.from_numpy(r.standard_normal((1, cout, cin, 3, 3)).astype(np.float32)))
-    return m.to(dev), r
 
 
 def _packed(m, mode, g, name="wp"):
@@ -39,23 +31,9 @@ def _packed(m, mode, g, name="wp"):
     return g.inp(wp.reshape(-1), name)
 
 
-def _direct_conv(x, s, d, w, up):
-    """fp64 reference of the shared-weight formulation: conv(x * s, W) * wscale * d (transposed, stride 2, for up)."""
-    import torch.nn.functional as F
-
-    xs = (x * s[:, :, None, None]).double().cpu()
-    wd = w[0].double().cpu()
-    if up:
-        y = F.conv_transpose2d(xs, wd.transpose(0, 1), stride=2)
-    else:
-        y = F.conv2d(xs, wd, padding=1)
-    scale = 1.0 / np.sqrt(w.shape[2] * 9)
-    return (y * scale * d[:, :, None, None].double().cpu()).float()
-
-
 PLAIN = [  # (mode, cin, cout, h, w, batch)
     (0, 512, 512, 4, 4, 2),      # direct, split-K (the 4^2 layer of every generator): `ws` slabs
-    (0, 24, 40, 5, 7, 3),        # direct, odd everything: generic loads, ragged tiles
+    (0, 24, 40, 5, 7, 3),        # direct, odd map, four images per tile with three present; FAST loads (Cin % 8 == 0, 64 padded columns = the tile)
     (0, 512, 512, 8, 8, 8),      # the generator's 8^2 layer at the bench batch
     (2, 64, 64, 16, 34, 1),      # Winograd F(2,3): W even, not a multiple of the tile
     (2, 512, 512, 16, 16, 2),
@@ -98,7 +76,7 @@ def test_plain_conv_modes_stay_inside_their_buffers(gpu, mode, cin, cout, h, w, 
 
 UP = [  # (mode, cin, cout, h, w, batch)
     (1, 512, 512, 4, 4, 2),      # polyphase, split-K
-    (1, 24, 40, 5, 7, 3),        # generic loads, ragged
+    (1, 24, 40, 5, 7, 3),        # ragged 6 x 8 position grid on one 2-D tile; FAST loads (generic loads: tests/test_conv_instances_gpu.py)
     (4, 64, 32, 48, 96, 1),      # F(2,2) on the even x-phase
     (4, 128, 64, 64, 64, 2),
     (6, 4, 32, 8, 32, 1),        # F(2,2)^2, minimum: CC = 4, one K step; xcol export + edge lines
@@ -281,7 +259,7 @@ def test_partial_rgb_planes_stay_inside_their_buffers(gpu):
 
 LOWRES_UP = [  # (up, cin, cout, h, w, batch, noise_batch)
     (1, 512, 512, 4, 4, 8, 8),     # polyphase kernel, K split 32-fold: slabs, then reduce + blur + tail
-    (1, 24, 40, 5, 7, 3, 1),       # generic loads, ragged, K not split (one slab), shared noise
+    (1, 24, 40, 5, 7, 3, 1),       # ragged grid, FAST loads, K not split (one slab), shared noise
     (1, 512, 512, 8, 8, 2, 2),     # two flat runs per image
     (6, 8, 32, 16, 16, 1, 1),      # F(2,2)^2 on 16 x 16-position tiles, minimum: one K step, one slab; exported column + edge lines
     (6, 72, 96, 16, 16, 3, 0),     # nine K steps, three output-channel tiles, no noise

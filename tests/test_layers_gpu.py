@@ -176,12 +176,12 @@ def test_styled_conv_up_wide_vs_oracle(gpu):
 @pytest.mark.parametrize("cin,cout,h,w,batch", [
     (128, 128, 64, 64, 2),    # FAST path, whole tiles
     (256, 256, 32, 36, 1),    # ragged pair grid (18 pairs -> 2 tiles of 16), split-K
-    (136, 200, 40, 70, 3),    # Cout not a multiple of the 128-row weight tile, Cin % 4 == 0 only -> generic loads
+    (136, 200, 40, 70, 3),    # Cout not a multiple of the 128-row weight tile (padded to 256 columns), Cin % 4 == 0 only: still FAST loads
     (64, 160, 9, 34, 2),      # short map, several images... one image per tile, ragged rows
     (130, 128, 16, 32, 2),    # Cin % 4 != 0 -> generic path with a partial last chunk
     (32, 32, 72, 96, 2),      # 32-row weight tile (BM 32), 8-row tiles with a ragged last row block
     (64, 64, 48, 64, 1),      # 64-row weight tile
-    (24, 40, 20, 38, 2),      # generic path: Cin % 8 != 0, Cout not a multiple of 32
+    (24, 40, 20, 38, 2),      # 64-row tile with 40 channels (padded to 64), ragged pair grid; FAST loads (Cin % 8 == 0)
 ])
 def test_modconv_winograd_vs_oracle(gpu, cin, cout, h, w, batch):
     """Plain 3x3 layers with >= 128 output channels run the Winograd F(2,3) mode (mode 2 of maua_modconv3x3_f32);
@@ -218,7 +218,7 @@ def test_modconv_winograd_vs_oracle(gpu, cin, cout, h, w, batch):
 @pytest.mark.parametrize("cin,cout,h,w,batch", [
     (128, 128, 64, 64, 2),    # 128-row weight tile, FAST path, whole tiles
     (64, 64, 40, 128, 1),     # 64-row tile (TM 2 in one wave row), ragged row blocks
-    (136, 200, 24, 72, 2),    # generic loads: Cout not a multiple of the tile, ragged quads (18 per row -> 2 sub-tiles)
+    (136, 200, 24, 72, 2),    # Cout not a multiple of the tile (padded to 256 columns: FAST loads), ragged quads (18 per row -> 2 sub-tiles)
     (256, 256, 8, 64, 1),     # short map, split-K
     (32, 32, 48, 192, 2),     # 32-row weight tile (three patch slots per thread)
     (18, 32, 20, 68, 1),      # generic path at the 32-row tile: Cin % 4 != 0
@@ -558,7 +558,7 @@ def test_styledconv_rgbpart_lowres_equals_separate_launches_and_oracle(gpu, cin,
 @pytest.mark.parametrize("cin,cout,h,w,batch", [
     (128, 64, 64, 64, 2),     # 64-row tile, flat pair runs, FAST path
     (64, 32, 48, 96, 1),      # 32-row tile (three patch slots per thread)
-    (24, 72, 12, 20, 2),      # generic loads (Cin % 8 != 0), Cout not a multiple of the tile, small ragged grid
+    (24, 72, 12, 20, 2),      # generic loads (96 padded columns are no multiple of the 64-row tile), small ragged grid
     (512, 256, 16, 16, 1),    # split-K
     (64, 32, 130, 128, 1),    # large grid: the size at which the generator itself switches to mode 4
 ])
