@@ -298,6 +298,11 @@ int64_t maua_modconv_ws_floats(int batch, int cin, int cout, int h, int w, int u
 /* Name of the kernel template instance launched by the last modconv call of this process, as rocprofv3 prints it
  * ("modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP>") — the key of the per-instance PMC tables in profiles/. */
 int maua_modconv_last_instance(char* buf, int buf_len);
+/* The plan alone, for up == 0 .. 4: writes the name of the instance maua_modconv3x3_f32 would launch for this shape (the same host
+ * function picks it) and returns 0, or returns the code with which that call refuses the shape (MAUA_EINVAL: the width rules, more than
+ * 2^31 - 1 input elements, a patch that fits no tile of the mode; any other up is MAUA_EINVAL here).  Shapes only: no pointer is looked
+ * at, no HIP call is made, nothing needs a GPU.  The name does not depend on batch.  (Additive: the ABI version is unchanged.) */
+int maua_modconv_plan_instance(int batch, int cin, int cout, int h, int w, int up, char* buf, int buf_len);
 int maua_modconv3x3_f32(const float* x, const float* wp, const float* s, int s_stride, const float* d,
                         float* y, int batch, int cin, int cout, int h, int w, int up, float wscale, int fuse_act,
                         const float* noise, int64_t noise_batch_stride, const float* noise_w, const float* bias,

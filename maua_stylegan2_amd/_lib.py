@@ -116,6 +116,7 @@ _SIGNATURES = {
     "maua_modconv_w2d_mtiles": (c_int, [c_int] * 4),
     "maua_modconv_ws_floats": (c_int64, [c_int] * 6),
     "maua_modconv_last_instance": (c_int, [c_char_p, c_int]),
+    "maua_modconv_plan_instance": (c_int, [c_int] * 6 + [c_char_p, c_int]),
     "maua_modconv3x3_f32": (c_int, [_P, _P, _P, c_int, _P, _P] + [c_int] * 6 + [c_float, c_int, _P, c_int64, _P, _P, _P, _P, c_int, _P]),
     "maua_styledconv_torgb_f32": (c_int, [_P, _P, _P, c_int, _P, _P] + [c_int] * 6 + [c_float, _P, c_int64, _P, _P, _P, _P, c_float,
                                           _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P]),
@@ -239,6 +240,14 @@ def last_modconv_instance():
     buf = ctypes.create_string_buffer(128)
     check(load().maua_modconv_last_instance(buf, 128), "maua_modconv_last_instance")
     return buf.value.decode()
+
+
+def planned_modconv_instance(batch, cin, cout, h, w, mode):
+    """(rc, name): the instance maua_modconv3x3_f32 would launch for the shape in modes 0 .. 4 (rc 0), or its refusal (name None).
+    Shapes only, no launch: works without a GPU."""
+    buf = ctypes.create_string_buffer(128)
+    rc = load().maua_modconv_plan_instance(batch, cin, cout, h, w, mode, buf, 128)
+    return rc, (buf.value.decode() if rc == 0 else None)
 
 
 class HipEvent:

@@ -51,7 +51,7 @@ namespace {
 
 // channels per K chunk: the weight tile As[rows][CC][BM] is kept at <= 18..24 KB so that the double buffer fits 2-3x per CU
 constexpr int chunk_channels(int bm, int bn = 0, int mode = 0) {
-    if (mode == 3) return bm >= 128 ? 2 : 4;  // F(4,3): 18 weight rows per channel
+    if (mode == 3) return 4;  // F(4,3): 18 weight rows per channel (tiles of 32 and 64 rows only: see make_plan)
     return (bm >= 128 || bn >= 512) ? 4 : 8;
 }
 
@@ -1273,9 +1273,73 @@ inline int ilog2(int v) {
 }
 inline int pow2_ceil(int v) { return 1 << ilog2(v); }
 
+// ---- which instance a shape runs: ONE table of the instances the library holds, ONE host function that picks among them
+// The template arguments of an instance.  make_plan() derives the key of a shape; the table below finds its launcher.
+struct ConvKey {
+    int bm, bn, wm, mode;
+    bool multi, fast;
+    int maxp;
+    bool operator==(const ConvKey& o) const {
+        return bm == o.bm && bn == o.bn && wm == o.wm && mode == o.mode && multi == o.multi && fast == o.fast && maxp == o.maxp;
+    }
+};
+
+struct ConvInstance {
+    ConvKey key;
+    const char* name;  // as rocprofv3 prints it: bench.py and tests/golden/conv_instances.json join on it
+    int (*launch)(const char* name, int64_t blocks, size_t lds_bytes, hipStream_t st, const ConvGeom& g, const ConvPtrs& p);
+};
+
+// Rows (BM, BN, WM, MODE, MULTI, MAXP), each instantiated with FAST and without.  These are the keys make_plan() can return, no
+// others: tests/test_conv_instances_host.py enumerates the plan over the range its saturation argument (at make_plan) names and
+// tests/test_isa_checks.py compares the compiled set with the same table.  Why the other MULTI x MAXP combinations of a config cannot
+// occur is listed in DESIGN.md 4.0 (smallest / largest patch of each tile, flat runs hold one image).
+#define MAUA_CONV_BOTH(X, bm, bn, wm, mode, maxp) X(bm, bn, wm, mode, true, maxp) X(bm, bn, wm, mode, false, maxp)
+#define MAUA_CONV_ROWS(X)                                                                          \
+    MAUA_CONV_BOTH(X, 128, 128, 2, 0, 1) MAUA_CONV_BOTH(X, 128, 128, 2, 0, 2) /* direct 3x3 */     \
+    MAUA_CONV_BOTH(X, 64, 256, 1, 0, 2)                                                            \
+    MAUA_CONV_BOTH(X, 32, 256, 1, 0, 2)                                                            \
+    MAUA_CONV_BOTH(X, 32, 128, 1, 1, 1) MAUA_CONV_BOTH(X, 32, 128, 1, 1, 2)   /* transposed */     \
+    MAUA_CONV_BOTH(X, 64, 64, 2, 1, 1) X(64, 64, 2, 1, true, 2)                                    \
+    MAUA_CONV_BOTH(X, 128, 64, 2, 2, 1) MAUA_CONV_BOTH(X, 128, 64, 2, 2, 2)   /* F(2,3) */         \
+    MAUA_CONV_BOTH(X, 64, 128, 1, 2, 2)                                                            \
+    MAUA_CONV_BOTH(X, 32, 128, 1, 2, 2)                                                            \
+    MAUA_CONV_BOTH(X, 64, 128, 1, 3, 3)                                       /* F(4,3) */         \
+    MAUA_CONV_BOTH(X, 32, 128, 1, 3, 3)                                                            \
+    X(32, 128, 1, 4, false, 3) X(64, 64, 2, 4, false, 2)                      /* transposed + F(2,2): flat runs only */
+// The tile configs only the A/B bits of an experiments build select (g_conv_cfg), with every MULTI x MAXP their patch limit allows.
+#define MAUA_CONV_ROWS_EXPERIMENTS(X)                                                                          \
+    MAUA_CONV_BOTH(X, 32, 512, 1, 0, 1) MAUA_CONV_BOTH(X, 32, 512, 1, 0, 2) MAUA_CONV_BOTH(X, 32, 512, 1, 0, 3) \
+    MAUA_CONV_BOTH(X, 64, 128, 2, 0, 1) MAUA_CONV_BOTH(X, 64, 128, 2, 0, 2)                                     \
+    MAUA_CONV_BOTH(X, 32, 256, 1, 2, 1) MAUA_CONV_BOTH(X, 32, 256, 1, 2, 2) MAUA_CONV_BOTH(X, 32, 256, 1, 2, 3)
+#define MAUA_CONV_ENTRY1(BM, BN, WM, MODE, MULTI, FAST, MAXP)                                              \
+    {{BM, BN, WM, MODE, MULTI, FAST, MAXP}, "modconv_mfma_kernel<" #BM ", " #BN ", " #WM ", " #MODE ", " #MULTI ", " #FAST ", " #MAXP ">", \
+     &maua_launch_conv<modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP>, ConvGeom, ConvPtrs>},
+#define MAUA_CONV_ENTRY(BM, BN, WM, MODE, MULTI, MAXP) \
+    MAUA_CONV_ENTRY1(BM, BN, WM, MODE, MULTI, true, MAXP) MAUA_CONV_ENTRY1(BM, BN, WM, MODE, MULTI, false, MAXP)
+const ConvInstance kConvInstances[] = {
+    MAUA_CONV_ROWS(MAUA_CONV_ENTRY)
+#ifdef MAUA_EXPERIMENTS
+    MAUA_CONV_ROWS_EXPERIMENTS(MAUA_CONV_ENTRY)
+#endif
+};
+
+const ConvInstance* find_instance(const ConvKey& key) {
+    for (const ConvInstance& inst : kConvInstances)
+        if (inst.key == key) return &inst;
+    return nullptr;
+}
+
+// Floats per channel the staged patch of a config may hold.  A thread stages MAXP positions of it (PSTRIDE <= 256 MAXP); the instances
+// with MAXP = 3 exist for the wide-N configs only.
+constexpr int patch_limit(int mode, int bn) {
+    return (bn >= 512 || (mode == 2 && bn >= 256) || ((mode == 3 || mode == 4) && bn >= 128)) ? 768 : 512;
+}
+
 struct Plan {
-    int bm, bn, wm;
-    bool fallback = false;
+    ConvKey key;               // the instance; tile config = key.bm x key.bn, key.wm wave rows
+    const ConvInstance* inst;  // its table entry (null: rc != 0)
+    int rc;                    // 0, or why no launch serves the shape (MAUA_EINVAL: refused; MAUA_ENOSYS: no such instance in this build)
     ConvGeom g;
     size_t lds_bytes;
     int64_t blocks;
@@ -1287,37 +1351,57 @@ int g_conv_debug = 0;
 int g_conv_cfg = 0;  // tuning key 2: bit0 -> Cout<=64 uses 64x128 (WM 2); bit1 -> Cout<=32 uses 32x512; bit2 -> no flat runs
 #endif
 
-// Tile-shape selection (host).  BM follows Cout; the pixel tile is a stack of 32-pixel MFMA groups.
-// mode 0 plain, 1 transposed stride 2, 2 plain through Winograd F(2,3) along x (needs an even width)
+// Shape -> instance, geometry, grid and LDS size (host; positive sizes, mode 0 .. 4).  BM follows Cout; the pixel tile is a stack of
+// 32-pixel MFMA groups.  mode 0 plain, 1 transposed stride 2, 2 / 3 plain through Winograd F(2,3) / F(4,3) along x, 4 transposed with
+// F(2,2) on the even x-phase.  Every refusal of a shape is decided here (Plan::rc); the geometry is filled in either way, so that
+// maua_modconv_ws_floats answers for any shape.
+//
+// What the key sees of a shape (why a bounded enumeration of shapes reaches every key, tests/test_conv_instances_host.py):
+//   * cin only as "a multiple of the K chunk (4 or 8)", cout as <= 32 / <= 64 / above and as "CoutPad a multiple of BM"; batch not at all:
+//     MULTI is "the tile has room for several images" (ni > 1), a property of the map, and the patch is sized for ni images whether
+//     the batch fills them or not;
+//   * h and w through the position grid GH x GW (w, w / 2, w / 4, h + 1, w + 1, w / 2 + 1) and that grid only through pow2_ceil() of
+//     itself or of its quotient by a power of two, each capped by the tile: a sub-tile is at most 32 positions wide, a tile at most 16
+//     sub-tiles (BN <= 512).  So a key changes with h or w only where a grid dimension passes a power of two, and not beyond
+//     GW = 32 x 16 (w = 4 x 512 in mode 3) or GH = 32 x 16: every h in 1 .. 139 and w in 1 .. 299 plus 2^k - 1, 2^k, 2^k + 1 (and the
+//     next even width and multiple of four) up to 1025 and two sizes beyond it cover every threshold;
+//   * as GH GW > BN (flat runs), with BN <= 128 in the transposed modes: a flat run's geometry depends on BN alone (and its patch,
+//     2 (BN + 2) or 2 (2 BN + 2) floats, is inside the limit: a flat run never falls back), and the maps that are not flat have
+//     (h + 1) (w + 1) <= 128, in mode 4 (h + 1) (w / 2 + 1) <= 128: w <= 126, inside the dense range;
+//   * as the width rules of modes 2, 3 and 4, and as the 2^31 element limit (a refusal, not a key).
 Plan make_plan(int batch, int cin, int cout, int h, int w, int mode) {
     Plan pl{};
+    ConvKey& k = pl.key;
     ConvGeom& g = pl.g;
     const bool up = mode == 1 || mode == 4, uw = mode == 4, wino = mode == 2 || mode == 3, w43 = mode == 3;
     const int wx = w43 ? 4 : 2;  // outputs per Winograd position
+    k.mode = mode;
+    if ((int64_t)batch * cin * h * w > 0x7fffffffLL) pl.rc = MAUA_EINVAL;                             // 32-bit patch offsets
+    if (((mode == 2 || mode == 4) && (w & 1)) || (mode == 3 && (w & 3))) pl.rc = MAUA_EINVAL;         // whole output pairs / quads
     g.B = batch, g.Cin = cin, g.Cout = cout, g.CoutPad = wino ? wino_cout_pad(cout) : pad32(cout), g.H = h, g.W = w;
     if (w43) {
         g.GH = h, g.GW = w / 4, g.OH = h, g.OW = w;  // positions are output quads
-        if (cout <= 32) pl.bm = 32, pl.wm = 1, pl.bn = 128;
-        else pl.bm = 64, pl.wm = 1, pl.bn = 128;  // (a 128-row tile holds 192 accumulator registers per wave as well, but its
-                                                  // 18-row weight tile only leaves room for 2-channel chunks: 4-7 % slower)
+        if (cout <= 32) k.bm = 32, k.wm = 1, k.bn = 128;
+        else k.bm = 64, k.wm = 1, k.bn = 128;  // (a 128-row tile holds 192 accumulator registers per wave as well, but its 18-row weight
+                                               // tile only leaves room for 2-channel chunks: 4-7 % slower.  Dropped, with its chunk size.)
     } else if (wino) {
         g.GH = h, g.GW = w / 2, g.OH = h, g.OW = w;  // positions are output pairs
-        if (cout <= 32) pl.bm = 32, pl.wm = 1, pl.bn = MAUA_CFG(2) ? 256 : 128;
-        else if (cout <= 64) pl.bm = 64, pl.wm = 1, pl.bn = 128;
-        else pl.bm = 128, pl.wm = 2, pl.bn = 64;
+        if (cout <= 32) k.bm = 32, k.wm = 1, k.bn = MAUA_CFG(2) ? 256 : 128;
+        else if (cout <= 64) k.bm = 64, k.wm = 1, k.bn = 128;
+        else k.bm = 128, k.wm = 2, k.bn = 64;
     } else if (uw) {
         g.GH = h + 1, g.GW = w / 2 + 1, g.OH = 2 * h + 1, g.OW = 2 * w + 1;  // positions are pairs; W + 2 positions per row
-        if (cout <= 32) pl.bm = 32, pl.wm = 1, pl.bn = 128;
-        else pl.bm = 64, pl.wm = 2, pl.bn = 64;
+        if (cout <= 32) k.bm = 32, k.wm = 1, k.bn = 128;
+        else k.bm = 64, k.wm = 2, k.bn = 64;
     } else if (up) {
         g.GH = h + 1, g.GW = w + 1, g.OH = 2 * h + 1, g.OW = 2 * w + 1;
-        if (cout <= 32) pl.bm = 32, pl.wm = 1, pl.bn = 128;
-        else pl.bm = 64, pl.wm = 2, pl.bn = 64;
+        if (cout <= 32) k.bm = 32, k.wm = 1, k.bn = 128;
+        else k.bm = 64, k.wm = 2, k.bn = 64;
     } else {
         g.GH = h, g.GW = w, g.OH = h, g.OW = w;
-        if (cout <= 32) pl.bm = 32, pl.wm = 1, pl.bn = MAUA_CFG(2) ? 512 : 256;
-        else if (cout <= 64) pl.bm = 64, pl.wm = MAUA_CFG(1) ? 2 : 1, pl.bn = MAUA_CFG(1) ? 128 : 256;
-        else pl.bm = 128, pl.wm = 2, pl.bn = 128;
+        if (cout <= 32) k.bm = 32, k.wm = 1, k.bn = MAUA_CFG(2) ? 512 : 256;
+        else if (cout <= 64) k.bm = 64, k.wm = MAUA_CFG(1) ? 2 : 1, k.bn = MAUA_CFG(1) ? 128 : 256;
+        else k.bm = 128, k.wm = 2, k.bn = 128;
     }
     auto shape = [&](int bn) {
         const int nsub = bn / 32;
@@ -1343,30 +1427,35 @@ Plan make_plan(int batch, int cin, int cout, int h, int w, int mode) {
         }
         g.PSTRIDE = ni * g.PH * g.PWS;
     };
-    shape(pl.bn);
-    if (up && g.GH * g.GW > pl.bn && !MAUA_CFG(4)) {
+    shape(k.bn);
+    if (up && g.GH * g.GW > k.bn && !MAUA_CFG(4)) {
         // The (H+1)x(W+1) position grid never fits power-of-two 2-D tiles (29 % idle MFMA columns at 65x65); tiles are
         // instead runs of BN consecutive positions of the flattened grid, one image each.  A position reads inputs
         // p, p-1, p-GW, p-GW-1 of the pitch-GW flattened (zero-padded) input: two runs of BN+1 floats per channel.
         // (From two runs per image on — round 6: the 9 x 9 grid of the 8^2 -> 16^2 layer took 16 x 16 = 256 slots as a 2-D tile, 32 % of its
         // MFMA columns useful; as two runs of 64 it is 63 %.)
         g.flat = 1;
-        g.lsw = 5, g.lsh = 0, g.lnsx = ilog2(pl.bn / 32), g.lnsy = 0, g.lni = 0;
-        g.tiles_x = ceil_div(g.GH * g.GW, pl.bn), g.tiles_y = 1, g.img_groups = batch;
-        g.PH = 2, g.PW = (uw ? 2 : 1) * pl.bn + 1, g.PWS = (uw ? 2 : 1) * pl.bn + 2;
+        g.lsw = 5, g.lsh = 0, g.lnsx = ilog2(k.bn / 32), g.lnsy = 0, g.lni = 0;
+        g.tiles_x = ceil_div(g.GH * g.GW, k.bn), g.tiles_y = 1, g.img_groups = batch;
+        g.PH = 2, g.PW = (uw ? 2 : 1) * k.bn + 1, g.PWS = (uw ? 2 : 1) * k.bn + 2;
         g.PSTRIDE = g.PH * g.PWS;
     }
-    if (g.PSTRIDE > ((pl.bn >= 512 || (wino && pl.bn >= 256) || ((w43 || uw) && pl.bn >= 128)) ? 768 : 512)) {  // tiny feature maps under a wide-N config: fall back to the 128-pixel tile
-        if (w43) pl.bm = 64, pl.wm = 1, pl.bn = 128;
-        else if (wino) pl.bm = 128, pl.wm = 2, pl.bn = 64;
-        else if (up) pl.bm = 64, pl.wm = 2, pl.bn = 64;
-        else pl.bm = 128, pl.wm = 2, pl.bn = 128;
-        shape(pl.bn);
-        pl.fallback = true;
+    if (g.PSTRIDE > patch_limit(mode, k.bn)) {  // tiny feature maps under a wide-N config: fall back to the 128-pixel tile
+        if (w43) k.bm = 64, k.wm = 1, k.bn = 128;
+        else if (wino) k.bm = 128, k.wm = 2, k.bn = 64;
+        else if (up) k.bm = 64, k.wm = 2, k.bn = 64;
+        else k.bm = 128, k.wm = 2, k.bn = 128;
+        shape(k.bn);
     }
-    const int CC = chunk_channels(pl.bm, pl.bn, mode);
+    if (uw && !g.flat) pl.rc = MAUA_EINVAL;                        // mode 4 has no 2-D tiles: grids too small for flat pair runs use mode 1
+    if (g.PSTRIDE > patch_limit(mode, k.bn)) pl.rc = MAUA_EINVAL;  // no tile of the mode holds this map's patch
+    const int CC = chunk_channels(k.bm, k.bn, mode);
+    k.multi = g.lni > 0;
+    k.fast = cin % CC == 0 && g.CoutPad % k.bm == 0;
+    k.maxp = g.PSTRIDE <= 256 ? 1 : (g.PSTRIDE <= 512 ? 2 : 3);
+    if (!pl.rc && !(pl.inst = find_instance(k))) pl.rc = MAUA_ENOSYS;
     g.n_chunks = ceil_div(cin, CC);
-    g.m_tiles = ceil_div(g.CoutPad, pl.bm);
+    g.m_tiles = ceil_div(g.CoutPad, k.bm);
     g.n_tiles = g.tiles_x * g.tiles_y * g.img_groups;
     // split-K until the grid covers the chip ~2x (256 CUs), never below 2 chunks per split
     const int64_t base_blocks = (int64_t)g.m_tiles * g.n_tiles;
@@ -1377,38 +1466,11 @@ Plan make_plan(int batch, int cin, int cout, int h, int w, int mode) {
     g.splits = ceil_div(g.n_chunks, g.chunks_per_split);
     g.ws_slab = (int64_t)batch * cout * g.OH * g.OW;
     pl.blocks = base_blocks * g.splits;
-    pl.lds_bytes = 2 * ((size_t)(w43 ? 18 : (wino || uw) ? 12 : 9) * CC * pl.bm + (size_t)CC * g.PSTRIDE) * sizeof(float);
+    pl.lds_bytes = 2 * ((size_t)(w43 ? 18 : (wino || uw) ? 12 : 9) * CC * k.bm + (size_t)CC * g.PSTRIDE) * sizeof(float);
     if (g.lni == 0)  // the DMA patch path also stages the styles of one image
         pl.lds_bytes += (size_t)cin * sizeof(float);
-    if (pl.lds_bytes < (size_t)2 * pl.bm * sizeof(float)) pl.lds_bytes = (size_t)2 * pl.bm * sizeof(float);
+    if (pl.lds_bytes < (size_t)2 * k.bm * sizeof(float)) pl.lds_bytes = (size_t)2 * k.bm * sizeof(float);
     return pl;
-}
-
-template <int BM, int BN, int WM, int UP, bool MULTI, bool FAST, int MAXP>
-int launch_conv_impl2(const Plan& pl, const ConvPtrs& ptrs, hipStream_t st) {
-    char name[96];
-    snprintf(name, sizeof(name), "modconv_mfma_kernel<%d, %d, %d, %d, %s, %s, %d>", BM, BN, WM, UP, MULTI ? "true" : "false",
-             FAST ? "true" : "false", MAXP);
-    return maua_launch_conv<modconv_mfma_kernel<BM, BN, WM, UP, MULTI, FAST, MAXP>>(name, pl.blocks, pl.lds_bytes, st, pl.g, ptrs);
-}
-
-template <int BM, int BN, int WM, int UP, bool MULTI, bool FAST>
-int launch_conv_impl(const Plan& pl, const ConvPtrs& ptrs, hipStream_t st) {
-    if (pl.g.PSTRIDE <= 256) return launch_conv_impl2<BM, BN, WM, UP, MULTI, FAST, 1>(pl, ptrs, st);
-    constexpr bool WIDE = BN >= 512 || (UP == 2 && BN >= 256) || ((UP == 3 || UP == 4) && BN >= 128);  // configs whose patch can exceed 512 floats per channel
-    if (pl.g.PSTRIDE <= 512 || !WIDE) return launch_conv_impl2<BM, BN, WM, UP, MULTI, FAST, 2>(pl, ptrs, st);
-    return launch_conv_impl2<BM, BN, WM, UP, MULTI, FAST, (WIDE ? 3 : 2)>(pl, ptrs, st);
-}
-
-template <int BM, int BN, int WM, int UP>
-int launch_conv(const Plan& pl, const ConvPtrs& ptrs, hipStream_t st) {
-    constexpr int CC = chunk_channels(BM, BN, UP);
-    if (pl.g.PSTRIDE > 768) return MAUA_EINVAL;
-    const bool fast = (pl.g.Cin % CC == 0) && (pl.g.CoutPad % BM == 0);
-    if (pl.g.lni > 0) return fast ? launch_conv_impl<BM, BN, WM, UP, true, true>(pl, ptrs, st)
-                                  : launch_conv_impl<BM, BN, WM, UP, true, false>(pl, ptrs, st);
-    return fast ? launch_conv_impl<BM, BN, WM, UP, false, true>(pl, ptrs, st)
-                : launch_conv_impl<BM, BN, WM, UP, false, false>(pl, ptrs, st);
 }
 
 }  // namespace
@@ -1467,6 +1529,15 @@ extern "C" int maua_modconv_last_instance(char* buf, int buf_len) {
     return 0;
 }
 
+// The plan without a launch: which instance maua_modconv3x3_f32 would run for this shape, or the shape's refusal.  No HIP call.
+extern "C" int maua_modconv_plan_instance(int batch, int cin, int cout, int h, int w, int up, char* buf, int buf_len) {
+    if (!buf || buf_len <= 0 || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || up < 0 || up > 4) return MAUA_EINVAL;
+    const Plan pl = make_plan(batch, cin, cout, h, w, up);
+    if (pl.rc) return pl.rc;
+    snprintf(buf, (size_t)buf_len, "%s", pl.inst->name);
+    return 0;
+}
+
 namespace {
 int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, const float* d, float* y, int batch,
                  int cin, int cout, int h, int w, int up, float wscale, int fuse_act, const TailArgs& tail, float* ws, const RgbArgs* rgb,
@@ -1490,10 +1561,10 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
         if (fuse_act || rgb) return MAUA_EINVAL;
         return maua_up2d_launch(x, wp, s, s_stride, d, y, ws, batch, cin, cout, h, w, wscale, stream);
     }
-    if ((int64_t)batch * cin * h * w > 0x7fffffffLL) return MAUA_EINVAL;  // 32-bit patch offsets
-    if (up < 0 || up > 4 || ((up == 2 || up == 4) && (w & 1)) || (up == 3 && (w & 3))) return MAUA_EINVAL;
+    if (up < 0 || up > 4) return MAUA_EINVAL;
     if (up == 4 && (fuse_act || rgb)) return MAUA_EINVAL;  // raw output only: the blur kernel applies the tail
     Plan pl = make_plan(batch, cin, cout, h, w, up);
+    if (pl.rc) return pl.rc;  // the shape's own refusals (width rules, 2^31 elements, no tile for its patch) and a key without instance
     if (pl.g.splits > 1 && !ws) return MAUA_EINVAL;
     pl.g.force_ws = partial_splits ? 1 : 0;
     pl.g.s_stride = s_stride;
@@ -1509,7 +1580,7 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
     if (rgb) {
         // fusable only when one workgroup holds every channel of its pixels in a single wave row (BM >= Cout, WM == 1),
         // no split-K, one image per tile, the tail fused
-        const bool ok = up != 1 && up != 4 && fuse_act && pl.wm == 1 && pl.g.m_tiles == 1 && pl.g.splits == 1 && pl.g.lni == 0 &&
+        const bool ok = up != 1 && up != 4 && fuse_act && pl.key.wm == 1 && pl.g.m_tiles == 1 && pl.g.splits == 1 && pl.g.lni == 0 &&
                         rgb->w && rgb->s && rgb->bias && (rgb->out || rgb->u8) && (!rgb->skip || (rgb->k4 && !(h & 1) && !(w & 1)));
         if (!ok) return MAUA_ENOSYS;
         pl.g.rgb = rgb->mode;
@@ -1518,31 +1589,7 @@ int modconv_impl(const float* x, const float* wp, const float* s, int s_stride, 
         ptrs.rgb_k4 = rgb->k4, ptrs.rgb_out = rgb->out, ptrs.rgb_u8 = rgb->u8;
     }
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (up == 4) {
-        if (!pl.g.flat || pl.fallback) return MAUA_EINVAL;  // grids too small for flat pair runs use mode 1
-        if (pl.bm == 32) rc = launch_conv<32, 128, 1, 4>(pl, ptrs, st);
-        else rc = launch_conv<64, 64, 2, 4>(pl, ptrs, st);
-    } else if (up == 3) {
-        if (pl.bm == 32) rc = launch_conv<32, 128, 1, 3>(pl, ptrs, st);
-        else rc = launch_conv<64, 128, 1, 3>(pl, ptrs, st);
-    } else if (up == 2) {
-        if (pl.bm == 32 && pl.bn == 256) rc = launch_conv<32, 256, 1, 2>(pl, ptrs, st);
-        else if (pl.bm == 32) rc = launch_conv<32, 128, 1, 2>(pl, ptrs, st);
-        else if (pl.bm == 64) rc = launch_conv<64, 128, 1, 2>(pl, ptrs, st);
-        else rc = launch_conv<128, 64, 2, 2>(pl, ptrs, st);
-    } else if (up == 1) {
-        if (pl.fallback) rc = launch_conv<64, 64, 2, 1>(pl, ptrs, st);
-        else if (pl.bm == 32) rc = launch_conv<32, 128, 1, 1>(pl, ptrs, st);
-        else rc = launch_conv<64, 64, 2, 1>(pl, ptrs, st);
-    } else {
-        if (pl.bm == 32 && pl.bn == 512) rc = launch_conv<32, 512, 1, 0>(pl, ptrs, st);
-        else if (pl.bm == 32) rc = launch_conv<32, 256, 1, 0>(pl, ptrs, st);
-        else if (pl.bm == 64 && pl.bn == 128) rc = launch_conv<64, 128, 2, 0>(pl, ptrs, st);
-        else if (pl.bm == 64) rc = launch_conv<64, 256, 1, 0>(pl, ptrs, st);
-        else rc = launch_conv<128, 128, 2, 0>(pl, ptrs, st);
-    }
-    if (rc) return rc;
+    if (int rc = pl.inst->launch(pl.inst->name, pl.blocks, pl.lds_bytes, st, pl.g, ptrs)) return rc;
     if (partial_splits) {
         *partial_splits = pl.g.splits;
         return 0;

@@ -1,10 +1,11 @@
 """GPU: every instance of modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP> (csrc/modconv.hip) a call can reach, launched through
 the C ABI at the smallest shape that reaches it, between red zones, against the fp64 direct convolution with a per-element bound.
 
-The rows come from tests/golden/conv_instances.json, which tools/conv_instance_sweep.py writes on the GPU: it walks a grid of small shapes
-through maua_modconv3x3_f32 and keeps the cheapest shape per name reported by maua_modconv_last_instance.  Every case asserts that its
-shape still reaches the recorded name, so the coverage claim cannot rot silently (a change of make_plan() shows up here and, without a
-GPU, in tests/test_conv_instances_host.py).
+The rows come from tests/golden/conv_instances.json, which tools/conv_instance_sweep.py writes on the CPU: it walks a grid of small shapes
+through maua_modconv_plan_instance (the plan maua_modconv3x3_f32 dispatches through, without the launch) and keeps the cheapest shape per
+name.  Every case asserts that the launch of its shape reports the recorded name (maua_modconv_last_instance), so the coverage claim
+cannot rot silently; without a GPU, tests/test_conv_instances_host.py asserts the same names on the plan, that an enumeration of the plan
+reaches no name outside the table, and tests/test_isa_checks.py that the library compiles exactly the table's instances.
 
 Every case: the weight is packed by the library's own pack entry straight into a guarded window of exactly the documented size
 (9 cin pad32(cout) floats for modes 0 and 1, 12 cin P for mode 2, 18 cin P for mode 3, 12 cin pad32(cout) for mode 4; P = cout padded to

@@ -1,6 +1,10 @@
 """CPU: the instance table of the generic convolution kernel (tests/golden/conv_instances.json, written by tools/conv_instance_sweep.py)
-against what the library answers without a GPU.  A change of make_plan() that moves a recorded shape to another split-K layout shows up
-here as a different maua_modconv_ws_floats; the GPU test (tests/test_conv_instances_gpu.py) asserts the instance names themselves."""
+against what the library answers without a GPU.  maua_modconv_plan_instance is the plan maua_modconv3x3_f32 dispatches through, called
+without a launch: every row's name is what the plan gives for its shape, an enumeration of the plan over a range that saturates it
+(the comment at make_plan, csrc/modconv.hip, says why) reaches the table's 58 names and no other, and a change of make_plan() that
+moves a recorded shape to another split-K layout shows up as a different maua_modconv_ws_floats.  The GPU test
+(tests/test_conv_instances_gpu.py) launches the rows and asserts the same names on what really ran."""
+import ctypes
 import json
 import os
 import re
@@ -44,6 +48,63 @@ def test_rows_are_distinct_well_formed_and_obey_the_argument_rules():
 @pytest.mark.parametrize("row", ROWS, ids=lambda r: re.sub(r"[^0-9a-z]+", "_", r["name"][20:-1]))
 def test_workspace_size_of_every_row_is_the_recorded_one(lib, row):
     assert lib.maua_modconv_ws_floats(row["batch"], row["cin"], row["cout"], row["h"], row["w"], row["mode"]) == row["ws_floats"]
+
+
+def plan(lib, batch, cin, cout, h, w, mode):
+    from maua_stylegan2_amd import _lib
+
+    return _lib.planned_modconv_instance(batch, cin, cout, h, w, mode)
+
+
+@pytest.mark.parametrize("row", ROWS, ids=lambda r: re.sub(r"[^0-9a-z]+", "_", r["name"][20:-1]))
+def test_plan_gives_the_recorded_name_of_every_row(lib, row):
+    assert plan(lib, row["batch"], row["cin"], row["cout"], row["h"], row["w"], row["mode"]) == (0, row["name"])
+
+
+ENUM_COUT = (8, 32, 40, 64, 72, 96, 128)
+ENUM_CIN = (3, 8)
+ENUM_H = tuple(range(1, 140)) + (255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2048, 4096)
+ENUM_W = tuple(range(1, 300)) + (511, 512, 513, 514, 516, 1023, 1024, 1025, 1026, 1028, 2048, 4096)
+
+
+def test_enumerated_plan_reaches_exactly_the_table(lib):
+    """Every name the plan can answer is a row of the table (so every compiled instance is tested on the GPU) and every row is reached.
+    The plan refuses some of these shapes (MAUA_EINVAL: no tile of modes 3 / 4 holds the patch); it never answers MAUA_ENOSYS, i.e. it
+    never asks for an instance the library does not hold."""
+    buf = ctypes.create_string_buffer(128)
+    fn = lib.maua_modconv_plan_instance
+    seen, codes = set(), set()
+    for mode in range(5):
+        widths = [w for w in ENUM_W if not ((mode in (2, 4) and w % 2) or (mode == 3 and w % 4))]
+        for cout in ENUM_COUT:
+            for cin in ENUM_CIN:
+                for h in ENUM_H:
+                    for w in widths:
+                        rc = fn(1, cin, cout, h, w, mode, buf, 128)
+                        if rc == 0:
+                            seen.add(buf.value)
+                        else:
+                            codes.add(rc)
+    assert codes <= {-22}, codes
+    assert {n.decode() for n in seen} == {r["name"] for r in ROWS}
+
+
+def test_plan_does_not_depend_on_batch(lib):
+    shapes = [(r["cin"], r["cout"], r["h"], r["w"], r["mode"]) for r in ROWS[::7]]
+    shapes += [(512, 512, 4, 4, 0), (512, 512, 4, 4, 1), (512, 512, 8, 8, 2), (64, 32, 16, 16, 3), (64, 64, 16, 66, 4), (3, 3, 1, 4, 3)]
+    for cin, cout, h, w, mode in shapes:
+        first = plan(lib, 1, cin, cout, h, w, mode)
+        assert first[0] in (0, -22)
+        assert plan(lib, 3, cin, cout, h, w, mode) == first and plan(lib, 8, cin, cout, h, w, mode) == first, (cin, cout, h, w, mode)
+
+
+def test_plan_entry_refuses_what_the_call_refuses(lib):
+    """Width rules, the 2^31 element limit, modes outside 0 .. 4 and bad arguments: MAUA_EINVAL, as maua_modconv3x3_f32 (tests/test_abi.py)."""
+    assert plan(lib, 1, 64, 64, 64, 63, 2)[0] == -22 and plan(lib, 1, 64, 64, 64, 66, 3)[0] == -22 and plan(lib, 1, 64, 64, 64, 63, 4)[0] == -22
+    assert plan(lib, 1, 64, 64, 4, 4, 4)[0] == -22                                   # grid too small for flat pair runs
+    assert plan(lib, 1, 8, 8, 1 << 14, 1 << 14, 0)[0] == -22 and plan(lib, 1, 7, 8, 1 << 14, 1 << 14, 0)[0] == 0
+    assert plan(lib, 1, 64, 64, 64, 64, 5)[0] == -22 and plan(lib, 1, 64, 64, 64, 64, -1)[0] == -22 and plan(lib, 0, 64, 64, 64, 64, 0)[0] == -22
+    assert lib.maua_modconv_plan_instance(1, 64, 64, 64, 64, 0, None, 128) == -22
 
 
 def test_rounding_ratios_are_recorded_and_sane():

@@ -3,6 +3,7 @@
 Why they exist: in round 3 a prologue change made the compiler treat a buffer resource descriptor as divergent; every LDS-DMA
 instruction of the K loop was then wrapped in a waterfall loop (v_readfirstlane x4 + compare + s_and_saveexec), +25 % VALU per K step
 and -6 % on the whole plain-layer family, with every parity test still green.  Nothing but the ISA shows that."""
+import json
 import os
 import re
 import subprocess
@@ -14,6 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 SOURCES = ("modconv_w2d", "modconv_up2d")
 STREAMING = ("upfirdn2d",)  # HBM-bound kernels: no LDS-DMA, but a spill or a scratch array there is HBM traffic the roofline does not count
+GENERIC = ("modconv",)  # the generic convolution kernel: which instances the product build holds, and that the FAST ones do not spill
 
 
 @pytest.fixture(scope="module")
@@ -28,8 +30,8 @@ def device_asm(tmp_path_factory):
                         f"{REPO}/maua_stylegan2_amd/csrc/{name}.hip", "-o", dst], check=True, capture_output=True)
         return name, open(dst).read()
 
-    with ThreadPoolExecutor(len(SOURCES + STREAMING)) as pool:
-        return dict(pool.map(build, SOURCES + STREAMING))
+    with ThreadPoolExecutor(len(SOURCES + STREAMING + GENERIC)) as pool:
+        return dict(pool.map(build, SOURCES + STREAMING + GENERIC))
 
 
 @pytest.mark.parametrize("name", SOURCES)
@@ -81,6 +83,29 @@ def test_hot_kernels_use_no_scratch_memory(device_asm, name):
     sizes = _per_kernel(device_asm[name], "private_segment_fixed_size")
     for kernel, size in sizes.items():
         assert size <= (FUSED_LIMITS["scratch"] if FUSED in kernel else 0), (kernel, size)
+
+
+def test_generic_conv_kernel_compiled_set_is_the_instance_table(device_asm):
+    """csrc/modconv.hip instantiates modconv_mfma_kernel from one table (MAUA_CONV_ROWS); the product build must hold exactly the 58
+    instances of tests/golden/conv_instances.json — the ones the plan can reach (tests/test_conv_instances_host.py enumerates it) and
+    the GPU test launches — so no kernel is compiled that no call runs, and none is tested that is not compiled.  The FAST instances
+    (channel counts in whole K chunks and weight tiles: every layer of a real generator) keep everything in registers; the ragged-channel
+    instances carry 12 .. 196 bytes of scratch for their masked loads and are not held to that."""
+    table = json.load(open(os.path.join(REPO, "tests", "golden", "conv_instances.json")))["instances"]
+    mangled = re.compile(r"modconv_mfma_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELb([01])ELi(\d+)EE")
+
+    def demangled(symbol):
+        bm, bn, wm, mode, multi, fast, maxp = mangled.search(symbol).groups()
+        return f"modconv_mfma_kernel<{bm}, {bn}, {wm}, {mode}, {('false', 'true')[int(multi)]}, {('false', 'true')[int(fast)]}, {maxp}>"
+
+    spills = _per_kernel(device_asm["modconv"], "vgpr_spill_count")
+    scratch = _per_kernel(device_asm["modconv"], "private_segment_fixed_size")
+    symbols = [k for k in spills if "modconv_mfma_kernel" in k]
+    assert sorted(demangled(k) for k in symbols) == sorted(r["name"] for r in table) and len(symbols) == 58
+    fast = [k for k in symbols if mangled.search(k).group(6) == "1"]
+    assert len(fast) == 29
+    for k in fast:
+        assert spills[k] == 0 and scratch[k] == 0, (demangled(k), spills[k], scratch[k])
 
 
 def test_fused_kernel_spills_stay_outside_the_k_loop(device_asm):

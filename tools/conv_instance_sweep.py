@@ -3,14 +3,15 @@
 smallest shape?  -> tests/golden/conv_instances.json, the table tests/test_conv_instances_gpu.py and tests/test_conv_instances_host.py
 are parametrised over.
 
-    python tools/conv_instance_sweep.py            # on the GPU: walk the grid, record one row per distinct instance
+    python tools/conv_instance_sweep.py            # on the CPU: walk the grid, record one row per distinct instance
     python tools/conv_instance_sweep.py --ratios   # on the CPU: measure the rounding amplification of modes 2 / 3 / 4 into the same file
 
-The sweep launches maua_modconv3x3_f32 for modes 0 .. 4 over a grid of small shapes (aligned and ragged channel counts, maps from one
-pixel to a few tile widths, widths odd, 2 mod 4 and just over 32 / 64 / 128, batches 1, 2, 3, 5, 8), asks the library which instance
-ran (maua_modconv_last_instance: names are discovered by launching, nothing re-implements the plan) and keeps the cheapest shape
-(batch * cin * cout * h * w) per name.  It stops at the first non-zero return code or HIP error.  Run it as ONE process under one
-`timeout`; operands live in buffers sized for the largest shape of the grid, allocated once.
+The sweep asks the library's plan (maua_modconv_plan_instance: the host function maua_modconv3x3_f32 itself dispatches through, called
+without a launch, so nothing here re-implements it) for modes 0 .. 4 over a grid of small shapes (aligned and ragged channel counts,
+maps from one pixel to a few tile widths, widths odd, 2 mod 4 and just over 32 / 64 / 128, batches 1, 2, 3, 5, 8) and keeps the
+cheapest shape (batch * cin * cout * h * w) per name.  A shape the plan refuses (MAUA_EINVAL) is counted; any other code ends the sweep.
+Regenerating must reproduce the committed table byte for byte: a difference means make_plan() has changed what some shape runs.
+That the table holds EVERY instance a call can reach, not only those of this grid, is tests/test_conv_instances_host.py's enumeration.
 
 --ratios: for every row of modes 2, 3 and 4 (and the extra shapes of the GPU test's edge variants), on the seeded operands the GPU test
 feeds (conv_ref.case_operands), a float32 numpy emulation of the transforms exactly as the kernel writes them (tests/conv_ref.py) is
@@ -32,21 +33,11 @@ CHANNELS = [3, 4, 8, 12, 18, 24, 32, 40, 64, 68, 72, 128, 136, 200]
 HEIGHTS = [1, 2, 3, 4, 5, 8, 9, 16, 20, 33, 40, 72]
 WIDTHS = [1, 2, 3, 4, 5, 6, 8, 9, 12, 16, 20, 33, 34, 36, 65, 66, 68, 129, 130, 132]
 BATCHES = [1, 2, 3, 5, 8]
-MAX_COST = 1 << 26  # batch * cin * cout * h * w of one launch: every instance is reachable with few channels, none needs a long launch
+MAX_COST = 1 << 26  # batch * cin * cout * h * w of a shape: every instance is reachable with few channels (the table's rows are launched by the GPU test)
 
 
 def out_hw(mode, h, w):
     return (2 * h + 1, 2 * w + 1) if mode in (1, 4) else (h, w)
-
-
-def weight_rows(mode):
-    return {0: 9, 1: 9, 2: 12, 3: 18, 4: 12}[mode]
-
-
-def weight_cols(mode, cout):
-    if mode in (2, 3) and cout > 32:
-        return (cout + 63) // 64 * 64
-    return (cout + 31) // 32 * 32
 
 
 def grid():
@@ -60,48 +51,29 @@ def grid():
 
 
 def sweep(out=None):
-    import torch
+    import ctypes
 
     from maua_stylegan2_amd import _lib
 
     lib = _lib.load()
-    dev = torch.device("cuda:0")
-    shapes = list(grid())
-    n_x = max(b * cin * h * w for _, cin, _, h, w, b in shapes)
-    n_y = max(b * cout * out_hw(m, h, w)[0] * out_hw(m, h, w)[1] for m, _, cout, h, w, b in shapes)
-    n_w = max(weight_rows(m) * cin * weight_cols(m, cout) for m, cin, cout, _, _, _ in shapes)
-    n_ws = max(lib.maua_modconv_ws_floats(b, cin, cout, h, w, m) for m, cin, cout, h, w, b in shapes)
-    print(f"{len(shapes)} shapes; x {n_x} y {n_y} w {n_w} ws {n_ws} floats", flush=True)
-    g = torch.Generator(device="cpu").manual_seed(0)
-    x = torch.randn(n_x, generator=g).to(dev)
-    wp = torch.randn(n_w, generator=g).to(dev)
-    s = (1 + 0.3 * torch.randn(8 * 256, generator=g)).to(dev)
-    d = (0.5 + torch.rand(8 * 256, generator=g)).to(dev)
-    y = torch.empty(n_y + 4096, device=dev)
-    ws = torch.empty(max(n_ws, 1) + 4096, device=dev)
-    stream = _lib.stream_ptr(dev)
+    buf = ctypes.create_string_buffer(128)
     best, refused = {}, {}
-    for k, (mode, cin, cout, h, w, b) in enumerate(shapes):
-        n = lib.maua_modconv_ws_floats(b, cin, cout, h, w, mode)
-        rc = lib.maua_modconv3x3_f32(x.data_ptr(), wp.data_ptr(), s.data_ptr(), 256, d.data_ptr(), y.data_ptr(), b, cin, cout, h, w, mode,
-                                     1.0 / (9 * cin) ** 0.5, 0, None, 0, None, None, ws.data_ptr(), None, 0, stream)
+    for mode, cin, cout, h, w, b in grid():
+        rc = lib.maua_modconv_plan_instance(b, cin, cout, h, w, mode, buf, 128)
         if rc == -22:  # a shape the plan refuses (documented: no patch of that map fits a tile); recorded, not an error
             refused.setdefault(mode, []).append((cin, cout, h, w, b))
             continue
         if rc != 0:
             sys.exit(f"rc {rc} at mode {mode} cin {cin} cout {cout} h {h} w {w} batch {b}")
-        if k % 64 == 0:
-            torch.cuda.synchronize(dev)  # a HIP error raises here and ends the sweep
-            if k % 65536 == 0:
-                print(f"{k} / {len(shapes)}: {len(best)} instances", flush=True)
-        name = _lib.last_modconv_instance()
+        name = buf.value.decode()
         cost = b * cin * cout * h * w
         if name not in best or cost < best[name][0]:
+            n = lib.maua_modconv_ws_floats(b, cin, cout, h, w, mode)
             oh, ow = out_hw(mode, h, w)
             best[name] = (cost, dict(name=name, mode=mode, cin=cin, cout=cout, h=h, w=w, batch=b, ws_floats=int(n), split_k=n > 0,
                                      splits=int(n // (b * cout * oh * ow)) if n else 1))
-    torch.cuda.synchronize(dev)
     rows = [best[k][1] for k in sorted(best, key=lambda q: (best[q][1]["mode"], q))]
+    # (the string is part of the committed table, which this sweep must reproduce byte for byte)
     doc = {"generated_by": "tools/conv_instance_sweep.py (GPU sweep; --ratios on the CPU)", "instances": rows,
            "refused_einval": {str(m): len(v) for m, v in sorted(refused.items())},
            "refused_examples": {str(m): v[:4] for m, v in sorted(refused.items())}}
