@@ -562,6 +562,38 @@ int maua_bend_morph_f32(const float* x, float* y, int batch, int channels, int h
  * unknown mode, a reflect / circular pad beyond its limit, or a noise_channels other than 1 / channels. */
 int maua_bend_pad_f32(const float* x, float* y, int batch, int channels, int h, int w, int pad_l, int pad_r, int pad_t, int pad_b,
                       int mode, float value, const float* noise, int noise_channels, void* stream);
+/* Coordinate-remap bends (additive to ABI 8; csrc/bend_remap.hip; audioreactive/bend.py: Mirror, Kaleidoscope, Swirl, Ripple, Displace):
+ * y[b, c, oy, ox] = x[b, c] sampled bilinearly at a source coordinate s(b, oy, ox) on the selected channels, the others copied through.
+ * chan_mask, param_rows and src select channels and parameter rows exactly as in maua_bend_point_f32: param [param_rows,
+ * MAUA_BEND_REMAP_PARAMS]; param_rows == 1: every sample uses row 0; src != NULL: sample b uses row src->frame0 + b, read on the device;
+ * otherwise row b, param_rows == batch.
+ *
+ * Coordinates.  Output pixel o = (ox, oy), centre c = ((w - 1) / 2, (h - 1) / 2), d = o - c, r = |d|; angles in radians; row p[0..3]:
+ *   op 0 mirror        n = (p0, p1) a unit normal (from the host), t = d . n - p2;  s = o - 2 t n where t < 0, s = o elsewhere
+ *   op 1 kaleidoscope  N = clamp(rint(p0), 1, 64), ws = 2 pi / N;  a = atan2(dy, dx) - p1;  a -= ws floor(a / ws);  a = ws - a where
+ *                      a > ws / 2;  a += p1 + p2;  s = c + r (cos a, sin a)
+ *   op 2 swirl         phi = p0 exp(-r / p1);  s = c + (cos phi dx - sin phi dy, sin phi dx + cos phi dy)
+ *   op 3 ripple        k = p0 sin(2 pi (r / p1 - p2));  s = o + k d / r  (s = o at r = 0)
+ *   op 4 displace      s = o + p0 D(o, p1).  field [field_frames, 2, field_h, field_w] holds (dx, dy) planes of a looping bank, sampled
+ *                      bilinearly at u = ox (field_w - 1) / (w - 1), v = oy (field_h - 1) / (h - 1) (0 along a map axis of length 1);
+ *                      t = floor(p1), ft = p1 - t, t0 = t mod field_frames (non-negative), t1 = (t0 + 1) mod field_frames;
+ *                      D = (1 - ft) field[t0] + ft field[t1]: a fractional loop position blends neighbouring frames.
+ * Sampling.  s is folded per axis into [0, n - 1]: border 0 reflects without repeating the edge (period 2 (n - 1); an axis of length 1
+ * gives 0), border 1 clamps; then x0 = floor(s), x1 = min(x0 + 1, n - 1) and the bilinear blend — grid_sample(mode="bilinear",
+ * padding_mode="reflection" | "border", align_corners=True) on pixel coordinates.  The blend is held inside the range of its four taps,
+ * so an output never leaves the range of its source plane; a NaN tap gives a NaN.
+ * Bad rows.  A row with a NaN or an infinity among the parameters its op uses, or with p1 <= 0 for swirl or ripple, leaves its sample
+ * unchanged (y = x, every channel).  Every finite row, however large, keeps every load inside x and field: the folded coordinate and
+ * the integer taps are clamped.
+ * The coordinate, the tap offsets and the weights are computed once per (sample, pixel) and reused over a chunk of channels.
+ * batch <= 64, channels <= 65535, planes (of x and of field) below 2 GiB, any h, w >= 1; y == x is refused (a gather).  MAUA_EINVAL,
+ * without a launch, on null or non-positive arguments, an unknown op or border, or op 4 without a field or with a non-positive field
+ * size; field is ignored by ops 0 .. 3. */
+#define MAUA_BEND_REMAP_PARAMS 4
+int maua_bend_remap_f32(const float* x, float* y, int batch, int channels, int h, int w, int op, int border,
+                        const float* param, int param_rows,                             /* [param_rows, 4] */
+                        const float* field, int field_frames, int field_h, int field_w, /* op 4 only: [F, 2, fh, fw] (dx, dy planes) */
+                        const uint8_t* chan_mask, const maua_frame_source_t* src, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ hipGraph runtime
  * Capture everything launched on `stream` between begin/end into a hipGraph and replay it (per-frame generator

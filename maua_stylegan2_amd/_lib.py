@@ -152,6 +152,7 @@ _SIGNATURES = {
     "maua_bend_point_f32": (c_int, [_P, _P, c_int, c_int, c_int64, c_int, _P, c_int, _P, _P, _P]),
     "maua_bend_morph_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
     "maua_bend_pad_f32": (c_int, [_P, _P] + [c_int] * 9 + [c_float, _P, c_int, _P]),
+    "maua_bend_remap_f32": (c_int, [_P, _P] + [c_int] * 6 + [_P, c_int, _P] + [c_int] * 3 + [_P, _P, _P]),
     "maua_graph_begin_capture": (c_int, [_P]),
     "maua_graph_end_capture": (c_int, [_P, POINTER(c_void_p)]),
     "maua_graph_launch": (c_int, [_P, _P]),

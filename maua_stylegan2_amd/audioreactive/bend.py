@@ -1,7 +1,8 @@
 """Network bending with the reference's ``audioreactive.bend`` surface, on one HIP warp kernel instead of kornia.
 
 Mirrors /root/reference/audioreactive/bend.py: NetworkBend :12-26 · AddNoise :29-41 · Print :44-49 · Translate :52-72 ·
-Zoom :75-87 · Rotate :90-102.  The reference composes ReflectionPad2d -> kornia Translate/Scale/Rotate -> kornia
+Zoom :75-87 · Rotate :90-102 (and, without a counterpart there, the point / morphological bends, the
+padding bend and the coordinate-remap bends Mirror, Kaleidoscope, Swirl, Ripple, Displace).  The reference composes ReflectionPad2d -> kornia Translate/Scale/Rotate -> kornia
 CenterCrop (three full-size intermediates); here the composition is evaluated per OUTPUT pixel by
 maua_affine_reflect_warp_f32: inverse affine map into the padded canvas, bilinear taps, reflection folded into the
 index.  kornia is an un-pinned, un-vendored dependency (requirements.txt:8) -> "parity unpinned" (DESIGN.md); the
@@ -438,3 +439,149 @@ class Dilate(NetworkBend):
 
     def __init__(self, modulation, channels=None):
         super().__init__(lambda m: MorphBend("dilate", th.round(th.as_tensor(m).float()), channels), modulation)
+
+
+_REMAP_OPS = {"mirror": 0, "kaleidoscope": 1, "swirl": 2, "ripple": 3, "displace": 4}  # `op` of maua_bend_remap_f32
+_REMAP_BORDERS = {"reflect": 0, "clamp": 1}                                             # `border` of maua_bend_remap_f32
+_REMAP_PARAMS = 4                                                                       # MAUA_BEND_REMAP_PARAMS
+_MAX_SECTORS = 64
+
+
+class RemapBend(_ChannelBend):
+    """y = x sampled bilinearly at a per-pixel source coordinate (``op`` one of _REMAP_OPS) on the channels ``channels``, the others
+    copied through: one launch of maua_bend_remap_f32, whose header comment defines every op.  ``table`` [rows, 4] holds the device's
+    parameter rows (angles in radians, the mirror's normal as a unit vector); ``border``: how a coordinate outside the map is folded
+    back, one of _REMAP_BORDERS; ``field`` [F, 2, fh, fw]: the static flow-field bank of "displace".  What the device would pass through
+    as a bad row is refused here."""
+
+    def __init__(self, op, table, channels, border="reflect", field=None, n_channels=None):
+        if op not in _REMAP_OPS:
+            raise ValueError(f"unknown remap bend {op!r} ({' | '.join(_REMAP_OPS)})")
+        if border not in _REMAP_BORDERS:
+            raise ValueError(f"unknown border {border!r} ({' | '.join(_REMAP_BORDERS)})")
+        table = th.as_tensor(table).float()
+        if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != _REMAP_PARAMS:
+            raise ValueError(f"remap bend parameters must be [n_frames, {_REMAP_PARAMS}] (got shape {tuple(table.shape)})")
+        if not bool(th.isfinite(table).all()):
+            raise ValueError(f"{op} bend: the modulation holds a NaN or an infinity")
+        if op == "kaleidoscope" and not bool(((th.round(table[:, 0]) >= 1) & (th.round(table[:, 0]) <= _MAX_SECTORS)).all()):
+            raise ValueError(f"kaleidoscope sectors must lie in 1 .. {_MAX_SECTORS}")
+        if op in ("swirl", "ripple") and not bool((table[:, 1] > 0).all()):
+            raise ValueError(f"{op} bend: the {'radius' if op == 'swirl' else 'wavelength'} must be positive")
+        if (field is not None) != (op == "displace"):
+            raise ValueError("a flow field goes with the displace bend, and only with it")
+        if field is not None:
+            field = th.as_tensor(field)
+            if field.dim() != 4 or field.shape[1] != 2 or min(field.shape) < 1:
+                raise ValueError(f"the flow field must be a bank [F, 2, fh, fw] of (dx, dy) planes (got shape {tuple(field.shape)})")
+            field = field.float()
+            if not bool(th.isfinite(field).all()):
+                raise ValueError("the flow field holds a NaN or an infinity")
+        super().__init__(table, channels, n_channels)
+        self.op, self.border, self.field = _REMAP_OPS[op], _REMAP_BORDERS[border], field
+        self._field_dev = {}  # device -> the field bank there; never evicted, like _dev
+
+    def _launch(self, x, y, table, mask, src):
+        b, c, h, w = x.shape
+        field = None
+        if self.field is not None:
+            key = str(x.device)
+            if key not in self._field_dev:
+                self._field_dev[key] = self.field.to(x.device).contiguous()
+            field = self._field_dev[key]
+        frames, fh, fw = (0, 0, 0) if field is None else (field.shape[0], field.shape[2], field.shape[3])
+        with th.cuda.device(x.device):
+            _lib.check(_lib.load().maua_bend_remap_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, self.op, self.border, table.data_ptr(),
+                                                       self.sequence_rows, _lib.ptr(field), frames, fh, fw, _lib.ptr(mask), src,
+                                                       _lib.stream_ptr(x.device)), "maua_bend_remap_f32")
+        return y
+
+
+def _modulation_columns(name, modulation, columns):
+    """The column rule of the remap bends: ``modulation`` is [n_frames] (the first parameter) or [n_frames, k] (the first k parameters, in
+    the order of ``columns`` = ((name, constant or None), ...)); every parameter without a column takes its keyword constant for all
+    frames.  Returns [n_frames, len(columns)] where the modulation lives."""
+    m = th.as_tensor(modulation).float()
+    if m.dim() == 1:
+        m = m[:, None]
+    if m.dim() != 2 or m.shape[0] < 1 or not 1 <= m.shape[1] <= len(columns):
+        raise ValueError(f"{name} modulation must be [n_frames] or [n_frames, k] with k <= {len(columns)} columns "
+                         f"({', '.join(c for c, _ in columns)}), got shape {tuple(m.shape)}")
+    missing = columns[m.shape[1]:]
+    for column, constant in missing:
+        if constant is None:
+            raise ValueError(f"{name} needs {column}: as a modulation column or as the keyword {column}=")
+    if missing:
+        m = th.cat([m, th.tensor([float(c) for _, c in missing], device=m.device).expand(m.shape[0], -1)], 1)
+    return m
+
+
+def _remap_rows(*columns):
+    """[n_frames, 4] device rows from up to four columns (the rest 0)."""
+    rows = th.zeros(columns[0].shape[0], _REMAP_PARAMS, device=columns[0].device)
+    for i, column in enumerate(columns):
+        rows[:, i] = column
+    return rows
+
+
+class Mirror(NetworkBend):
+    """Mirror across a line: the side the normal points away from shows the other side's reflection.  Modulation columns: ``angle`` of the
+    normal in degrees (0: the normal points along +x, so the left half mirrors the right half; 90: the top mirrors the bottom), ``offset`` of
+    the line from the map's centre along the normal, in pixels."""
+
+    def __init__(self, modulation, offset=0.0, channels=None, border="reflect"):
+        def make(m):
+            m = _modulation_columns("Mirror", m, (("angle", None), ("offset", offset)))
+            a = th.deg2rad(m[:, 0])
+            return RemapBend("mirror", _remap_rows(th.cos(a), th.sin(a), m[:, 1]), channels, border)
+
+        super().__init__(make, modulation)
+
+
+class Kaleidoscope(NetworkBend):
+    """Fold the map into ``sectors`` mirrored wedges about its centre.  Modulation columns: ``rotation`` of the sampled content in degrees,
+    ``angle`` of the wedge pattern in degrees, ``sectors`` (rounded, 1 .. 64)."""
+
+    def __init__(self, modulation, angle=0.0, sectors=6, channels=None, border="reflect"):
+        def make(m):
+            m = _modulation_columns("Kaleidoscope", m, (("rotation", None), ("angle", angle), ("sectors", sectors)))
+            return RemapBend("kaleidoscope", _remap_rows(m[:, 2], th.deg2rad(m[:, 1]), th.deg2rad(m[:, 0])), channels, border)
+
+        super().__init__(make, modulation)
+
+
+class Swirl(NetworkBend):
+    """Rotate about the centre by an angle that decays with the distance r from it: ``strength`` exp(-r / ``radius``).  Modulation columns:
+    ``strength`` in degrees, ``radius`` in pixels (> 0)."""
+
+    def __init__(self, modulation, radius=None, channels=None, border="reflect"):
+        def make(m):
+            m = _modulation_columns("Swirl", m, (("strength", None), ("radius", radius)))
+            return RemapBend("swirl", _remap_rows(th.deg2rad(m[:, 0]), m[:, 1]), channels, border)
+
+        super().__init__(make, modulation)
+
+
+class Ripple(NetworkBend):
+    """Push every pixel along its radius by ``amplitude`` sin(2 pi (r / ``wavelength`` - ``phase``)).  Modulation columns: ``amplitude`` in
+    pixels, ``wavelength`` in pixels (> 0), ``phase`` in cycles (a rising phase moves the rings outwards)."""
+
+    def __init__(self, modulation, wavelength=None, phase=0.0, channels=None, border="reflect"):
+        def make(m):
+            m = _modulation_columns("Ripple", m, (("amplitude", None), ("wavelength", wavelength), ("phase", phase)))
+            return RemapBend("ripple", _remap_rows(m[:, 0], m[:, 1], m[:, 2]), channels, border)
+
+        super().__init__(make, modulation)
+
+
+class Displace(NetworkBend):
+    """Displace along a flow field ("liquid"): ``field`` [F, 2, fh, fw] is a static looping bank of (dx, dy) planes (an ``ar.perlin_noise``
+    loop, say), stretched over the map.  Modulation columns: ``amplitude`` in pixels per unit of the field, ``position`` in the loop in
+    frames of the bank (fractional positions blend neighbouring frames, any value wraps: a modulated speed is a cumulative sum)."""
+
+    def __init__(self, modulation, field, position=0.0, channels=None, border="reflect"):
+        def make(m):
+            m = _modulation_columns("Displace", m, (("amplitude", None), ("position", position)))
+            return RemapBend("displace", _remap_rows(m[:, 0], m[:, 1]), channels, border, field=field)
+
+        super().__init__(make, modulation)
