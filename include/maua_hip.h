@@ -417,6 +417,26 @@ int maua_crop_resize_u8(const uint8_t* in, uint8_t* out, int batch, int in_h, in
  * (MAUA_EINVAL otherwise); batch == 0 is a successful no-op, more than 65535 frames a launch are MAUA_ENOSYS.  Any even width and any
  * alignment is served; w % 8 == 0 with 8-byte aligned buffers takes the vector path.  (Additive: the ABI version is unchanged.) */
 int maua_rgb_to_yuv420p_u8(const uint8_t* rgb, uint8_t* out, int batch, int h, int w, void* stream);
+/* Packed uint8 frames rgb[B,h,w,3] -> one baseline JPEG per frame (4:2:0, the standard Huffman tables, restart intervals of restart_mcus
+ * 16 x 16 MCUs; the stream is defined in integers in csrc/jpeg.hip and the device reproduces that definition byte for byte).  1 <= h, w
+ * <= 65535, quality in 1 .. 95, restart_mcus in 1 .. 65535: MAUA_EINVAL otherwise.  (Additive: the ABI version is unchanged.)
+ *   maua_jpeg_header    host only, no HIP call: writes the bytes from SOI up to and including the SOS header (they depend on h, w, quality
+ *                       and restart_mcus only) to h_buf[cap] and returns their count; MAUA_EINVAL for bad arguments or a cap too small.
+ *   maua_jpeg_ws_bytes  size of the workspace of maua_jpeg_encode_u8: zig-zag int16 coefficients [B][MCU][6][64], one worst-case segment
+ *                       per restart interval (2496 bytes per MCU + 16) and the intervals' lengths; a pure function of its arguments, 0
+ *                       for arguments outside the ranges above.
+ *   maua_jpeg_encode_u8 three launches on `stream` (colour + DCT + quantiser; entropy coding, a workgroup per restart interval; packing),
+ *                       no allocation, no synchronisation.  `header`: a DEVICE copy of maua_jpeg_header's bytes for the same h, w, quality
+ *                       and restart_mcus.  out[B, slot_bytes], per frame: bytes 0..3 the stream's length n (little-endian), bytes 4..7 the
+ *                       status (0 ok, 1 overflow), bytes 8..15 zero, the stream from byte 16; the slot's bytes behind 16 + n are not
+ *                       written.  Overflow (16 + n > slot_bytes): status 1, n is the length the stream would have had, nothing but the 16
+ *                       bytes is written, the other frames of the batch are unaffected.  MAUA_EINVAL (before any HIP call) for a NULL
+ *                       pointer, slot_bytes < 16 + header_len + 2 or a ws that is not 16-byte aligned; batch == 0 is a successful no-op,
+ *                       more than 65535 frames a launch are MAUA_ENOSYS.  rgb and out may have any alignment. */
+int maua_jpeg_header(int h, int w, int quality, int restart_mcus, uint8_t* h_buf, int cap);
+int64_t maua_jpeg_ws_bytes(int batch, int h, int w, int restart_mcus);
+int maua_jpeg_encode_u8(const uint8_t* rgb, int batch, int h, int w, int quality, int restart_mcus, const uint8_t* header, int header_len,
+                        uint8_t* out, int64_t slot_bytes, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ audio / temporal
  * Circular Gaussian FIR along time (audioreactive/signal.py:319-368): x [T, F] -> y [T, F], taps[2*radius+1]

@@ -59,7 +59,9 @@ CLI_FLAGS = (
     ("--ffmpeg_preset", dict(type=str, default="slow")),
     ("--output_file", dict(type=str, default=None)),
     # (not one of the reference's: what travels to the encoder — planar 4:2:0 is made on the device, render.frames_to_yuv420p)
+    # ... or one baseline JPEG per frame, render.frames_to_mjpeg, at --mjpeg_quality 1 .. 95)
     ("--pipe_pix_fmt", dict(type=str, default="rgb24", choices=render.PIPE_PIX_FMTS)),
+    ("--mjpeg_quality", dict(type=int, default=render.MJPEG_DEFAULT_QUALITY)),
 )
 
 
@@ -352,7 +354,8 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # generate() keeps the reference's parameter list: the pipe format arrives in the namespace (--pipe_pix_fmt, a plugin's OVERRIDE,
         # a caller's own ``args``) or through $MAUA_PIPE_PIX_FMT
         written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
-                          output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None))
+                          output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
+                          getattr(args, "mjpeg_quality", None))
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -363,7 +366,9 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
 
 
 def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
-            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None):
+            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None, mjpeg_quality=None):
+    if pipe_pix_fmt == "mjpeg" and mjpeg_quality is not None:
+        pipe_pix_fmt = f"mjpeg:{mjpeg_quality}"  # (render_shard's parameter list is pinned: the quality travels in the format's name)
     if pipe_pix_fmt not in (None, "rgb24"):
         written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
                                       truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt)
@@ -428,6 +433,7 @@ def main(argv=None):
         setattr(args, key, value)
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
+    settings.pop("mjpeg_quality", None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)
     finally:

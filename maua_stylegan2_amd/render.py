@@ -21,6 +21,8 @@ Sinks: ffmpeg rawvideo pipe (same pixel format / codec arguments as render.py:58
 otherwise raw rgb24 bytes to ``output_file`` (+ ".rgb24"), or a null sink for benchmarking (``output_file=None``).
 Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to planar YUV 4:2:0 on the device (frames_to_yuv420p) before
 they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
+Opt-in pipe format ``mjpeg`` (``mjpeg:<quality>``): every frame is encoded as one baseline JPEG on the device (frames_to_mjpeg) and travels
+in a fixed-size slot; the sink writes the streams alone, to ``ffmpeg -f mjpeg`` or, without a binary, to a playable Motion-JPEG .avi (avi.py).
 """
 import collections
 import contextlib
@@ -34,7 +36,7 @@ import threading
 import numpy as np
 import torch as th
 
-from . import _lib, sharding
+from . import _lib, avi, sharding
 from .audioreactive.noise import NoiseSynth
 
 th.set_grad_enabled(False)
@@ -58,39 +60,78 @@ def _output_dims(out_size):
     raise Exception("The only output sizes currently supported are: 512, 1024, 1080, or 1920")
 
 
-PIPE_PIX_FMTS = ("rgb24", "yuv420p")  # what travels to the sink: packed RGB (the reference's, default) or planar 4:2:0 made on the device
+# what travels to the sink: packed RGB (the reference's, default), planar 4:2:0 made on the device, or one JPEG per frame made on the device
+PIPE_PIX_FMTS = ("rgb24", "yuv420p", "mjpeg")
+MJPEG_DEFAULT_QUALITY = 90
 # how a yuv420p pipe is tagged: the matrix / range csrc/yuv420.hip converts with (BT.601 limited range), so that players decode with it
 YUV420P_TAGS = ["-colorspace", "smpte170m", "-color_primaries", "smpte170m", "-color_trc", "smpte170m", "-color_range", "tv"]
 
 
 def _pipe_pix_fmt(pix_fmt):
-    """A ``pipe_pix_fmt`` argument resolved: None -> $MAUA_PIPE_PIX_FMT -> rgb24."""
+    """A ``pipe_pix_fmt`` argument resolved: None -> $MAUA_PIPE_PIX_FMT -> rgb24.  ``mjpeg`` may carry its quality, ``mjpeg:<q>``
+    (_mjpeg_quality reads it): the bare name is returned."""
     pix_fmt = pix_fmt or os.environ.get("MAUA_PIPE_PIX_FMT") or "rgb24"
-    if pix_fmt not in PIPE_PIX_FMTS:
+    name = "mjpeg" if pix_fmt.startswith("mjpeg:") else pix_fmt
+    if name not in PIPE_PIX_FMTS:
         raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
-    return pix_fmt
+    return name
+
+
+def _mjpeg_quality(pix_fmt):
+    """The JPEG quality of an mjpeg pipe: the suffix of ``mjpeg:<q>`` -> $MAUA_MJPEG_QUALITY -> 90; 1 .. 95."""
+    pix_fmt = pix_fmt or os.environ.get("MAUA_PIPE_PIX_FMT") or ""
+    text = pix_fmt[len("mjpeg:"):] if pix_fmt.startswith("mjpeg:") else os.environ.get("MAUA_MJPEG_QUALITY") or str(MJPEG_DEFAULT_QUALITY)
+    try:
+        quality = int(text)
+    except ValueError:
+        raise ValueError(f"mjpeg quality {text!r} is not an integer") from None
+    if not 1 <= quality <= 95:
+        raise ValueError(f"mjpeg quality {quality} outside 1 .. 95")
+    return quality
+
+
+def mjpeg_slot_bytes(w, h):
+    """Bytes of the fixed-size slot an mjpeg frame travels in (16 bytes of slot header + the stream): the yuv420p frame plus 1 KiB.
+    Uniform noise at quality 95 takes about 1.2 bytes per pixel, so no picture overflows the 1.5 in practice; one that does is reported by
+    the sink (status 1 in the slot header)."""
+    return 1024 + w * h * 3 // 2
 
 
 class FrameSink:
     """Ordered consumer of uint8 [H, W, 3] frames (``pix_fmt="rgb24"``) or of flat planar I420 frames [H * W * 3 / 2]
-    (``pix_fmt="yuv420p"``: converted, and for wide outputs resized, on the device — frames_to_yuv420p)."""
+    (``pix_fmt="yuv420p"``: converted, and for wide outputs resized, on the device — frames_to_yuv420p), or of flat mjpeg slots
+    [mjpeg_slot_bytes] (``pix_fmt="mjpeg"``: one JPEG per frame behind a 16-byte slot header — frames_to_mjpeg; ``quality`` is only quoted
+    in the error an overflowed slot raises)."""
 
     def __init__(self, output_file, width, height, framerate, audio_file=None, offset=0, duration=None,
-                 ffmpeg_preset="slow", pix_fmt="rgb24"):
+                 ffmpeg_preset="slow", pix_fmt="rgb24", quality=None):
         if pix_fmt not in PIPE_PIX_FMTS:
             raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
         if pix_fmt == "yuv420p" and (width % 2 or height % 2):
             raise ValueError(f"yuv420p needs even dimensions, got {width}x{height}")
         self.w, self.h = width, height
         self.pix_fmt = pix_fmt
+        self.quality = quality
         self.proc = None
         self.file = None
         self.count = 0
         if output_file is None:
             return
+        if pix_fmt == "mjpeg" and shutil.which("ffmpeg") is None:
+            # no encoder needed: the streams are a playable Motion-JPEG file as they are (audio is not muxed)
+            self.file = avi.MjpegAviWriter(output_file, width, height, framerate)
+            path = self.file.paths[0]
+            audio = f" -ss {offset} -t {duration} -i {audio_file}" if audio_file is not None else ""
+            mux = " -b:a 320K -ac 2" if audio_file is not None else ""
+            print(f"ffmpeg binary not found: writing Motion-JPEG frames ({width}x{height}) to {path}\n"
+                  f"  mux or transcode later with: ffmpeg -i {path}{audio} -c:v copy{mux} {output_file}")
+            return
         if shutil.which("ffmpeg") is not None:
-            cmd = ["ffmpeg", "-hide_banner", "-y", "-v", "warning", "-f", "rawvideo", "-pix_fmt", pix_fmt, "-framerate",
-                   f"{framerate}", "-s", f"{width}x{height}", "-i", "pipe:"]
+            if pix_fmt == "mjpeg":
+                cmd = ["ffmpeg", "-hide_banner", "-y", "-v", "warning", "-f", "mjpeg", "-framerate", f"{framerate}", "-i", "pipe:"]
+            else:
+                cmd = ["ffmpeg", "-hide_banner", "-y", "-v", "warning", "-f", "rawvideo", "-pix_fmt", pix_fmt, "-framerate",
+                       f"{framerate}", "-s", f"{width}x{height}", "-i", "pipe:"]
             if audio_file is not None:
                 cmd += ["-ss", f"{offset}", "-t", f"{duration}", "-guess_layout_max", "0", "-i", audio_file]
             cmd += ["-r", f"{framerate}", "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-preset", ffmpeg_preset]
@@ -114,7 +155,22 @@ class FrameSink:
 
     def write(self, frame):
         """frame: numpy uint8 [H, W, 3]; wide 2048-px outputs are cropped + resized as render.py:98-105.  A yuv420p sink takes the flat
-        planar frame [H * W * 3 / 2] as it is: it was resized on the device before the conversion, neither PIL nor the crop applies."""
+        planar frame [H * W * 3 / 2] as it is: it was resized on the device before the conversion, neither PIL nor the crop applies.  An
+        mjpeg sink takes the flat slot, checks its header and writes the stream alone."""
+        if self.pix_fmt == "mjpeg":
+            slot_bytes = mjpeg_slot_bytes(self.w, self.h)
+            if frame.ndim != 1 or frame.shape[0] != slot_bytes or frame.dtype != np.uint8:
+                raise ValueError(f"an mjpeg frame of {self.w}x{self.h} is a flat uint8 slot of {slot_bytes} bytes, got {frame.dtype} "
+                                 f"{tuple(frame.shape)}")
+            frame = np.ascontiguousarray(frame)
+            n, status = (int(v) for v in frame[:8].view("<u4"))
+            if status != 0 or 16 + n > slot_bytes:
+                raise ValueError(f"mjpeg frame {self.count} overflowed its slot: the stream needs {n} bytes, the slot holds {slot_bytes - 16} "
+                                 f"(quality {self.quality if self.quality is not None else 'unknown'}: lower it)")
+            if self.proc is not None or self.file is not None:
+                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(frame[16: 16 + n]).cast("B"))
+            self.count += 1
+            return
         if self.pix_fmt == "yuv420p":
             if frame.ndim != 1 or frame.shape[0] != self.w * self.h * 3 // 2:
                 raise ValueError(f"a yuv420p frame of {self.w}x{self.h} is a flat array of {self.w * self.h * 3 // 2} bytes, got shape "
@@ -269,9 +325,45 @@ def frames_to_yuv420p(u8, scratch):
     return out
 
 
-def _deliverable(u8, out_size, pix_fmt, scratch):
-    """A batch as it leaves the device: wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0."""
+def frames_to_mjpeg(u8, scratch, quality):
+    """uint8 [b, H, W, 3] device frames -> mjpeg slots [b, mjpeg_slot_bytes(W, H)] uint8 on the device, on the current (= producing) stream:
+    per frame a 16-byte slot header (stream length, status) and one baseline JPEG at ``quality`` by maua_jpeg_encode_u8, one restart
+    interval per MCU row.  ``scratch``: dict holding the reusable buffers (the protocol of crop_resize_for_delivery): the slots and the
+    workspace per input buffer — the lanes' batches are encoded concurrently on their own streams, a workspace cannot be shared between
+    them — and the device copy of the JPEG header per (H, W, quality)."""
+    if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != th.uint8 or not u8.is_cuda:
+        raise RuntimeError(f"frames_to_mjpeg takes uint8 [b, H, W, 3] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
+    b, h, w, _ = u8.shape
+    lib = _lib.load()
+    u8 = u8.contiguous()
+    slot_bytes = mjpeg_slot_bytes(w, h)
+    restart_mcus = (w + 15) // 16
+    key = ("mjpeg-header", h, w, quality)
+    header = scratch.get(key)
+    if header is None:
+        host = np.empty(1024, np.uint8)
+        n = lib.maua_jpeg_header(h, w, quality, restart_mcus, host.ctypes.data, host.size)
+        if n <= 0:
+            _lib.check(n, "maua_jpeg_header")
+        header = scratch[key] = th.from_numpy(host[:n].copy()).to(u8.device)
+    key = ("mjpeg", u8.data_ptr(), b, h, w, quality)
+    buffers = scratch.get(key)
+    if buffers is None:
+        out = th.empty((b, slot_bytes), dtype=th.uint8, device=u8.device)
+        ws = th.empty(max(int(lib.maua_jpeg_ws_bytes(b, h, w, restart_mcus)), 16), dtype=th.uint8, device=u8.device)
+        buffers = scratch[key] = (out, ws)
+    out, ws = buffers
+    with th.cuda.device(u8.device):
+        _lib.check(lib.maua_jpeg_encode_u8(u8.data_ptr(), b, h, w, quality, restart_mcus, header.data_ptr(), header.numel(), out.data_ptr(),
+                                           slot_bytes, ws.data_ptr(), _lib.stream_ptr(u8.device)), "maua_jpeg_encode_u8")
+    return out
+
+
+def _deliverable(u8, out_size, pix_fmt, scratch, quality=None):
+    """A batch as it leaves the device: wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0 or — mjpeg — encoded."""
     u8 = crop_resize_for_delivery(u8, out_size, scratch)
+    if pix_fmt == "mjpeg":
+        return frames_to_mjpeg(u8, scratch, MJPEG_DEFAULT_QUALITY if quality is None else quality)
     return frames_to_yuv420p(u8, scratch) if pix_fmt == "yuv420p" else u8
 
 
@@ -720,9 +812,11 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
     """``render`` with an optional ``_shard = (lo, hi, n_frames)``: set by generate() after sharding.scatter_frames, it says
     that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames.
-    ``pipe_pix_fmt``: "rgb24" or "yuv420p" (PIPE_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24) — what crosses to the host, to rank 0
-    and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the environment variable."""
+    ``pipe_pix_fmt``: "rgb24", "yuv420p", "mjpeg" or "mjpeg:<quality>" (PIPE_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24) — what
+    crosses to the host, to rank 0 and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the
+    environment variable."""
     width, height = _output_dims(out_size)
+    quality = _mjpeg_quality(pipe_pix_fmt) if _pipe_pix_fmt(pipe_pix_fmt) == "mjpeg" else None
     pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
     rank, world = sharding.rank_world()
     # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM) or "host" (per-rank D2H into shared memory)
@@ -740,7 +834,8 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
-            sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt)
+            sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt,
+                             quality=quality)
             unwind.callback(sink.close)  # the encoder process / output file must not outlive a failed render: closed last, and always
             worker = SinkWorker(sink)
             unwind.callback(_drain_quietly, worker)
@@ -763,7 +858,7 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
                 # (lanes: synthesize's default, 3, on every path)
                 for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
                                         frame_range=frame_range):
-                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch))  # 2048-px frames leave the device as 1920x1080 already
+                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality))  # 2048-px frames leave the device as 1920x1080 already
                 delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt))
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
@@ -772,7 +867,8 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
 
 def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
     """[H, W, 3] of the frames the generator produces for ``out_size`` (1920 / 1080 render 2048-px-wide / -high frames
-    that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p"."""
+    that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p", [mjpeg_slot_bytes] for
+    "mjpeg"."""
     side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
     if out_size == 1920:
         shape = (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
@@ -780,4 +876,6 @@ def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
         shape = (1920, 1080, 3) if side == 1024 else (2 * side, side, 3)
     else:
         shape = (side, side, 3)
+    if pix_fmt == "mjpeg":
+        return (mjpeg_slot_bytes(shape[1], shape[0]),)
     return (shape[0] * shape[1] * 3 // 2,) if pix_fmt == "yuv420p" else shape
