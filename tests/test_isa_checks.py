@@ -16,6 +16,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 SOURCES = ("modconv_w2d", "modconv_up2d")
 STREAMING = ("upfirdn2d",)  # HBM-bound kernels: no LDS-DMA, but a spill or a scratch array there is HBM traffic the roofline does not count
 GENERIC = ("modconv",)  # the generic convolution kernel: which instances the product build holds, and that the FAST ones do not spill
+SIDE = ("modconv_sbf16",)  # the split-bf16 side measurement: only which kernels the product build holds
 
 
 @pytest.fixture(scope="module")
@@ -30,8 +31,8 @@ def device_asm(tmp_path_factory):
                         f"{REPO}/maua_stylegan2_amd/csrc/{name}.hip", "-o", dst], check=True, capture_output=True)
         return name, open(dst).read()
 
-    with ThreadPoolExecutor(len(SOURCES + STREAMING + GENERIC)) as pool:
-        return dict(pool.map(build, SOURCES + STREAMING + GENERIC))
+    with ThreadPoolExecutor(len(SOURCES + STREAMING + GENERIC + SIDE)) as pool:
+        return dict(pool.map(build, SOURCES + STREAMING + GENERIC + SIDE))
 
 
 @pytest.mark.parametrize("name", SOURCES)
@@ -106,6 +107,41 @@ def test_generic_conv_kernel_compiled_set_is_the_instance_table(device_asm):
     assert len(fast) == 29
     for k in fast:
         assert spills[k] == 0 and scratch[k] == 0, (demangled(k), spills[k], scratch[k])
+
+
+def test_dedicated_conv_kernels_compiled_set_is_the_dedicated_table(device_asm):
+    """csrc/modconv_w2d.hip, modconv_up2d.hip and modconv_sbf16.hip: the product build must hold exactly the conv kernel instances named in
+    tests/golden/conv_dedicated_instances.json (6 + 7 + 2, each launched by tests/test_conv_dedicated_gpu.py under that name) plus the
+    helper kernels listed here — no kernel is compiled that no case runs, and none is tested that is not compiled."""
+    table = json.load(open(os.path.join(REPO, "tests", "golden", "conv_dedicated_instances.json")))["instances"]
+    helpers = {"modconv_w2d": {"pack_weight_wino2d_kernel"},
+               "modconv_up2d": {"up2d_seam_kernel", "up2d_edge_kernel", "pack_weight_up2d_kernel"},
+               "modconv_sbf16": {"export_last_column_kernel", "pack_weight_sbf16_kernel", "pack_edge_taps_kernel"}}
+    flag = ("false", "true")
+
+    def demangled(symbol):
+        if m := re.search(r"\d+modconv_w2d_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])EE", symbol):
+            return f"modconv_w2d_kernel<{m[1]}, {m[2]}, {m[3]}, {flag[int(m[4])]}>"
+        if m := re.search(r"\d+modconv_w2dw_kernelILb([01])EE", symbol):
+            return f"modconv_w2dw_kernel<{flag[int(m[1])]}>"
+        if m := re.search(r"\d+modconv_up2d_kernelILi(\d+)ELi(\d+)ELb([01])ELi(\d+)EE", symbol):
+            return f"modconv_up2d_kernel<{m[1]}, {m[2]}, {flag[int(m[3])]}, {m[4]}>"
+        if m := re.search(r"\d+modconv_sbf16_kernelILi(n?)(\d+)EE", symbol):
+            return f"modconv_sbf16_kernel<{'-' if m[1] else ''}{m[2]}>"
+        if re.search(r"\d+modconv_sbf16_up_kernelE", symbol):
+            return "modconv_sbf16_up_kernel"
+        m = re.match(r"_ZN12_GLOBAL__N_1\d+([a-z0-9_]+?)E", symbol)
+        assert m, symbol
+        return m[1]
+
+    compiled = {}
+    for source in SOURCES + SIDE:
+        names = [demangled(k) for k in re.findall(r"^\s+\.name:\s+(_Z\S+)", device_asm[source], flags=re.M)]
+        assert len(set(names)) == len(names), names
+        assert helpers[source] <= set(names), (source, names)
+        compiled[source] = set(names) - helpers[source]
+    assert [len(compiled[k]) for k in SOURCES + SIDE] == [6, 7, 2], compiled
+    assert set().union(*compiled.values()) == {r["name"] for r in table}
 
 
 def test_fused_kernel_spills_stay_outside_the_k_loop(device_asm):

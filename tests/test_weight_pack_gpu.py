@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import conv_ref
 from conv_ref import U32, conv_and_magnitude
 from maua_stylegan2_amd import _lib
 from redzone import Guard
@@ -163,63 +164,21 @@ def test_tile_image_packers_keep_their_buffer_contract(gpu, entry, size, accepte
     assert lib.maua_modconv_w2d_ok(8, 48, 16, 32) == 0 and lib.maua_pack_weight_sbf16_bytes(40, 16) == 0
 
 
-def _wino2d_ratio(x, wt):
-    """Rounding ratio of the two-axis form F(2x4, 3x3) (mode 5) on the test's own operands (x [cin, h, w] already scaled by the styles,
-    wt [cout, cin, 3, 3]; the amplification at an element depends on the data), measured with the float32 emulation of
-    tests/test_winograd_algebra.py (_wino_layer_f32: transforms, products and channel sums in float32) against fp64, on the CPU:
-    max |emulation - fp64| / (u M)."""
-    import test_winograd_algebra as wa
+def _ratio(mode, x, wt):
+    """Rounding ratio of mode 5 (F(2x4, 3x3)) / mode 6 (F(2,2) on both axes) on the test's own operands (x [cin, h, w] already scaled by the
+    styles, wt [cout, cin, 3, 3]; the amplification at an element depends on the data): the float32 emulations of tests/conv_ref.py
+    (transforms, products and channel sums in float32, on the matrices and the index scheme tests/test_winograd_algebra.py proves) against
+    fp64, on the CPU: max |emulation - fp64| / (u M).  Mode 6 includes the edge lines (row 2H, column 2W), plain polyphase sums."""
+    cin, cout = x.shape[0], wt.shape[0]
+    return conv_ref.ratio_of(mode, torch.from_numpy(x)[None], torch.ones(1, cin), torch.ones(1, cout), torch.from_numpy(wt)[None])
 
-    (cin, h, w), cout = x.shape, wt.shape[0]
-    got = wa._wino_layer_f32(x, wt, wa._BT2, wa._G2, wa._AT2, wa._BT4, wa._G4, wa._AT4)
-    one = torch.ones(1, cin)
-    want, mag = conv_and_magnitude(torch.from_numpy(x)[None], one, torch.ones(1, cout), torch.from_numpy(wt)[None], False)
-    scale = 1.0 / np.sqrt(cin * 9)  # (conv_and_magnitude applies wscale; the emulation does not)
-    return float((np.abs(got.astype(np.float64) * scale - want[0].numpy()) / (U32 * mag[0].numpy())).max())
+
+def _wino2d_ratio(x, wt):
+    return _ratio(5, x, wt)
 
 
 def _up2d_ratio(x, wt):
-    """The same (on the test's own operands) for F(2,2) on both axes of the transposed convolution (mode 6): the 16 kernel entries and 16 window forms of
-    tests/test_winograd_algebra.py (up2d_pack / up2d_block) evaluated in float32, every one of the 25 products of a 2 x 2 block of positions
-    summed over the channels in float32 BEFORE the output sums, as the kernel's accumulators are; output rows 0 .. 2H-1, columns 0 .. 2W-1
-    (the edge lines are a plain polyphase form: the (9 cin + 8) u M bound of modes 0 / 1 covers them)."""
-    import test_winograd_algebra as wa
-
-    (cin, h, w), cout = x.shape, wt.shape[0]
-    u = [np.empty((cout, cin), _F) for _ in range(16)]
-    for o in range(cout):
-        for c in range(cin):
-            for k, v in enumerate(wa.up2d_pack(wt[o, c])):
-                u[k][o, c] = v
-
-    def dot(uk, v):  # [O, C] x [C] -> [O], channel after channel in float32
-        acc = np.zeros(cout, _F)
-        for c in range(cin):
-            acc = acc + uk[:, c] * v[c]
-        return acc
-
-    xp = np.pad(x, ((0, 0), (1, 1), (1, 1)))
-    got = np.zeros((cout, 2 * h, 2 * w), _F)
-    for br in range(h // 2):
-        for bc in range(w // 2):
-            win = xp[:, 2 * br: 2 * br + 3, 2 * bc: 2 * bc + 3]          # rows / columns p - 1, p, p + 1 of every channel
-            r = [win[:, 0] - win[:, 1], win[:, 1], win[:, 2] - win[:, 1], win[:, 2]]
-            b = [[rf[:, 0] - rf[:, 1], rf[:, 1], rf[:, 2] - rf[:, 1], rf[:, 2]] for rf in r]
-            ee = [[dot(u[3 * a + c], b[a][c]) for c in range(3)] for a in range(3)]
-            eo = [[dot(u[9 + a], b[a][1 + 2 * j]) for j in range(2)] for a in range(3)]
-            oe = [[dot(u[12 + c], b[1 + 2 * i][c]) for c in range(3)] for i in range(2)]
-            oo = [[dot(u[15], b[1 + 2 * i][1 + 2 * j]) for j in range(2)] for i in range(2)]
-            for i in range(2):
-                for j in range(2):
-                    got[:, 4 * br + 2 * i, 4 * bc + 2 * j] = (ee[i][j] + ee[i][j + 1]) + (ee[i + 1][j] + ee[i + 1][j + 1])
-                    got[:, 4 * br + 2 * i, 4 * bc + 2 * j + 1] = eo[i][j] + eo[i + 1][j]
-                    got[:, 4 * br + 2 * i + 1, 4 * bc + 2 * j] = oe[i][j] + oe[i][j + 1]
-                    got[:, 4 * br + 2 * i + 1, 4 * bc + 2 * j + 1] = oo[i][j]
-    assert got.dtype == _F
-    want, mag = conv_and_magnitude(torch.from_numpy(x)[None], torch.ones(1, cin), torch.ones(1, cout), torch.from_numpy(wt)[None], True)
-    scale = 1.0 / np.sqrt(cin * 9)
-    want, mag = want[0, :, :2 * h, :2 * w].numpy(), mag[0, :, :2 * h, :2 * w].numpy()
-    return float((np.abs(got.astype(np.float64) * scale - want) / (U32 * mag)).max())
+    return _ratio(6, x, wt)
 
 
 # (mode, cin, cout, h, w, batch): the minimum each kernel accepts (modes 7 / 8: cin % 16, cout % 128 / % 32, h % 8, w % 32)

@@ -5,6 +5,7 @@ are parametrised over.
 
     python tools/conv_instance_sweep.py            # on the CPU: walk the grid, record one row per distinct instance
     python tools/conv_instance_sweep.py --ratios   # on the CPU: measure the rounding amplification of modes 2 / 3 / 4 into the same file
+    python tools/conv_instance_sweep.py --dedicated  # on the CPU: the table of the dedicated kernels (modes 5 .. 8) -> conv_dedicated_instances.json
 
 The sweep asks the library's plan (maua_modconv_plan_instance: the host function maua_modconv3x3_f32 itself dispatches through, called
 without a launch, so nothing here re-implements it) for modes 0 .. 4 over a grid of small shapes (aligned and ragged channel counts,
@@ -17,7 +18,12 @@ That the table holds EVERY instance a call can reach, not only those of this gri
 feeds (conv_ref.case_operands), a float32 numpy emulation of the transforms exactly as the kernel writes them (tests/conv_ref.py) is
 compared with the fp64 direct convolution; the largest
 |emulation - fp64| / (u M) per mode, u = 2^-24, M = the convolution of the absolute values, goes into "rounding_ratio".  The GPU
-test's bound for those modes is four times that ratio: it comes from the transforms' arithmetic, not from the kernel under test."""
+test's bound for those modes is four times that ratio: it comes from the transforms' arithmetic, not from the kernel under test.
+
+--dedicated: modes 5 .. 8 (csrc/modconv_w2d.hip, modconv_up2d.hip, modconv_sbf16.hip) have no plan function, so their rows are LISTED below,
+each with the reason for its shape and the instance name a reading of the launchers expects; tests/test_conv_dedicated_gpu.py asserts
+the name on every launch.  Per row the rounding ratio R of modes 5 / 6 is measured on the operands the GPU test feeds (the pre-scaled ones
+for the s == NULL instances) and the workspace size is asked of the library."""
 import argparse
 import itertools
 import json
@@ -120,9 +126,73 @@ def ratios():
     print(doc["rounding_ratio"])
 
 
+OUT_DEDICATED = os.path.join(REPO, "tests", "golden", "conv_dedicated_instances.json")
+W2D, W2DW, UP2D = "modconv_w2d_kernel<%s, %s>", "modconv_w2dw_kernel<%s>", "modconv_up2d_kernel<%d, %d, %s, %d>"
+# (entry, mode, cin, cout, h, w, batch, pre, name, why this shape)
+DEDICATED = [
+    # ---- mode 5 through maua_modconv3x3_f32.  64-channel m-tiles x 8 rows x 32 columns; K chunks of 4 channels
+    ("modconv3x3", 5, 4, 64, 8, 32, 1, False, W2D % ("4, 2, 2", "false"), "the minimum: one tile, one K chunk"),
+    ("modconv3x3", 5, 12, 128, 16, 64, 3, False, W2D % ("4, 2, 2", "false"), "2 x 2 x 2 tiles (x, y, channels), 3 images, 3 K chunks"),
+    ("modconv3x3", 5, 4, 64, 8, 32, 1, True, W2D % ("4, 2, 2", "true"), "the minimum, pre-scaled input"),
+    # 32 channels, h % 16 != 0: the 8-row tile of the general kernel
+    ("modconv3x3", 5, 4, 32, 8, 32, 1, False, W2D % ("2, 2, 3", "false"), "the minimum: h % 16 != 0 keeps the general kernel"),
+    ("modconv3x3", 5, 20, 32, 24, 64, 2, False, W2D % ("2, 2, 3", "false"), "2 x 3 tiles, 2 images, 5 K chunks; h % 16 != 0"),
+    ("modconv3x3", 5, 4, 32, 8, 32, 1, True, W2D % ("2, 2, 3", "true"), "the minimum, pre-scaled input"),
+    # 32 channels, h % 16 == 0: the wave-complete kernel on 16-row tiles
+    ("modconv3x3", 5, 4, 32, 16, 32, 1, False, W2DW % "false", "the minimum: one 16-row tile"),
+    ("modconv3x3", 5, 20, 32, 32, 96, 2, False, W2DW % "false", "3 x 2 tiles, 2 images, 5 K chunks"),
+    ("modconv3x3", 5, 4, 32, 16, 32, 1, True, W2DW % "true", "the minimum, pre-scaled input"),
+    # ---- mode 6 through maua_modconv3x3_f32.  32-channel m-tiles x 8 x 32 positions; K chunks of 8 channels where cin % 8 == 0, else 4
+    ("modconv3x3", 6, 4, 32, 8, 32, 1, False, UP2D % (4, 0, "false", 32), "the minimum: cin % 8 != 0"),
+    ("modconv3x3", 6, 12, 64, 16, 64, 2, False, UP2D % (4, 0, "false", 32), "2 x 2 x 2 tiles, 2 images, 3 K chunks of 4"),
+    ("modconv3x3", 6, 4, 32, 8, 32, 1, True, UP2D % (4, 0, "true", 32), "the minimum, pre-scaled input"),
+    ("modconv3x3", 6, 8, 32, 8, 32, 1, False, UP2D % (8, 0, "false", 32), "the minimum: one K chunk of 8"),
+    ("modconv3x3", 6, 24, 96, 24, 96, 3, False, UP2D % (8, 0, "false", 32), "3 x 3 x 3 tiles, 3 images, 3 K chunks of 8"),
+    ("modconv3x3", 6, 8, 32, 8, 32, 1, True, UP2D % (8, 0, "true", 32), "the minimum, pre-scaled input"),
+    # ---- maua_upconv_blur_f32: 60-column x tiles, vertical segments of tiles (H / 8 + 1 tiles in all)
+    ("upconv_blur", 6, 8, 32, 8, 32, 1, False, UP2D % (8, 2, "false", 32), "the minimum: one segment"),
+    ("upconv_blur", 6, 8, 32, 32, 32, 3, False, UP2D % (8, 2, "false", 32), "5 y tiles in several segments, the last one shorter; two x tiles; 3 images"),
+    ("upconv_blur", 6, 24, 64, 16, 96, 2, False, UP2D % (8, 2, "false", 32), "four x tiles, two channel tiles, 3 K chunks, 2 images"),
+    ("upconv_blur", 6, 8, 32, 8, 32, 1, True, UP2D % (8, 2, "true", 32), "the minimum, pre-scaled input"),
+    # ---- maua_upconv_blur_lowres_f32(up = 6): 16 x 16-position tiles, K split over workgroups
+    ("upconv_blur_lowres", 6, 8, 32, 16, 16, 1, False, UP2D % (8, 0, "false", 16), "the minimum: one slab"),
+    ("upconv_blur_lowres", 6, 72, 32, 16, 16, 2, False, UP2D % (8, 0, "false", 16), "nine chunks in two splits of 5 + 4"),
+    ("upconv_blur_lowres", 6, 136, 64, 16, 16, 2, False, UP2D % (8, 0, "false", 16), "seventeen chunks in four splits, the last of 2"),
+    # ---- modes 7 / 8 (side measurements)
+    ("modconv3x3", 7, 16, 128, 8, 32, 1, False, "modconv_sbf16_kernel<-1>", "the minimum"),
+    ("modconv3x3", 7, 48, 128, 16, 64, 2, False, "modconv_sbf16_kernel<-1>", "2 x 2 tiles, 2 images, 3 K chunks: the fused tail with per-image noise"),
+    ("modconv3x3", 8, 16, 32, 8, 32, 1, False, "modconv_sbf16_up_kernel", "the minimum"),
+    ("modconv3x3", 8, 32, 64, 16, 64, 2, False, "modconv_sbf16_up_kernel", "2 x 2 x 2 tiles, 2 images"),
+]
+
+
+def dedicated(out=None):
+    import conv_ref
+    from maua_stylegan2_amd import _lib
+
+    lib = _lib.load()
+    rows = []
+    for entry, mode, cin, cout, h, w, b, pre, name, why in DEDICATED:
+        if entry == "upconv_blur":
+            n = lib.maua_upconv_blur_ws_floats(b, cin, cout, h, w)
+        elif entry == "upconv_blur_lowres":
+            n = lib.maua_lowres_ws_floats(b, cin, cout, h, w, 6)
+        else:
+            n = lib.maua_modconv_ws_floats(b, cin, cout, h, w, mode)
+        r = round(conv_ref.rounding_ratio(mode, cin, cout, h, w, b, pre=pre), 2) if mode in (5, 6) else None
+        rows.append(dict(entry=entry, mode=mode, cin=cin, cout=cout, h=h, w=w, batch=b, pre=pre, name=name, ws_floats=int(n), R=r, why=why))
+        print(rows[-1], flush=True)
+    dump({"generated_by": "tools/conv_instance_sweep.py --dedicated (CPU)", "instances": rows}, out or OUT_DEDICATED)
+    print(f"{len(rows)} rows -> {out or OUT_DEDICATED}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="write the sweep's table here instead of tests/golden/conv_instances.json")
     ap.add_argument("--ratios", action="store_true", help="CPU: measure the rounding ratios of modes 2, 3, 4 into the table")
+    ap.add_argument("--dedicated", action="store_true", help="CPU: write the table of the dedicated kernels (modes 5 .. 8)")
     args = ap.parse_args()
-    ratios() if args.ratios else sweep(args.out)
+    if args.dedicated:
+        dedicated(args.out)
+    else:
+        ratios() if args.ratios else sweep(args.out)
