@@ -437,6 +437,19 @@ int maua_jpeg_header(int h, int w, int quality, int restart_mcus, uint8_t* h_buf
 int64_t maua_jpeg_ws_bytes(int batch, int h, int w, int restart_mcus);
 int maua_jpeg_encode_u8(const uint8_t* rgb, int batch, int h, int w, int quality, int restart_mcus, const uint8_t* header, int header_len,
                         uint8_t* out, int64_t slot_bytes, void* ws, void* stream);
+/* Temporal supersampling (csrc/temporal_fold.hip): in[groups * subframes, frame_bytes] -> out[groups, frame_bytes], every output frame the
+ * weighted average of `subframes` consecutive input frames.  A frame is a flat run of bytes (H * W * 3 for packed RGB).  With weights
+ * w_i and W = sum w_i, in 32-bit unsigned integers (`/` is floor, so the rounding is half up), bit for bit:
+ *   both tables NULL (encoded light)  out[g][j] = (sum_i w_i * in[g N + i][j] + W / 2) / W
+ *   both tables given (linear light)  L = (sum_i w_i * decode[in[g N + i][j]] + W / 2) / W,  out[g][j] = max{ v : encode_threshold[v] <= L }
+ * `weights`: a HOST pointer to `subframes` bytes, copied into the kernel arguments (the launch is capturable: one launch on `stream`, no
+ * allocation, no synchronisation).  decode / encode_threshold: DEVICE tables of 256 entries; the caller guarantees encode_threshold[0] ==
+ * 0 and a non-decreasing table.  MAUA_EINVAL (before any HIP call) for subframes outside 1 .. 16, W == 0, frame_bytes <= 0, groups < 0,
+ * exactly one table, a NULL pointer, or out overlapping in; groups == 0 is a successful no-op, more than 65535 groups a launch are
+ * MAUA_ENOSYS.  Any frame size and any alignment of in and out is served: frame_bytes % 16 == 0 with in and out at the same offset from a
+ * 16-byte boundary takes the 16-byte vector path, everything else goes byte by byte.  (Additive: the ABI version is unchanged.) */
+int maua_temporal_fold_u8(const uint8_t* in, uint8_t* out, int groups, int subframes, int64_t frame_bytes, const uint8_t* weights,
+                          const uint16_t* decode, const uint16_t* encode_threshold, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ audio / temporal
  * Circular Gaussian FIR along time (audioreactive/signal.py:319-368): x [T, F] -> y [T, F], taps[2*radius+1]

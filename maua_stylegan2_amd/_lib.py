@@ -129,6 +129,7 @@ _SIGNATURES = {
     "maua_jpeg_header": (c_int, [c_int] * 4 + [_P, c_int]),
     "maua_jpeg_ws_bytes": (c_int64, [c_int] * 4),
     "maua_jpeg_encode_u8": (c_int, [_P] + [c_int] * 5 + [_P, c_int, _P, c_int64, _P, _P]),
+    "maua_temporal_fold_u8": (c_int, [_P, _P, c_int, c_int, c_int64, _P, _P, _P, _P]),
     "maua_sg1_epilogue_f32": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "maua_temporal_fir_f32": (c_int, [_P, _P, _P, c_int, c_int64, c_int, _P]),
     "maua_stft_power_f32": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P]),

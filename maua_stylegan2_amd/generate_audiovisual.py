@@ -11,6 +11,10 @@ What is different: features come from HIP STFT/mel/chroma kernels, latents and n
 hipGraph-replayed, frames leave as uint8, and under ``torchrun`` every GPU renders a contiguous shard of the frames
 (``--dataparallel`` is accepted and ignored).  Importing this module aliases ``audioreactive``, ``render``,
 ``models.stylegan2`` and ``op`` to this package's mirrors so unmodified reference plugin files run.
+
+Temporal supersampling (not in the reference): ``--fps F --subframes N`` is ``--fps F * N`` up to and including synthesis; the frames are
+then folded N:1 on the device (``--shutter``, ``--shutter_light``; render.TemporalFold) and written at F.  ``--batch`` must be a multiple
+of N.
 """
 import argparse
 import gc
@@ -62,6 +66,11 @@ CLI_FLAGS = (
     # ... or one baseline JPEG per frame, render.frames_to_mjpeg, at --mjpeg_quality 1 .. 95)
     ("--pipe_pix_fmt", dict(type=str, default="rgb24", choices=render.PIPE_PIX_FMTS)),
     ("--mjpeg_quality", dict(type=int, default=render.MJPEG_DEFAULT_QUALITY)),
+    # (temporal supersampling, render.TemporalFold: --fps F --subframes N is --fps F * N up to and including synthesis; the frames are then
+    # folded N:1 on the device and written at F)
+    ("--subframes", dict(type=int, default=1, help="sub-frames rendered and averaged per video frame (1 .. 16)")),
+    ("--shutter", dict(type=str, default="box", help="box, tent or N comma-separated integer weights, e.g. 1,1,0,0")),
+    ("--shutter_light", dict(type=str, default="encoded", choices=render.SHUTTER_LIGHTS)),
 )
 
 
@@ -182,18 +191,33 @@ def _collect_noise(get_noise, args, out_size, G_res, stylegan1, header=None):
     return maps
 
 
-def _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames):
+def _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames, subframes=1):
     """One process per GPU: rank 0 ran the audio front end and the callbacks; every rank receives only its contiguous
     block of the per-frame inputs (sharding.scatter_frames).  Bend modulations are broadcast (they are [n_frames, k]
-    vectors) and cut to the block here, because the transforms that consume them are closures every rank built itself."""
+    vectors) and cut to the block here, because the transforms that consume them are closures every rank built itself.
+    ``subframes`` N > 1 (a temporal fold): the job is sharded in units of delivered frames — every per-frame tensor travels as
+    [n_frames / N, N, ...] — so that a rank's block, render.fold_shard_bounds, holds whole groups of sub-frames."""
     rank, world = sharding.rank_world()
     dev = th.device("cuda", th.cuda.current_device()) if th.cuda.is_available() else th.device("cpu")
     on_dev = lambda t: None if t is None else t.to(dev, th.float32).contiguous()  # noqa: E731
-    latents = sharding.scatter_frames(on_dev(latents), n_frames, device=dev)
+    if subframes == 1:
+        scatter = lambda t: sharding.scatter_frames(t, n_frames, device=dev)  # noqa: E731
+    else:
+        if n_frames % subframes:
+            raise RuntimeError(f"{n_frames} frames are not whole groups of {subframes} sub-frames")
+        n_out = n_frames // subframes
+
+        def scatter(t):
+            if t is not None and t.shape[0] != n_frames:
+                raise RuntimeError(f"per-frame tensor has {t.shape[0]} entries for {n_frames} frames")
+            block = sharding.scatter_frames(None if t is None else t.reshape((n_out, subframes) + tuple(t.shape[1:])), n_out, device=dev)
+            return None if block is None else block.flatten(0, 1)
+
+    latents = scatter(on_dev(latents))
     # NoiseSynth recipes are broadcast, not scattered: their structure rides along with the slot count (a job without recipes sends the
     # plain count, as before), their tensors — loops, envelopes, masks: small next to a per-frame sequence — follow one by one, and every
     # rank cuts its frames out with ``window``, which copies nothing
-    lo, hi = sharding.shard_bounds(n_frames, rank, world)
+    lo, hi = render.fold_shard_bounds(n_frames, subframes, rank, world)
     recipes = {i: nz for i, nz in enumerate(noise) if isinstance(nz, ar.NoiseSynth)} if rank == 0 else {}
     head = sharding.broadcast_object((len(noise) if not recipes else (len(noise), {i: nz.structure() for i, nz in recipes.items()}))
                                      if rank == 0 else None)
@@ -210,12 +234,12 @@ def _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames):
                 raise RuntimeError(f"noise[{i}]: the recipe's envelopes cover {recipe.n_frames} frames, the job has {n_frames}")
             noise[i] = recipe.window(lo, hi)
         else:
-            noise[i] = sharding.scatter_frames(on_dev(noise[i]) if rank == 0 else None, n_frames, device=dev)
+            noise[i] = scatter(on_dev(noise[i]) if rank == 0 else None)
     is_float = sharding.broadcast_object(isinstance(truncation, float) if rank == 0 else None)
     if is_float:
         truncation = float(sharding.broadcast_object(truncation if rank == 0 else None))
     else:
-        truncation = sharding.scatter_frames(on_dev(truncation) if rank == 0 else None, n_frames, device=dev)
+        truncation = scatter(on_dev(truncation) if rank == 0 else None)
     for bend in bends:
         if "modulation" in bend:
             bend["modulation"] = sharding.broadcast_tensor(on_dev(bend["modulation"]))[lo:hi]
@@ -234,6 +258,16 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     if args is None:  # direct (notebook) call: the namespace is this call's own arguments, as in the reference (:94-98)
         args = argparse.Namespace(**{k: v for k, v in locals().items() if k != "args"})
         args.args = None
+
+    # Temporal supersampling (generate() keeps the reference's parameter list: --subframes / --shutter / --shutter_light arrive in the
+    # namespace, as the pipe format does).  ``--fps F --subframes N`` IS ``--fps F * N`` up to and including synthesis — args.fps, the
+    # smoothing factor and args.n_frames are those of the rendered rate, so plugins that count frames or smooth in seconds stay right —;
+    # the frames are then folded N:1 on the device and written at F (args.video_fps).
+    fold = _fold_of(args)
+    subframes = 1 if fold is None else fold.subframes
+    args.video_fps, args.subframes = fps, subframes
+    if subframes > 1:
+        args.fps = fps * subframes
 
     started = time.time()
     th.set_grad_enabled(False)
@@ -279,7 +313,7 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         args.audio, args.sr, duration = ar.load_audio(audio_file, offset, duration)
     duration = float(sharding.broadcast_object(duration if rank == 0 else None))
     args.duration = duration
-    args.n_frames = n_frames = int(round(duration * fps))
+    args.n_frames = n_frames = subframes * int(round(duration * fps))  # (delivered frames = round(duration * fps), N rendered for each)
     if front_end:
         if initialize is not None:
             args = initialize(args)
@@ -320,8 +354,11 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
 
     shard = None
     if grouped:
-        latents, noise, truncation = _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames)
-        lo, hi = sharding.shard_bounds(n_frames, rank, world)
+        if subframes > 1:
+            latents, noise, truncation = _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames, subframes)
+        else:
+            latents, noise, truncation = _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames)
+        lo, hi = render.fold_shard_bounds(n_frames, subframes, rank, world)
         shard = (lo, hi, n_frames)
 
     # (reference :191-192.)  The job's one collection — 45-70 ms on this heap.  Full on purpose where it runs: young-generation collections
@@ -355,7 +392,7 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # a caller's own ``args``) or through $MAUA_PIPE_PIX_FMT
         written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
                           output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
-                          getattr(args, "mjpeg_quality", None))
+                          getattr(args, "mjpeg_quality", None), *((fold,) if subframes > 1 else ()))
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -365,11 +402,23 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     return output_file
 
 
+def _fold_of(args):
+    """The temporal fold a namespace asks for (``subframes``, ``shutter``, ``shutter_light``: the CLI flags, a plugin's OVERRIDE or a
+    caller's own ``args``): a render.TemporalFold, or None for one sub-frame — the plain render, whatever the other two say."""
+    subframes = getattr(args, "subframes", None)
+    if subframes is None or subframes == 1:
+        return None
+    return render.TemporalFold(subframes, getattr(args, "shutter", None) or "box", getattr(args, "shutter_light", None) or "encoded")
+
+
 def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
-            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None, mjpeg_quality=None):
+            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None, mjpeg_quality=None, fold=None):
     if pipe_pix_fmt == "mjpeg" and mjpeg_quality is not None:
         pipe_pix_fmt = f"mjpeg:{mjpeg_quality}"  # (render_shard's parameter list is pinned: the quality travels in the format's name)
-    if pipe_pix_fmt not in (None, "rgb24"):
+    if fold is not None and fold.subframes > 1:  # (latents and every per-frame input hold N rows per delivered frame)
+        written = render.render_folded(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
+                                       truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt, fold=fold)
+    elif pipe_pix_fmt not in (None, "rgb24"):
         written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
                                       truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt)
     elif shard is None:
@@ -434,6 +483,8 @@ def main(argv=None):
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     settings.pop("mjpeg_quality", None)
+    for key in ("subframes", "shutter", "shutter_light"):
+        settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)
     finally:

@@ -23,9 +23,12 @@ Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to plan
 they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
 Opt-in pipe format ``mjpeg`` (``mjpeg:<quality>``): every frame is encoded as one baseline JPEG on the device (frames_to_mjpeg) and travels
 in a fixed-size slot; the sink writes the streams alone, to ``ffmpeg -f mjpeg`` or, without a binary, to a playable Motion-JPEG .avi (avi.py).
+Opt-in temporal supersampling (TemporalFold, ``render_folded``; $MAUA_SUBFRAMES for the pinned entries): N rendered sub-frames per delivered
+frame, averaged on the device by fold_frames before any of the above; the sink and the transports then count delivered frames.
 """
 import collections
 import contextlib
+import ctypes
 import gc
 import os
 import queue
@@ -359,8 +362,135 @@ def frames_to_mjpeg(u8, scratch, quality):
     return out
 
 
-def _deliverable(u8, out_size, pix_fmt, scratch, quality=None):
-    """A batch as it leaves the device: wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0 or — mjpeg — encoded."""
+MAX_SUBFRAMES = 16
+SHUTTER_LIGHTS = ("encoded", "linear")
+
+
+def shutter_weights(shutter, subframes):
+    """The integer weights (0 .. 255, not all zero) of a shutter over ``subframes`` sub-frames: "box" (all ones), "tent"
+    (w_i = min(i + 1, N - i)) or a comma-separated list of N integers — "1,1,0,0" is a 180 degree shutter."""
+    n = subframes
+    if shutter == "box":
+        return (1,) * n
+    if shutter == "tent":
+        return tuple(min(i + 1, n - i) for i in range(n))
+    try:
+        weights = tuple(int(part) for part in str(shutter).split(","))
+    except ValueError:
+        raise ValueError(f"shutter {shutter!r} is neither box, tent nor a comma-separated list of integers") from None
+    if len(weights) != n:
+        raise ValueError(f"shutter {shutter!r} lists {len(weights)} weights for {n} sub-frames")
+    if any(not 0 <= w <= 255 for w in weights):
+        raise ValueError(f"shutter {shutter!r}: weights are integers in 0 .. 255")
+    if not any(weights):
+        raise ValueError(f"shutter {shutter!r}: the weights must not all be zero")
+    return weights
+
+
+class TemporalFold:
+    """Temporal supersampling: ``subframes`` (1 .. 16) consecutive rendered frames are averaged into one delivered frame on the device
+    (fold_frames) with the integer ``weights`` of ``shutter`` (shutter_weights), on the frames' encoded values (``light="encoded"``) or on
+    linear light through the sRGB transfer function (``light="linear"``, srgb_fold_tables).  Sub-frames of weight zero are still rendered."""
+
+    def __init__(self, subframes, shutter="box", light="encoded"):
+        if isinstance(subframes, bool) or int(subframes) != subframes or not 1 <= int(subframes) <= MAX_SUBFRAMES:
+            raise ValueError(f"subframes must be an integer in 1 .. {MAX_SUBFRAMES}, got {subframes!r}")
+        if light not in SHUTTER_LIGHTS:
+            raise ValueError(f"unknown shutter light {light!r} ({' | '.join(SHUTTER_LIGHTS)})")
+        self.subframes = int(subframes)
+        self.shutter = shutter
+        self.light = light
+        self.weights = shutter_weights(shutter, self.subframes)
+
+    def __repr__(self):
+        return f"TemporalFold({self.subframes}, shutter={self.shutter!r}, light={self.light!r})"
+
+
+def _fold_from_env():
+    """The fold of a render whose parameter list is pinned (render, render_shard): $MAUA_SUBFRAMES, $MAUA_SHUTTER (box),
+    $MAUA_SHUTTER_LIGHT (encoded).  $MAUA_SUBFRAMES unset, empty or 1: no fold."""
+    text = os.environ.get("MAUA_SUBFRAMES")
+    if not text:
+        return None
+    try:
+        subframes = int(text)
+    except ValueError:
+        raise ValueError(f"$MAUA_SUBFRAMES {text!r} is not an integer") from None
+    if subframes == 1:  # the plain render, whatever the other two say
+        return None
+    return TemporalFold(subframes, os.environ.get("MAUA_SHUTTER") or "box", os.environ.get("MAUA_SHUTTER_LIGHT") or "encoded")
+
+
+def _subframes(fold):
+    """Rendered frames per delivered frame: 1 without a fold."""
+    return 1 if fold is None else fold.subframes
+
+
+def srgb_fold_tables():
+    """The two 256-entry uint16 tables of a linear-light fold, numpy, built in float64 from the piecewise sRGB transfer function (IEC
+    61966-2-1): decode[v] = rint(65535 * srgb_to_linear(v / 255)) and encode_threshold[v] = the smallest 16-bit L whose
+    rint(255 * linear_to_srgb(L / 65535)) is >= v.  The encoding is monotone in L, so max{v : encode_threshold[v] <= L} IS the encoding
+    of L; encode(decode[v]) == v for every v (tests/test_temporal_fold_host.py)."""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    decode = np.rint(65535.0 * np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4)).astype(np.uint16)
+    lin = np.arange(65536, dtype=np.float64) / 65535.0
+    encoded = np.rint(255.0 * np.where(lin <= 0.0031308, 12.92 * lin, 1.055 * lin ** (1.0 / 2.4) - 0.055)).astype(np.int64)
+    threshold = np.searchsorted(encoded, np.arange(256), side="left").astype(np.uint16)  # (encoded is non-decreasing and reaches 255)
+    return decode, threshold
+
+
+def check_fold_tables(decode, encode_threshold):
+    """What csrc/temporal_fold.hip assumes of its tables: 256 uint16 entries each, encode_threshold[0] == 0, non-decreasing thresholds."""
+    decode, encode_threshold = np.asarray(decode), np.asarray(encode_threshold)
+    for name, table in (("decode", decode), ("encode_threshold", encode_threshold)):
+        if table.shape != (256,) or table.dtype != np.uint16:
+            raise ValueError(f"{name} must hold 256 uint16 entries, got {table.dtype} {tuple(table.shape)}")
+    if encode_threshold[0] != 0 or np.any(np.diff(encode_threshold.astype(np.int64)) < 0):
+        raise ValueError("encode_threshold must start at 0 and must not decrease")
+    return decode, encode_threshold
+
+
+_FOLD_TABLES = {}  # device index -> (decode, encode_threshold) of srgb_fold_tables on that device (uint16 bits in int16 tensors)
+
+
+def _device_fold_tables(dev):
+    index = dev.index if dev.index is not None else th.cuda.current_device()
+    tables = _FOLD_TABLES.get(index)
+    if tables is None:
+        host = check_fold_tables(*srgb_fold_tables())
+        tables = _FOLD_TABLES[index] = tuple(th.from_numpy(t.view(np.int16).copy()).to(dev) for t in host)
+    return tables
+
+
+def fold_frames(u8, fold, scratch):
+    """uint8 [b, ...] device frames -> [b // N, ...] on the current (= producing) stream: frame g of the result is the weighted average of
+    the frames g N .. g N + N - 1 (TemporalFold; maua_temporal_fold_u8 states the arithmetic).  ``scratch``: dict holding the reusable
+    output buffers, keyed by the input buffer (the protocol of crop_resize_for_delivery: the lanes' batches are in flight concurrently)."""
+    if u8.dim() < 2 or u8.dtype != th.uint8 or not u8.is_cuda:
+        raise RuntimeError(f"fold_frames takes uint8 [b, ...] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
+    n = fold.subframes
+    b = u8.shape[0]
+    if b % n:
+        raise ValueError(f"a batch of {b} frames does not hold whole groups of {n} sub-frames")
+    u8 = u8.contiguous()
+    frame_bytes = int(np.prod(u8.shape[1:]))
+    key = ("fold", u8.data_ptr(), b, n, tuple(u8.shape[1:]))
+    out = scratch.get(key)
+    if out is None:
+        out = scratch[key] = th.empty((b // n,) + tuple(u8.shape[1:]), dtype=th.uint8, device=u8.device)
+    decode, threshold = _device_fold_tables(u8.device) if fold.light == "linear" else (None, None)
+    weights = (ctypes.c_uint8 * n)(*fold.weights)
+    with th.cuda.device(u8.device):
+        _lib.check(_lib.load().maua_temporal_fold_u8(u8.data_ptr(), out.data_ptr(), b // n, n, frame_bytes, weights, _lib.ptr(decode),
+                                                     _lib.ptr(threshold), _lib.stream_ptr(u8.device)), "maua_temporal_fold_u8")
+    return out
+
+
+def _deliverable(u8, out_size, pix_fmt, scratch, quality=None, fold=None):
+    """A batch as it leaves the device: the sub-frames of a temporal fold averaged (on the generator's own frames, so that every later
+    stage sees delivered frames only), wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0 or — mjpeg — encoded."""
+    if _subframes(fold) > 1:
+        u8 = fold_frames(u8, fold, scratch)
     u8 = crop_resize_for_delivery(u8, out_size, scratch)
     if pix_fmt == "mjpeg":
         return frames_to_mjpeg(u8, scratch, MJPEG_DEFAULT_QUALITY if quality is None else quality)
@@ -814,8 +944,37 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames.
     ``pipe_pix_fmt``: "rgb24", "yuv420p", "mjpeg" or "mjpeg:<quality>" (PIPE_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24) — what
     crosses to the host, to rank 0 and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the
-    environment variable."""
+    environment variable.  This parameter list is pinned as well: a temporal fold comes from $MAUA_SUBFRAMES, $MAUA_SHUTTER and
+    $MAUA_SHUTTER_LIGHT (_fold_from_env; unset: none) — ``render_folded`` takes it as an argument."""
+    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, _fold_from_env())
+
+
+def render_folded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None):
+    """``render_shard`` with an explicit ``fold`` (TemporalFold or None; the environment is not read): ``latents`` and every per-frame input
+    hold ``fold.subframes`` rows per delivered frame, each batch is folded N:1 on the device before anything else happens to it, the sink
+    runs at delivered frames / duration and the return value counts delivered frames.  ``batch_size`` and the frame count (of the job and
+    of every rank's block: ``_shard`` stays in rendered frames) must be multiples of N."""
+    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold)
+
+
+def fold_shard_bounds(n_frames, subframes, rank, world):
+    """[lo, hi) of a rank's block in RENDERED frames when every delivered frame is folded from ``subframes`` of them: the job is sharded in
+    units of delivered frames (sharding.shard_bounds of n_frames / N), so that no group straddles two ranks."""
+    lo, hi = sharding.shard_bounds(n_frames // subframes, rank, world)
+    return subframes * lo, subframes * hi
+
+
+def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold):
+    """The body of render_shard / render_folded.  ``fold`` None or of one sub-frame: the plain render, call for call."""
     width, height = _output_dims(out_size)
+    subframes = _subframes(fold)
+    if batch_size % subframes:
+        raise ValueError(f"--batch {batch_size} is not a multiple of --subframes {subframes}: a batch must hold whole groups of sub-frames "
+                         f"(e.g. --batch {subframes * max(1, round(batch_size / subframes))})")
     quality = _mjpeg_quality(pipe_pix_fmt) if _pipe_pix_fmt(pipe_pix_fmt) == "mjpeg" else None
     pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
     rank, world = sharding.rank_world()
@@ -825,16 +984,20 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
         raise ValueError(f"unknown frame transport {transport!r} (gather | host)")
     if _shard is None:
         n_frames = len(latents)
-        lo, hi = sharding.shard_bounds(n_frames, rank, world)  # (no process group: rank 0 of 1, every frame)
+        lo, hi = fold_shard_bounds(n_frames, subframes, rank, world)  # (no process group: rank 0 of 1, every frame)
         frame_range = (lo, hi)
     else:
         lo, hi, n_frames = _shard
         frame_range = (0, hi - lo)
+    if n_frames % subframes or lo % subframes or hi % subframes:
+        raise ValueError(f"{n_frames} rendered frames (this rank's: {lo} .. {hi}) are not whole groups of {subframes} sub-frames")
+    # what the sink and the transports count: delivered frames — n_frames and batch_size themselves without a fold
+    n_out, batch_out = n_frames // subframes, batch_size // subframes
     dev = device_of(generator)
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
-            sink = FrameSink(output_file, width, height, n_frames / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt,
+            sink = FrameSink(output_file, width, height, n_out / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt,
                              quality=quality)
             unwind.callback(sink.close)  # the encoder process / output file must not outlive a failed render: closed last, and always
             worker = SinkWorker(sink)
@@ -850,15 +1013,15 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
         # 45-90 ms up front, as much as it saves on a 900-frame job; generate() has just run one, as the reference does.)
         with parked_heap():
             if not sharding.grouped():
-                delivery = _LocalRing(dev, batch_size, worker)
+                delivery = _LocalRing(dev, batch_out, worker)
             else:
-                delivery = (_HostStore if transport == "host" else _GatherStream)(n_frames, batch_size, dev, rank, worker)
+                delivery = (_HostStore if transport == "host" else _GatherStream)(n_out, batch_out, dev, rank, worker)
             with contextlib.closing(delivery):
                 scratch = {}  # the reusable output buffers of the device-side crop / resize / conversion
                 # (lanes: synthesize's default, 3, on every path)
                 for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
                                         frame_range=frame_range):
-                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality))  # 2048-px frames leave the device as 1920x1080 already
+                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold))  # 2048-px frames leave the device as 1920x1080 already
                 delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt))
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
