@@ -506,6 +506,30 @@ int maua_chroma_cens_f32(const float* ch, float* out, int n_bins, int n_frames, 
 int64_t maua_nn_median_ws_doubles(int n_bins, int n_frames, int k);
 int maua_nn_median_f32(const float* ch, float* out, int n_bins, int n_frames, int k, int width, double* ws, void* stream);
 
+/* Monophonic pitch tracking (audioreactive raw_pitch / pitch; csrc/pitch.hip; additive: the ABI version is unchanged).
+ * YIN (de Cheveigne & Kawahara 2002, steps 1-5) on centred frames.  n_frames must equal 1 + n_samples / hop.
+ *   Framing.  L = frame + tau_max.  Frame t reads L samples starting at t * hop - L / 2 (integer division); samples outside
+ *     [0, n_samples) are 0.  x[j] below is frame-relative.
+ *   Difference function.  d(0) = 0; for tau = 1 .. tau_max, d(tau) = sum_{j=0}^{frame-1} (x[j] - x[j + tau])^2, the direct sum of squares
+ *     (not the energy / FFT form, which cancels).
+ *   Normalised difference (CMNDF).  d'(0) = 1; for tau >= 1, d'(tau) = d(tau) tau / sum_{k=1}^{tau} d(k) when that sum is > 0, else 1.
+ *   Pick.  The smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then advanced while tau + 1 <= tau_max and
+ *     d'(tau + 1) < d'(tau); if no lag is below the threshold, the first global minimum of d' over [tau_min, tau_max].  That is tau_int.
+ *   Refine.  a, b, c = d'(tau - 1), d'(tau), d'(tau + 1).  If tau - 1 >= 1, tau + 1 <= tau_max and a - 2 b + c > 0:
+ *     shift = clamp(0.5 (a - c) / (a - 2 b + c), -0.5, 0.5), lag = tau + shift, aperiodicity = max(0, b - 0.25 (a - c) shift) (the
+ *     unclamped parabola dips slightly below 0 on clean tones); otherwise lag = tau and aperiodicity = b.
+ *   The sample rate never enters: the host computes f0 = sr / lag.
+ * MAUA_EINVAL, before any device call: a NULL y / lag / aperiodicity / tau_int, frame outside 16 .. MAUA_YIN_MAX_FRAME, not
+ *   1 <= tau_min < tau_max <= MAUA_YIN_MAX_LAG, hop < 1, n_samples < 1, a threshold that is negative or not finite,
+ *   n_frames != 1 + n_samples / hop.
+ * Deterministic run to run, capturable, no workspace.  A non-finite sample may make the frames that cover it arbitrary, but their tau_int
+ *   stays inside [tau_min, tau_max]; it never changes a frame that does not cover it. */
+#define MAUA_YIN_MAX_FRAME 4096
+#define MAUA_YIN_MAX_LAG 2048
+int maua_yin_f32(const float* y, int64_t n_samples, int frame, int hop, int tau_min, int tau_max, float threshold,
+                 float* lag /*[n_frames]*/, float* aperiodicity /*[n_frames]*/, int32_t* tau_int /*[n_frames]*/,
+                 float* cmndf /*[n_frames, tau_max + 1] or NULL*/, int n_frames, void* stream);
+
 /* Structural segmentation (audioreactive laplacian_segmentation, ABI 6).  Every entry is deterministic run to run.
  * Tempogram: the onset envelope env[n_frames] padded by win/2 with a linear ramp to 0, framed with hop 1 (n_frames frames), each
  * frame times a periodic Hann window of win samples, autocorrelated over lags 0 .. win-1 (fp64), divided by its max |.| (unless

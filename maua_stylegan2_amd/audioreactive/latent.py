@@ -20,6 +20,19 @@ def chroma_weight_latents(chroma, latents):
     return th.einsum("tn,nld->tld", chroma.to(latents.device, latents.dtype), latents)
 
 
+def pitch_weight_latents(pitch, latents):
+    """[n_frames] pitch height in [0, 1] x [m, n_latent, 512] -> [n_frames, n_latent, 512]: a piecewise-linear walk along the selection
+    (the counterpart of :func:`chroma_weight_latents` for ``ar.pitch``).  With p = pitch (m - 1) a frame is
+    (1 - frac) latents[floor p] + frac latents[min(floor p + 1, m - 1)]: height 0 is the first entry, 1 the last, k / (m - 1) entry k.
+    Plain torch on the device of ``latents``."""
+    m = latents.shape[0]
+    p = pitch.to(latents.device, latents.dtype).clamp(0, 1) * (m - 1)
+    low = p.floor()
+    frac = (p - low)[:, None, None]
+    low = low.long().clamp(max=m - 1)
+    return (1 - frac) * latents[low] + frac * latents[(low + 1).clamp(max=m - 1)]
+
+
 def slerp(val, low, high):
     """Great-circle interpolation between two vectors (reference :29-45).  ``val`` may be a scalar or an array of
     fractions: all of them are evaluated at once, one row per fraction."""

@@ -567,6 +567,102 @@ def chroma(audio, sr, n_frames, margin=16, type="cens", notes=12, device=None):
     return ch.to(device if device is not None else "cpu")
 
 
+# ------------------------------------------------------------------------------------------------ pitch (no counterpart in the reference)
+YIN_MAX_FRAME, YIN_MAX_LAG = 4096, 2048  # MAUA_YIN_MAX_FRAME / MAUA_YIN_MAX_LAG (include/maua_hip.h)
+
+
+def raw_pitch(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, threshold=0.1):
+    """Fundamental frequency and voicing confidence per frame, ``(f0_hz [T], confidence [T])`` as device tensors, T = 1 + len / hop:
+    YIN (de Cheveigne & Kawahara 2002) over the lags floor(sr / fmax) .. ceil(sr / fmin) on the device (maua_yin_f32, csrc/pitch.hip; the
+    definition is the entry's comment in include/maua_hip.h).  ``confidence`` = 1 - min(aperiodicity, 1): close to 1 on a clean tone, 0
+    in silence.  f0 of an unvoiced frame is whatever lag had the smallest normalised difference."""
+    if not fmin < fmax:
+        raise ValueError(f"raw_pitch: fmin ({fmin} Hz) must be below fmax ({fmax} Hz): lower fmin or raise fmax")
+    if not fmin > 0:
+        raise ValueError(f"raw_pitch: fmin ({fmin} Hz) must be positive: raise fmin")
+    tau_min, tau_max = int(math.floor(sr / fmax)), int(math.ceil(sr / fmin))
+    if tau_min < 1:
+        raise ValueError(f"raw_pitch: fmax ({fmax} Hz) is above the sample rate ({sr} Hz), the shortest lag is one sample: lower fmax to at most {sr} Hz")
+    if tau_max > YIN_MAX_LAG:
+        raise ValueError(f"raw_pitch: fmin ({fmin} Hz) at {sr} Hz needs lags up to {tau_max} samples, the device searches at most {YIN_MAX_LAG}: "
+                         f"raise fmin to at least {sr / YIN_MAX_LAG:.2f} Hz")
+    if not 16 <= frame_length <= YIN_MAX_FRAME:
+        raise ValueError(f"raw_pitch: frame_length ({frame_length}) must lie in 16 .. {YIN_MAX_FRAME} samples")
+    if hop < 1:
+        raise ValueError(f"raw_pitch: hop ({hop}) must be at least one sample")
+    y = _to_dev(audio).reshape(-1)
+    n = y.numel()
+    n_frames = 1 + n // hop
+    lag = th.empty(n_frames, dtype=th.float32, device=y.device)
+    aperiodicity = th.empty_like(lag)
+    tau_int = th.empty(n_frames, dtype=th.int32, device=y.device)
+    with th.cuda.device(y.device):
+        _lib.check(_lib.load().maua_yin_f32(y.data_ptr(), n, int(frame_length), int(hop), tau_min, tau_max, float(threshold), lag.data_ptr(),
+                                            aperiodicity.data_ptr(), tau_int.data_ptr(), None, n_frames, _lib.stream_ptr(y.device)),
+                   "maua_yin_f32")
+    return float(sr) / lag, 1.0 - aperiodicity.clamp(max=1.0)
+
+
+def hold_fill(values, voiced):
+    """``values`` [T] with every unvoiced frame replaced by the last voiced one before it, leading unvoiced frames by the first voiced
+    one; None when no frame is voiced.  Plain torch, any device."""
+    if not bool(voiced.any()):
+        return None
+    at = th.arange(values.shape[0], device=values.device)
+    last = th.cummax(th.where(voiced, at, th.full_like(at, -1)), 0).values
+    first = int(voiced.to(th.uint8).argmax())
+    return values[th.where(last < 0, th.full_like(last, first), last)]
+
+
+def _median5(x):
+    """5-tap median along time on the device (maua_median_filter_f32, symmetric reflection at the ends)."""
+    x = x.contiguous()
+    out = th.empty_like(x)
+    with th.cuda.device(x.device):
+        _lib.check(_lib.load().maua_median_filter_f32(x.data_ptr(), out.data_ptr(), x.shape[0], 1, 5, 0, _lib.stream_ptr(x.device)),
+                   "maua_median_filter_f32")
+    return out
+
+
+def lerp_resize(x, num):
+    """Linear interpolation of x[n] (any device) at the ``num`` positions i (n - 1) / (num - 1): the end points are kept, steps stay
+    steps (the Fourier :func:`resample` rings on them)."""
+    n = x.shape[0]
+    num = int(num)
+    if n == 1 or num == 1:
+        return x[:1].expand(num).clone()
+    pos = th.arange(num, dtype=x.dtype, device=x.device) * ((n - 1) / (num - 1))
+    lo = pos.floor().long().clamp(max=n - 2)
+    frac = pos - lo.to(x.dtype)
+    return x[lo] * (1 - frac) + x[lo + 1] * frac
+
+
+def pitch(audio, sr, n_frames, fmin=65.0, fmax=2100.0, margin=8, bandpass=False, voicing=0.5, smooth=2, return_voicing=False, device=None):
+    """Pitch height of the melody in [0, 1] per video frame (0 = ``fmin``, 1 = ``fmax``, logarithmic), a CPU tensor unless ``device=`` is
+    given: harmonic separation (``margin``; None / 0 skips it) -> optionally the Butterworth band-pass of :func:`rms` over [fmin, fmax]
+    (a bass line under a lead) -> :func:`raw_pitch` -> log height -> frames less confident than ``voicing`` hold the last voiced height
+    (leading ones take the first) -> 5-tap median against octave blips -> linear interpolation to ``n_frames`` -> Gaussian smoothing.
+    The absolute height is the point: the result is neither percentile-clipped nor normalised (``ar.normalize`` does that).
+    ``return_voicing`` adds the confidence envelope, interpolated and smoothed the same way."""
+    y = harmonic(audio, margin=margin) if margin else audio
+    if bandpass:
+        y = y.detach().cpu().numpy() if isinstance(y, th.Tensor) else np.asarray(y)
+        y = scipy.signal.sosfilt(scipy.signal.butter(12, [fmin, fmax], "bp", fs=sr, output="sos"), y).astype(np.float32)
+    f0, confidence = raw_pitch(y, sr, fmin=fmin, fmax=fmax)
+    height = (th.log2(f0 / float(fmin)) / math.log2(fmax / fmin)).clamp(0.0, 1.0)
+    held = hold_fill(height, confidence >= voicing)
+    if held is None:
+        warnings.warn(f"pitch: no frame reaches the voicing confidence {voicing} between {fmin} and {fmax} Hz; returning zeros", stacklevel=2)
+        height = th.zeros_like(height)
+    else:
+        height = _median5(held)
+    out_device = device if device is not None else "cpu"
+    height = gaussian_filter(lerp_resize(height, n_frames), smooth).to(out_device)
+    if not return_voicing:
+        return height
+    return height, gaussian_filter(lerp_resize(confidence, n_frames), smooth).to(out_device)
+
+
 def laplacian_segmentation(signal, sr, k=5, plot=False):
     """Section start times and labels of a track (Laplacian structural segmentation, reference :159-240); the body is
     audioreactive/segment.py, whose docstring lists the deliberate differences from the reference."""
