@@ -544,8 +544,8 @@ int maua_tempogram_f32(const float* env, int n_frames, int win, double* ws, floa
 int maua_beat_track_f64(const double* onset, int n_frames, int period, double* localscore, double* cumscore, int* backlink,
                         void* stream);
 /* Beat-synchronous aggregation: out[r][s] = np.median (median = 1) or mean (median = 0) of x[r][bounds[s] .. bounds[s+1]) for
- * x[rows, n_frames]; bounds[n_spans + 1] increasing inside [0, n_frames] (clamped there; an empty span gives NaN).  Spans of any
- * length. */
+ * x[rows, n_frames]; bounds[n_spans + 1] increasing inside [0, n_frames] (clamped there: a bound outside [0, n_frames] is moved to
+ * the nearer end, a bound below an earlier one is raised to it; an empty span gives NaN).  Spans of any length. */
 int maua_beat_sync_f32(const float* x, int rows, int n_frames, const int* bounds, int n_spans, int median, float* out, void* stream);
 /* k-nearest-neighbour links of the columns of x[d, s] (d <= 1024, 2 <= s <= 8192): row i links the k columns j with |i - j| >= width
  * of smallest fp32 Euclidean distance (ties to the lower j); links[i][j] = that distance on a link, -1 elsewhere.  The squares are summed

@@ -230,8 +230,14 @@ __global__ __launch_bounds__(256) void beat_sync_kernel(const float* __restrict_
     const int s = blockIdx.x;
     const int r = blockIdx.y * 4 + wid;
     const bool active = r < rows;
-    int b0 = bounds[s], b1 = bounds[s + 1];
-    b0 = b0 < 0 ? 0 : (b0 > n_frames ? n_frames : b0);
+    // the bounds table clamped as a table: each bound inside [0, n_frames] and not below any bound before it (a span never starts
+    // before the end of the one before it)
+    int b0 = 0;
+    for (int q = lane; q <= s; q += 64) b0 = max(b0, bounds[q]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) b0 = max(b0, __shfl_xor(b0, off));
+    b0 = b0 > n_frames ? n_frames : b0;
+    int b1 = bounds[s + 1];
     b1 = b1 < b0 ? b0 : (b1 > n_frames ? n_frames : b1);
     const int L = b1 - b0;
     const float* src = x + (int64_t)(active ? r : 0) * n_frames + b0;

@@ -51,32 +51,51 @@ def tempo(tg, sr):
 
 
 # ------------------------------------------------------------------------------------------------ 3. beats
-def localscore(env, period):
+def localscore(env, period, normalise=True):
+    """The envelope over its sample std (``normalise``; left alone when already normalised by the caller) convolved with the Gaussian
+    taps, scipy's 'same': n values for every n, also where the 2 period + 1 taps are longer than the envelope (np.convolve's "same"
+    returns max(n, taps) values there)."""
     x = np.asarray(env, dtype=np.float64)
-    sd = x.std(ddof=1)
-    if sd > 0:
-        x = x / sd
+    if normalise and x.size > 1:
+        sd = x.std(ddof=1)
+        if sd > 0:
+            x = x / sd
     taps = np.exp(-0.5 * (np.arange(-period, period + 1) * 32.0 / period) ** 2)
-    return np.convolve(x, taps, mode="same")
+    return np.convolve(x, taps, mode="full")[period: period + x.size]
 
 
-def beat_dp(ls, period):
+def beat_dp_margins(ls, period):
+    """beat_dp with two measurements of how unambiguous its decisions are: ``min_gap``, the smallest difference between the best and
+    the second-best candidate over all frames, and ``min_threshold_gap``, the smallest |ls[i] - 0.01 max ls| over the frames
+    before the first beat (those whose backlink is -1).  inf where nothing is decided."""
+    ls = np.asarray(ls, dtype=np.float64)
     n = ls.size
     offsets = np.arange(-2 * period, -int(np.round(period / 2)) + 1)
     weight = -100.0 * np.log(-offsets / period) ** 2
+    thr = 0.01 * ls.max()
     cum = np.zeros(n)
     back = np.zeros(n, dtype=np.int64)
     started = False
+    min_gap = min_thr = np.inf
     for i in range(n):
         prev = i + offsets
         score = weight + np.where(prev >= 0, cum[np.maximum(prev, 0)], 0.0)
         best = int(np.argmax(score))
+        if score.size > 1:
+            top = np.partition(score, score.size - 2)[-2:]
+            min_gap = min(min_gap, float(top[1] - top[0]))
         cum[i] = ls[i] + score[best]
-        if not started and ls[i] < 0.01 * ls.max():
+        if not started and ls[i] < thr:
             back[i] = -1
+            min_thr = min(min_thr, float(thr - ls[i]))
         else:
             back[i] = prev[best]
             started = True
+    return cum, back, min_gap, min_thr
+
+
+def beat_dp(ls, period):
+    cum, back, _, _ = beat_dp_margins(ls, period)
     return cum, back
 
 
@@ -125,6 +144,31 @@ def sync(x, spans, how):
     return np.stack([how(x[:, a:b], axis=1) for a, b in spans], axis=1)
 
 
+def clamp_bounds(bounds, n_frames):
+    """The bounds table as the header reads it: every bound inside [0, n_frames] and none below the one before it."""
+    return np.maximum.accumulate(np.clip(np.asarray(bounds, dtype=np.int64), 0, n_frames))
+
+
+def beat_sync_ref(x, bounds, median):
+    """out[r][s] over x[r][b[s] .. b[s + 1]) with b = clamp_bounds(bounds): the float32 median (the middle element of the sorted span,
+    or the float32 mean of the two middle ones), or the float64 mean rounded to float32; NaN for an empty span."""
+    x = np.asarray(x, dtype=np.float32)
+    b = clamp_bounds(bounds, x.shape[1])
+    out = np.full((x.shape[0], len(b) - 1), np.nan, dtype=np.float32)
+    for s, (lo, hi) in enumerate(zip(b[:-1], b[1:])):
+        n = int(hi - lo)
+        if n == 0:
+            continue
+        if median:
+            srt = np.sort(x[:, lo:hi], axis=1)
+            with np.errstate(invalid="ignore"):  # (inf + -inf in a span that holds both)
+                out[:, s] = srt[:, n // 2] if n & 1 else (srt[:, n // 2 - 1] + srt[:, n // 2]) * np.float32(0.5)
+        else:
+            with np.errstate(invalid="ignore"):
+                out[:, s] = x[:, lo:hi].astype(np.float64).mean(axis=1).astype(np.float32)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ 6. recurrence
 def knn_k(n, width=3):
     return int(2 * math.ceil(math.sqrt(n - 2 * width + 1))) if n > 2 * width + 1 else 2
@@ -151,6 +195,44 @@ def knn_sets(dist, k, width=3):
     return out
 
 
+def pair_distances_rows(x, rows):
+    """pair_distances for the rows ``rows`` only: [len(rows), S]."""
+    x = np.asarray(x, dtype=np.float32)
+    d = np.zeros((len(rows), x.shape[1]), dtype=np.float32)
+    for f in range(x.shape[0]):
+        diff = x[f][rows, None] - x[f][None, :]
+        d = (d + diff * diff).astype(np.float32)
+    return np.sqrt(d)
+
+
+def knn_links_exact(x, k, width, rows=None, block=512):
+    """The link matrix itself, float32 [S, S] (or [len(rows), S] for the rows asked for): the fp32 distances of pair_distances, the band
+    |i - j| < width set to +inf, a stable argsort per row (ties to the lower j), the first min(k, columns outside the band) columns
+    keep their distance, every other cell is -1.  Computed ``block`` rows at a time."""
+    x = np.asarray(x, dtype=np.float32)
+    s = x.shape[1]
+    rows = np.arange(s) if rows is None else np.asarray(rows, dtype=np.int64)
+    out = np.full((len(rows), s), -1.0, dtype=np.float32)
+    cols = np.arange(s)
+    for a in range(0, len(rows), block):
+        r = rows[a: a + block]
+        dist = pair_distances_rows(x, r)
+        band = np.abs(r[:, None] - cols[None, :]) < width
+        order = np.argsort(np.where(band, np.float32(np.inf), dist), axis=1, kind="stable")
+        n_valid = s - band.sum(axis=1)
+        keep = np.arange(s)[None, :] < np.minimum(k, n_valid)[:, None]  # by rank
+        ri = np.broadcast_to(np.arange(len(r))[:, None], order.shape)
+        out[a + ri[keep], order[keep]] = dist[ri[keep], order[keep]]
+    return out
+
+
+def affinity_from_links(links, bandwidth):
+    """rec (fp64) of a link matrix (distance on a link, negative elsewhere): exp(-d / bandwidth) where i links j AND j links i, else 0."""
+    links = np.asarray(links)
+    mutual = (links >= 0) & (links.T >= 0)
+    return np.where(mutual, np.exp(-np.where(mutual, links, 0).astype(np.float64) / float(bandwidth)), 0.0)
+
+
 def affinity(dist, sets):
     s = dist.shape[0]
     linked = np.zeros((s, s), dtype=bool)
@@ -174,7 +256,7 @@ def timelag_median_formula(rec):
                 jp = -jp - 1 if jp < 0 else (2 * s - jp - 1 if jp >= s else jp)
                 r = i - j + jp
                 vals.append(rec[r, jp] if 0 <= r < s else 0.0)
-            out[i, j] = np.median(vals)
+            out[i, j] = sorted(vals)[3]  # the median of seven
     return out
 
 
