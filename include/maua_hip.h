@@ -530,6 +530,33 @@ int maua_yin_f32(const float* y, int64_t n_samples, int frame, int hop, int tau_
                  float* lag /*[n_frames]*/, float* aperiodicity /*[n_frames]*/, int32_t* tau_int /*[n_frames]*/,
                  float* cmndf /*[n_frames, tau_max + 1] or NULL*/, int n_frames, void* stream);
 
+/* Spectrogram factorisation (audioreactive nmf / decompose / components; csrc/nmf.hip; additive: the ABI version is unchanged).
+ * Non-negative matrix factorisation V [F, T] ~ W [F, K] . H [K, T] under the generalised Kullback-Leibler divergence by multiplicative
+ * updates (Lee & Seung 2000), in place, all fp32 and contiguous: V with frames contiguous, W contiguous in k, H contiguous in t.
+ * One iteration, in this order:
+ *   H step (update_h != 0):  P = max(W.H, eps);  R = V / P;  H[k,t] <- H[k,t] * (sum_f W[f,k] R[f,t]) / max(sum_f W[f,k], eps)
+ *   W step (update_w != 0):  P = max(W.H, eps) with the new H;  R = V / P;
+ *                            W[f,k] <- W[f,k] * (sum_t R[f,t] H[k,t]) / max(sum_t H[k,t], eps)
+ * Every element of W.H is the chain p = fmaf(W[f,k], H[k,t], p) for k ascending from p = 0; the quotients are IEEE divisions; the update is
+ * (old * sum) / denominator, in that order.  W.H and R are never stored.
+ * maua_nmf_kl_f32 enqueues n_iter iterations on `stream`; it neither synchronises nor allocates (no workspace) and can be captured.
+ * update_w = 0 keeps the dictionary fixed (activations only), update_h = 0 is the mirror case.  n_iter == 0 returns 0 without a launch.
+ * No atomics and no reduction across workgroups: the results of a call are bit-identical from run to run, and n calls of one iteration
+ * equal one call of n.
+ * Zeros absorb, bit for bit (finite input): a zero H[k,t] or W[f,k] stays exactly zero; an all-zero column of V (a silent frame) gives an
+ * exactly zero column of H after one H step; an all-zero column of W gives a zero row of H.
+ * Non-finite input: with update_w = 0, a NaN or an infinity in V[f,t] changes column t of H only, every other column keeps its bits; with
+ * both updates on it spreads everywhere (the callers refuse such input).
+ * maua_nmf_kl_div_f32: d_cols[t] = sum_f (V log(V / P) - V + P) with 0 log 0 = 0, P the same fp32 max(W.H, eps) as in the update, the
+ * terms and their sum in double; the divergence is the sum of the T numbers (the host adds them).
+ * MAUA_EINVAL, without a launch: a null pointer, F, T or K < 1, K > MAUA_NMF_MAX_K, F * T >= 2^31, eps not finite or <= 0, n_iter < 0,
+ * both update flags zero. */
+#define MAUA_NMF_MAX_K 32
+int maua_nmf_kl_f32(const float* v /*[F, T]*/, float* w /*[F, K]*/, float* h /*[K, T]*/, int F, int T, int K, int n_iter, int update_w,
+                    int update_h, float eps, void* stream);
+int maua_nmf_kl_div_f32(const float* v, const float* w, const float* h, int F, int T, int K, float eps, double* d_cols /*[T]*/,
+                        void* stream);
+
 /* Structural segmentation (audioreactive laplacian_segmentation, ABI 6).  Every entry is deterministic run to run.
  * Tempogram: the onset envelope env[n_frames] padded by win/2 with a linear ramp to 0, framed with hop 1 (n_frames frames), each
  * frame times a periodic Hann window of win samples, autocorrelated over lags 0 .. win-1 (fp64), divided by its max |.| (unless

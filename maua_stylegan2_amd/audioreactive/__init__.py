@@ -2,6 +2,7 @@
 (/root/reference/audioreactive/__init__.py:1-5)."""
 from . import signal as _signal_module
 from .bend import *  # noqa: F401,F403
+from .decompose import *  # noqa: F401,F403  (nmf, decompose, components: spectrogram factorisation, no counterpart in the reference)
 from .latent import *  # noqa: F401,F403
 from .noise import *  # noqa: F401,F403  (NoiseSynth, noise_term: synthesised noise slots, no counterpart in the reference)
 from .signal import *  # noqa: F401,F403
