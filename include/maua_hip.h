@@ -557,6 +557,32 @@ int maua_nmf_kl_f32(const float* v /*[F, T]*/, float* w /*[F, K]*/, float* h /*[
 int maua_nmf_kl_div_f32(const float* v, const float* w, const float* h, int F, int T, int K, float eps, double* d_cols /*[T]*/,
                         void* stream);
 
+/* Source separation by soft masks (audioreactive separate; csrc/separate.hip; additive: the ABI version is unchanged).
+ * From a factorisation V ~ W.H of a magnitude spectrogram and the complex spectrogram re + i im it was taken from to the complex
+ * spectrogram of every source ("stem"): component k belongs to stem group[k] in [0, G); a group may be empty.  Layouts as in
+ * maua_nmf_kl_f32: re, im [F, T] with frames contiguous, W [F, K] contiguous in k, H [K, T] contiguous in t; out_re, out_im
+ * [n_out, F, T], indexed in 64 bits.  `group` is a HOST array of K entries, read before the call returns and carried in the kernel
+ * arguments: one launch on `stream`, no upload, no workspace, no allocation, no synchronisation; the call can be captured.
+ * Per element (f, t), all fp32, in this order:
+ *   P_g = 0; for k ascending with group[k] == g:  P_g = fmaf(W[f,k], H[k,t], P_g)
+ *   q_g = P_g (power == 1, the ratio mask)  or  P_g * P_g (power == 2, the Wiener mask; one rounding)
+ *   D   = 0; for g ascending from 0:  D = D + q_g            (always over all G groups, whatever the window)
+ *   m_g = q_g / D (IEEE division) when D > 0, else 1.0f / G  (the equal split keeps the masks a partition of unity on silent bins;
+ *                                                             a NaN D compares false and takes it too)
+ *   out_re[g - g0, f, t] = m_g * re[f,t],  out_im[g - g0, f, t] = m_g * im[f,t]   for g0 <= g < g0 + n_out
+ * Consequences (finite W and H):
+ *   G == 1: the output equals the input bit for bit (q / q == 1 and 1 / 1 == 1);
+ *   two calls give identical bits (no atomics, no reduction across lanes: an element depends on its own operands only);
+ *   the call for a window (g0, n_out) gives the bits of the matching slices of the full call (g0 = 0, n_out = G);
+ *   an all-zero column of H gives (1.0f / G) * re and (1.0f / G) * im in every stem, re / G exactly where G is a power of two;
+ *   a non-finite value in re / im [f,t] or in H[:,t] changes column t only, one in W[f,:] row f only.
+ * MAUA_EINVAL, without a launch: a null pointer, F, T or K < 1, K > MAUA_NMF_MAX_K, G outside 1 .. MAUA_SEPARATE_MAX_GROUPS,
+ * F * T >= 2^31, power not 1 or 2, g0 < 0, n_out < 1, g0 + n_out > G, a group[k] outside [0, G). */
+#define MAUA_SEPARATE_MAX_GROUPS 32 /* = MAUA_NMF_MAX_K */
+int maua_nmf_separate_f32(const float* re, const float* im /*[F, T]*/, const float* w /*[F, K]*/, const float* h /*[K, T]*/,
+                          const int32_t* group /*HOST array [K]*/, int F, int T, int K, int G, int power /*1 or 2*/, int g0, int n_out,
+                          float* out_re, float* out_im /*[n_out, F, T]*/, void* stream);
+
 /* Structural segmentation (audioreactive laplacian_segmentation, ABI 6).  Every entry is deterministic run to run.
  * Tempogram: the onset envelope env[n_frames] padded by win/2 with a linear ramp to 0, framed with hop 1 (n_frames frames), each
  * frame times a periodic Hann window of win samples, autocorrelated over lags 0 .. win-1 (fp64), divided by its max |.| (unless

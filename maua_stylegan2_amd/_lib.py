@@ -145,6 +145,7 @@ _SIGNATURES = {
     "maua_yin_f32": (c_int, [_P, c_int64, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, c_int, _P]),
     "maua_nmf_kl_f32": (c_int, [_P, _P, _P] + [c_int] * 6 + [c_float, _P]),
     "maua_nmf_kl_div_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
+    "maua_nmf_separate_f32": (c_int, [_P, _P, _P, _P, POINTER(ctypes.c_int32)] + [c_int] * 7 + [_P, _P, _P]),
     "maua_filterbank_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "maua_tempogram_ws_doubles": (c_int64, [c_int] * 2),
     "maua_tempogram_f32": (c_int, [_P, c_int, c_int, _P, _P, _P]),

@@ -9,7 +9,10 @@ formulation to fall back to.
   * :func:`decompose`   templates and activations of a clip's mel or STFT magnitude spectrogram
   * :func:`components`  one envelope in [0, 1] per component and video frame, post-processed like :func:`signal.onsets`; feeds
                         ``ar.chroma_weight_latents`` unchanged
+  * :func:`separate`    the SOUND of every source: soft masks from the factorisation on the complex STFT (csrc/separate.hip behind
+                        maua_nmf_separate_f32), one inverse STFT per stem; a stem goes into every ``ar.*`` feature like the clip itself
 """
+import ctypes
 import math
 import warnings
 
@@ -19,9 +22,11 @@ import torch as th
 from .. import _lib
 from . import signal as _signal
 
-__all__ = ["nmf", "decompose", "components", "nmf_divergence", "NMF_MAX_COMPONENTS"]
+__all__ = ["nmf", "decompose", "components", "separate", "nmf_divergence", "NMF_MAX_COMPONENTS", "SEPARATE_MAX_GROUPS"]
 
 NMF_MAX_COMPONENTS = 32  # MAUA_NMF_MAX_K (include/maua_hip.h)
+SEPARATE_MAX_GROUPS = 32  # MAUA_SEPARATE_MAX_GROUPS
+_SEPARATE_WINDOW_BYTES = 256 << 20  # bound on the two masked-spectrum buffers of one maua_nmf_separate_f32 call
 _CHECK_EVERY = 10        # iterations between two evaluations of the divergence when ``tol`` is given
 
 
@@ -165,3 +170,82 @@ def components(audio, sr, n_frames, n_components=8, smooth=2, clip=100, power=1,
     env = _signal.gaussian_filter(env, smooth, causal=0).reshape(int(n_frames), K)
     env = th.stack([_clip_column(env[:, k], clip) for k in range(K)], dim=1) ** power
     return env.to(out_device)
+
+
+def _resolve_groups(groups, n_components):
+    """(group int32 [K], G) of the ``groups`` argument of :func:`separate`."""
+    K = int(n_components)
+    if groups is None:
+        return np.arange(K, dtype=np.int32), K
+    if isinstance(groups, (int, np.integer)) and not isinstance(groups, (bool, np.bool_)):
+        G = int(groups)
+        if not 1 <= G <= SEPARATE_MAX_GROUPS:
+            raise ValueError(f"separate: groups ({groups}) as a count must lie in 1 .. {SEPARATE_MAX_GROUPS}")
+        group = np.empty(K, np.int32)
+        for g, run in enumerate(np.array_split(np.arange(K), G)):
+            group[run] = g
+        return group, G
+    if isinstance(groups, (str, bytes, bool, np.bool_)) or not hasattr(groups, "__len__"):
+        raise ValueError(f"separate: groups must be None, a count or a sequence of {K} group ids (got {groups!r})")
+    ids = np.asarray(groups.cpu() if isinstance(groups, th.Tensor) else groups)
+    if ids.shape != (K,) or ids.dtype.kind not in "iu":
+        raise ValueError(f"separate: groups must hold one integer id per component, {K} in all (got {groups!r})")
+    if int(ids.min()) < 0 or int(ids.max()) >= SEPARATE_MAX_GROUPS:
+        raise ValueError(f"separate: group ids must lie in 0 .. {SEPARATE_MAX_GROUPS - 1} (got {groups!r})")
+    return ids.astype(np.int32), int(ids.max()) + 1
+
+
+def _masked_spectra(re, im, W, H, group, G, power, g0, n_out, out_re, out_im):
+    F, T = re.shape
+    ids = np.ascontiguousarray(group, np.int32)
+    with th.cuda.device(re.device):
+        _lib.check(_lib.load().maua_nmf_separate_f32(re.data_ptr(), im.data_ptr(), W.data_ptr(), H.data_ptr(), ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                     F, T, W.shape[1], G, power, g0, n_out, out_re.data_ptr(), out_im.data_ptr(),
+                                                     _lib.stream_ptr(re.device)), "maua_nmf_separate_f32")
+
+
+def separate(audio, sr, n_components=8, groups=None, power=2, n_iter=200, seed=0, W=None, update_w=True, device=None, return_model=False,
+             _window_bytes=_SEPARATE_WINDOW_BYTES):
+    """Stems [G, len(audio)] float32: the clip split into G sources that add up to it.  A numpy array (what ``load_audio`` returns, so
+    that ``stems[g]`` goes into every ``ar.*`` feature unchanged) unless ``device=`` is given, then a tensor on that device.
+
+    Chain, all on the device: complex STFT (frame 2048, hop 512, periodic Hann, as :func:`signal.hpss`) -> V = sqrt(re^2 + im^2) ->
+    :func:`nmf` (``n_components``, ``n_iter``, ``seed``, ``W``, ``update_w``; components ordered by ascending spectral centroid) -> soft
+    masks (maua_nmf_separate_f32: stem g's share of the model, sum_{k in g} W H, over the whole model; ``power=2`` the Wiener mask on the
+    squares, ``power=1`` the ratio mask; they sum to 1, an equal split where the model is silent) -> one inverse STFT per stem.
+    ``groups``: None, one stem per component; an int G, the ordered components in G contiguous runs sized as
+    ``numpy.array_split(range(K), G)``, stem 0 the lowest (beyond K the last runs are empty and their stems silent); a sequence of K ints in 0 .. G - 1 (G = max + 1), used as given.
+    ``sr`` is accepted for symmetry with the other features; nothing here depends on it.
+    ``return_model=True``: (stems, W [F, K], H [K, T], group int32 [K]), W and H device tensors.
+    A silent clip gives zeros with a warning.  ValueError: ``power`` not 1 or 2, empty audio, a ``groups`` that is none of the above."""
+    if power not in (1, 2) or isinstance(power, bool):
+        raise ValueError(f"separate: power ({power!r}) must be 1 (ratio mask) or 2 (Wiener mask)")
+    group, G = _resolve_groups(groups, n_components)
+    n = int(np.prod(np.shape(audio))) if not isinstance(audio, th.Tensor) else audio.numel()
+    if n == 0:
+        raise ValueError("separate: the audio is empty")
+    y = _signal._to_dev(audio).reshape(-1)
+    dev = y.device
+    re, im = _signal.stft_complex(y)
+    V = th.sqrt(re * re + im * im)
+    Wd, Hd = nmf(V, n_components, n_iter=n_iter, seed=seed, W=W, update_w=update_w)
+    stems = th.zeros((G, n), dtype=th.float32, device=dev)
+    if not float(V.max()) > 0:
+        warnings.warn("separate: the clip is silent, every stem is silent; returning zeros", stacklevel=2)
+    else:
+        F, T = re.shape
+        per_call = max(1, min(G, int(_window_bytes) // (2 * F * T * 4)))
+        out_re = th.empty((per_call, F, T), dtype=th.float32, device=dev)
+        out_im = th.empty_like(out_re)
+        win = _signal._hann(2048, dev)
+        frames_ws = th.empty((T, 2048), dtype=th.float32, device=dev)
+        lib = _lib.load()
+        for g0 in range(0, G, per_call):
+            n_out = min(per_call, G - g0)
+            _masked_spectra(re, im, Wd, Hd, group, G, int(power), g0, n_out, out_re, out_im)
+            with th.cuda.device(dev):
+                for j in range(n_out):
+                    _lib.check(lib.maua_istft_f32(out_re[j].data_ptr(), out_im[j].data_ptr(), win.data_ptr(), 2048, 512, T, frames_ws.data_ptr(),
+                                                  stems[g0 + j].data_ptr(), n, _lib.stream_ptr(dev)), "maua_istft_f32")
+    out = stems.to(device) if device is not None else stems.cpu().numpy()
+    return (out, Wd, Hd, group) if return_model else out

@@ -700,6 +700,18 @@ def _read_audio_file(audio_file, target_sr=22050):
     return data, target_sr
 
 
+def save_audio(path, audio, sr):
+    """Write ``audio`` (a numpy array or a tensor on any device, flattened to mono) as a 16-bit PCM WAV at ``sr`` through
+    scipy.io.wavfile — for listening to a stem of ``ar.separate``.  Samples are clipped to [-1, 1] and stored as round(x * 32768)
+    limited to 32767, so that :func:`_read_audio_file` returns them to within 1 / 32768."""
+    import scipy.io.wavfile
+
+    if isinstance(audio, th.Tensor):
+        audio = audio.detach().cpu().numpy()
+    x = np.clip(np.asarray(audio, dtype=np.float64).reshape(-1), -1.0, 1.0)
+    scipy.io.wavfile.write(str(path), int(sr), np.minimum(np.rint(x * 32768.0), 32767.0).astype(np.int16))
+
+
 def load_audio(audio_file, offset=0, duration=-1, cache=True):
     """Reference :371-405: (audio float32 mono @22050 Hz, sr, duration); cached under workspace/<stem>*.npy."""
     full, sr = None, 22050
