@@ -530,6 +530,66 @@ int maua_yin_f32(const float* y, int64_t n_samples, int frame, int hop, int tau_
                  float* lag /*[n_frames]*/, float* aperiodicity /*[n_frames]*/, int32_t* tau_int /*[n_frames]*/,
                  float* cmndf /*[n_frames, tau_max + 1] or NULL*/, int n_frames, void* stream);
 
+/* Probabilistic YIN (audioreactive raw_pyin / pitch(method="pyin"); csrc/pyin.hip; additive: the ABI version is unchanged).
+ * Mauch & Dixon, "pYIN: a fundamental frequency estimator using probabilistic threshold distributions", ICASSP 2014, in two entries
+ * behind the d' rows of maua_yin_f32.  tests/pyin_ref.py restates both in numpy.
+ *
+ * maua_pyin_candidates_f32: d' rows -> per-bin voiced mass.  cmndf [n_frames, tau_max + 1] as maua_yin_f32 writes it; obs and period
+ * [n_frames, n_bins]; voiced_prob [n_frames].  Per frame, with r = cmndf[t]:
+ *   Troughs.  A lag tau in [tau_min, tau_max - 1] is a trough where r[tau] < r[tau - 1] and r[tau] <= r[tau + 1]; at tau_min the left
+ *     neighbour counts as +inf; tau_max is never a trough.  fp32 compares of the given values (a NaN compares false).  Height h = r[tau].
+ *   Threshold prior.  Thresholds k / n_thr, k = 1 .. n_thr; cum_prior[0 .. n_thr] is the running sum of their prior (cum_prior[0] = 0,
+ *     non-decreasing, summed in float64 by the host and rounded once).  idx(x) = clamp((int)floorf(x * (float)n_thr), 0, n_thr), the
+ *     number of thresholds at or below x; idx(+inf) = idx(NaN) = n_thr.  Walking the troughs in ascending lag with m = the minimum
+ *     height of the earlier ones (+inf for the first): a trough with h < m — a record — gets p = cum_prior[idx(m)] - cum_prior[idx(h)],
+ *     one fp32 subtraction (it owns every threshold for which it is the first trough below); every other trough gets 0.  The first
+ *     trough of smallest height (the last record) gets p + no_trough_prob * cum_prior[idx(h)] instead: the product rounded, then one
+ *     addition (YIN's fallback picks the global minimum, with that probability, under every threshold no trough gets under).  A frame
+ *     without troughs has no mass.
+ *   Period.  Each trough with p > 0 is refined by the parabola of maua_yin_f32: a, b, c = r[tau - 1], r[tau], r[tau + 1]; if
+ *     tau - 1 >= 1 and a - 2 b + c > 0, lag = tau + fminf(fmaxf(0.5 (a - c) / (a - 2 b + c), -0.5), 0.5), otherwise lag = tau.
+ *   Bin.  bin_edge_period[0 .. n_bins] is strictly decreasing; bin b holds the periods in (edge[b + 1], edge[b]]; a period above
+ *     edge[0] goes to bin 0, one at or below edge[n_bins] to bin n_bins - 1.  (The host builds the edges in float64 from the bins'
+ *     frequencies and rounds once: the device needs no logarithm.)
+ *   Outputs.  obs[t, b] = the sum of the p that fall into b, added in ascending lag; period[t, b] = the refined lag of the heaviest
+ *     trough in b (ties to the lower lag), 0 where there is none; voiced_prob[t] = min(1, the sum of all p in ascending lag).  Every
+ *     element of the three outputs is written.
+ * MAUA_EINVAL, without a launch: a null pointer, n_frames < 1, not 1 <= tau_min < tau_max <= MAUA_YIN_MAX_LAG, n_thr outside
+ *   1 .. MAUA_PYIN_MAX_THRESHOLDS, n_bins outside 1 .. MAUA_PYIN_MAX_BINS, no_trough_prob outside [0, 1] or not finite.
+ * No atomics, no workspace, capturable: the result is a function of the arguments alone.
+ *
+ * maua_pyin_viterbi_f64: the most probable path through 2 P states, P = n_bins: state p < P is voiced in bin p, state P + p unvoiced
+ * in bin p.  logobs_voiced [T, P] and logobs_unvoiced [T] (shared by the unvoiced states of a frame) are fp32, widened exactly.
+ * log_tri [2 W + 1] holds the logarithms of the triangular weights W + 1 - |d|, log_norm [P] the logarithm of source bin i's sum of those
+ * weights over the targets inside [0, P - 1]; both built by the host in float64.  Every operation is a double addition, subtraction
+ * or compare, in this order:
+ *   Frame 0.  delta[s] = logobs(0, s) + log_init; row 0 of backptr holds each state's own index.
+ *   Frame t >= 1.  e_v[i] = delta[i] - log_norm[i], e_u[i] = delta[P + i] - log_norm[i].  For target bin j the window is
+ *     i in [max(0, j - W), min(P - 1, j + W)]; bv = the maximum over it of e_v[i] + log_tri[j - i + W] and iv its index, scanning
+ *     ascending i from the window's first element, a later candidate replacing the best only when strictly greater (ties go to the
+ *     lowest i, a NaN never replaces); bu, iu the same from e_u.
+ *     Voiced target: a = bv + log_stay, b = bu + log_switch; it takes a with backptr iv unless b > a, then b with backptr P + iu;
+ *       delta'[j] = logobs_voiced[t, j] + that.
+ *     Unvoiced target: a = bv + log_switch, b = bu + log_stay, the same rule; delta'[P + j] = logobs_unvoiced[t] + that.
+ *   End.  states[T - 1] = the first maximum of the final delta (scanning ascending from state 0, replaced only by a strictly greater
+ *     one); states[t - 1] = backptr[t][states[t]].
+ * delta_last [2 P], every element of backptr [T, 2 P] and of states [T] are written.  -inf in the inputs is legal (a frame of nothing
+ * but -inf decodes to the lowest index); a NaN does not fault, the rules above define what it does.
+ * MAUA_EINVAL, without a launch: a null pointer, n_frames < 1, n_bins outside 1 .. MAUA_PYIN_MAX_BINS, width outside
+ *   0 .. MAUA_PYIN_MAX_WIDTH (width >= n_bins is fine: the window is clipped).
+ * One workgroup, latency-bound by construction (one barrier per frame); capturable, no workspace. */
+#define MAUA_PYIN_MAX_BINS 1024
+#define MAUA_PYIN_MAX_THRESHOLDS 256
+#define MAUA_PYIN_MAX_WIDTH 128
+int maua_pyin_candidates_f32(const float* cmndf, int n_frames, int tau_min, int tau_max, const float* cum_prior /*[n_thr + 1]*/,
+                             int n_thr, float no_trough_prob, const float* bin_edge_period /*[n_bins + 1]*/, int n_bins,
+                             float* obs /*[n_frames, n_bins]*/, float* period /*[n_frames, n_bins]*/, float* voiced_prob /*[n_frames]*/,
+                             void* stream);
+int maua_pyin_viterbi_f64(const float* logobs_voiced, const float* logobs_unvoiced, int n_frames, int n_bins, int width,
+                          const double* log_tri, const double* log_norm, double log_init, double log_stay, double log_switch,
+                          double* delta_last /*[2 n_bins]*/, uint16_t* backptr /*[n_frames, 2 n_bins]*/, int32_t* states /*[n_frames]*/,
+                          void* stream);
+
 /* Spectrogram factorisation (audioreactive nmf / decompose / components; csrc/nmf.hip; additive: the ABI version is unchanged).
  * Non-negative matrix factorisation V [F, T] ~ W [F, K] . H [K, T] under the generalised Kullback-Leibler divergence by multiplicative
  * updates (Lee & Seung 2000), in place, all fp32 and contiguous: V with frames contiguous, W contiguous in k, H contiguous in t.

@@ -603,6 +603,107 @@ def raw_pitch(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, thr
     return float(sr) / lag, 1.0 - aperiodicity.clamp(max=1.0)
 
 
+PYIN_MAX_BINS, PYIN_MAX_THRESHOLDS, PYIN_MAX_WIDTH = 1024, 256, 128  # MAUA_PYIN_MAX_* (include/maua_hip.h)
+
+
+def _pyin_stages(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, bins_per_semitone=10, max_transition_rate=35.92,
+                 switch_prob=0.01, no_trough_prob=0.01, beta=(2, 18), n_thresholds=100):
+    """:func:`raw_pyin` with every intermediate kept: a dict of device tensors (cmndf, obs, period, voiced_prob, logobs_voiced,
+    logobs_unvoiced, delta_last, backptr, states) next to f0 and voiced_flag, and the host constants (n_bins, width, tau_min, tau_max)."""
+    import scipy.stats
+
+    if not fmin < fmax:
+        raise ValueError(f"raw_pyin: fmin ({fmin} Hz) must be below fmax ({fmax} Hz): lower fmin or raise fmax")
+    if not fmin > 0:
+        raise ValueError(f"raw_pyin: fmin ({fmin} Hz) must be positive: raise fmin")
+    tau_min, tau_max = int(math.floor(sr / fmax)), int(math.ceil(sr / fmin))
+    if tau_min < 1:
+        raise ValueError(f"raw_pyin: fmax ({fmax} Hz) is above the sample rate ({sr} Hz), the shortest lag is one sample: lower fmax to at most {sr} Hz")
+    if tau_max > YIN_MAX_LAG:
+        raise ValueError(f"raw_pyin: fmin ({fmin} Hz) at {sr} Hz needs lags up to {tau_max} samples, the device searches at most {YIN_MAX_LAG}: "
+                         f"raise fmin to at least {sr / YIN_MAX_LAG:.2f} Hz")
+    if not 16 <= frame_length <= YIN_MAX_FRAME:
+        raise ValueError(f"raw_pyin: frame_length ({frame_length}) must lie in 16 .. {YIN_MAX_FRAME} samples")
+    if hop < 1:
+        raise ValueError(f"raw_pyin: hop ({hop}) must be at least one sample")
+    bps = int(bins_per_semitone)
+    if bps < 1:
+        raise ValueError(f"raw_pyin: bins_per_semitone ({bins_per_semitone}) must be at least 1")
+    n_bins = int(math.floor(12 * bps * math.log2(fmax / fmin))) + 1
+    if n_bins > PYIN_MAX_BINS:
+        raise ValueError(f"raw_pyin: {bps} bins per semitone between {fmin} and {fmax} Hz are {n_bins} pitch bins, the device decodes at most "
+                         f"{PYIN_MAX_BINS}: lower bins_per_semitone to at most {int((PYIN_MAX_BINS - 1) / (12 * math.log2(fmax / fmin)))} or narrow the band")
+    width = int(round(max_transition_rate * 12 * hop / sr)) * bps // 2
+    if not 0 <= width <= PYIN_MAX_WIDTH:
+        raise ValueError(f"raw_pyin: max_transition_rate ({max_transition_rate} octaves / s) at hop {hop} lets the pitch move {width} bins a frame, the "
+                         f"device decodes at most {PYIN_MAX_WIDTH}: lower max_transition_rate, bins_per_semitone or hop")
+    n_thr = int(n_thresholds)
+    if not 1 <= n_thr <= PYIN_MAX_THRESHOLDS:
+        raise ValueError(f"raw_pyin: n_thresholds ({n_thresholds}) must lie in 1 .. {PYIN_MAX_THRESHOLDS}")
+    if not 0 < switch_prob < 1:
+        raise ValueError(f"raw_pyin: switch_prob ({switch_prob}) must lie strictly between 0 and 1")
+    if not 0 <= no_trough_prob <= 1:
+        raise ValueError(f"raw_pyin: no_trough_prob ({no_trough_prob}) must lie in 0 .. 1")
+    # host tables, float64 rounded once (the definitions are the entries' comments in include/maua_hip.h)
+    prior = np.diff(scipy.stats.beta.cdf(np.arange(n_thr + 1, dtype=np.float64) / n_thr, *beta))
+    cum_prior = _const_dev(np.concatenate([[0.0], np.cumsum(prior)]), np.float32)
+    edge = _const_dev(sr / (fmin * 2.0 ** ((np.arange(n_bins + 1, dtype=np.float64) - 0.5) / (12 * bps))), np.float32)
+    centre = _const_dev(fmin * 2.0 ** (np.arange(n_bins, dtype=np.float64) / (12 * bps)), np.float32)
+    d = np.arange(-width, width + 1)
+    tri = (width + 1 - np.abs(d)).astype(np.float64)
+    norm = np.array([tri[(d + i >= 0) & (d + i <= n_bins - 1)].sum() for i in range(n_bins)], np.float64)
+    log_tri, log_norm = _const_dev(np.log(tri), np.float64), _const_dev(np.log(norm), np.float64)
+
+    y = _to_dev(audio).reshape(-1)
+    n = y.numel()
+    dev = y.device
+    n_frames = 1 + n // hop
+    f32 = dict(dtype=th.float32, device=dev)
+    lag, aperiodicity, tau_int = th.empty(n_frames, **f32), th.empty(n_frames, **f32), th.empty(n_frames, dtype=th.int32, device=dev)
+    cmndf = th.empty(n_frames, tau_max + 1, **f32)
+    obs, period, voiced_prob = th.empty(n_frames, n_bins, **f32), th.empty(n_frames, n_bins, **f32), th.empty(n_frames, **f32)
+    delta_last = th.empty(2 * n_bins, dtype=th.float64, device=dev)
+    backptr = th.empty(n_frames, 2 * n_bins, dtype=th.int16, device=dev)  # (the bits of uint16: values stay below 2048)
+    states = th.empty(n_frames, dtype=th.int32, device=dev)
+    lib = _lib.load()
+    with th.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        _lib.check(lib.maua_yin_f32(y.data_ptr(), n, int(frame_length), int(hop), tau_min, tau_max, 0.1, lag.data_ptr(), aperiodicity.data_ptr(),
+                                    tau_int.data_ptr(), cmndf.data_ptr(), n_frames, stream), "maua_yin_f32")
+        _lib.check(lib.maua_pyin_candidates_f32(cmndf.data_ptr(), n_frames, tau_min, tau_max, cum_prior.data_ptr(), n_thr, float(no_trough_prob),
+                                                edge.data_ptr(), n_bins, obs.data_ptr(), period.data_ptr(), voiced_prob.data_ptr(), stream),
+                   "maua_pyin_candidates_f32")
+        tiny = float(np.finfo(np.float32).tiny)
+        logobs_voiced = obs.clamp(min=tiny).log().contiguous()
+        logobs_unvoiced = ((1.0 - voiced_prob) / float(n_bins)).clamp(min=tiny).log().contiguous()
+        _lib.check(lib.maua_pyin_viterbi_f64(logobs_voiced.data_ptr(), logobs_unvoiced.data_ptr(), n_frames, n_bins, width, log_tri.data_ptr(),
+                                             log_norm.data_ptr(), -math.log(2 * n_bins), math.log(1 - switch_prob), math.log(switch_prob),
+                                             delta_last.data_ptr(), backptr.data_ptr(), states.data_ptr(), stream), "maua_pyin_viterbi_f64")
+    voiced_flag = states < n_bins
+    pitch_bin = th.where(voiced_flag, states, states - n_bins).long()
+    per = period.gather(1, pitch_bin[:, None])[:, 0]
+    f0 = th.where(per > 0, float(sr) / per.clamp(min=tiny), centre[pitch_bin])
+    return {"f0": f0, "voiced_flag": voiced_flag, "voiced_prob": voiced_prob, "cmndf": cmndf, "obs": obs, "period": period,
+            "logobs_voiced": logobs_voiced, "logobs_unvoiced": logobs_unvoiced, "delta_last": delta_last, "backptr": backptr, "states": states,
+            "n_bins": n_bins, "width": width, "tau_min": tau_min, "tau_max": tau_max}
+
+
+def raw_pyin(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, bins_per_semitone=10, max_transition_rate=35.92, switch_prob=0.01,
+             no_trough_prob=0.01, beta=(2, 18), n_thresholds=100):
+    """Probabilistic YIN (Mauch & Dixon 2014): ``(f0_hz [T], voiced_flag [T] bool, voiced_prob [T])`` as device tensors, T = 1 + len / hop.
+    The d' rows of maua_yin_f32 (lags as in :func:`raw_pitch`) -> every trough's share of a Beta(``beta``) prior over ``n_thresholds``
+    YIN thresholds, collected in P = floor(12 B log2(fmax / fmin)) + 1 pitch bins of 1 / B semitone (maua_pyin_candidates_f32) -> the
+    logarithms (torch, on the device) -> the most probable path through (voiced | unvoiced) x bin, a pitch step of at most
+    W = round(max_transition_rate 12 hop / sr) B // 2 bins per frame under a triangular weight and ``switch_prob`` to change voicing
+    (maua_pyin_viterbi_f64).  f0 is the refined period of the heaviest candidate in the decoded bin, the bin's centre frequency where the
+    bin holds none (unvoiced frames); ``voiced_prob`` is the frame's total candidate mass.  The definitions are the two entries' comments
+    in include/maua_hip.h (csrc/pyin.hip).  Unlike :func:`raw_pitch` it needs no voicing gate, hold or median behind it on noisy or
+    masked tones: the decoder has the context."""
+    s = _pyin_stages(audio, sr, fmin, fmax, frame_length, hop, bins_per_semitone, max_transition_rate, switch_prob, no_trough_prob, beta,
+                     n_thresholds)
+    return s["f0"], s["voiced_flag"], s["voiced_prob"]
+
+
 def hold_fill(values, voiced):
     """``values`` [T] with every unvoiced frame replaced by the last voiced one before it, leading unvoiced frames by the first voiced
     one; None when no frame is voiced.  Plain torch, any device."""
@@ -637,25 +738,38 @@ def lerp_resize(x, num):
     return x[lo] * (1 - frac) + x[lo + 1] * frac
 
 
-def pitch(audio, sr, n_frames, fmin=65.0, fmax=2100.0, margin=8, bandpass=False, voicing=0.5, smooth=2, return_voicing=False, device=None):
+def pitch(audio, sr, n_frames, fmin=65.0, fmax=2100.0, margin=8, bandpass=False, voicing=0.5, smooth=2, return_voicing=False, device=None,
+          method="yin"):
     """Pitch height of the melody in [0, 1] per video frame (0 = ``fmin``, 1 = ``fmax``, logarithmic), a CPU tensor unless ``device=`` is
     given: harmonic separation (``margin``; None / 0 skips it) -> optionally the Butterworth band-pass of :func:`rms` over [fmin, fmax]
     (a bass line under a lead) -> :func:`raw_pitch` -> log height -> frames less confident than ``voicing`` hold the last voiced height
     (leading ones take the first) -> 5-tap median against octave blips -> linear interpolation to ``n_frames`` -> Gaussian smoothing.
     The absolute height is the point: the result is neither percentile-clipped nor normalised (``ar.normalize`` does that).
-    ``return_voicing`` adds the confidence envelope, interpolated and smoothed the same way."""
+    ``return_voicing`` adds the confidence envelope, interpolated and smoothed the same way.
+    ``method="pyin"`` tracks with :func:`raw_pyin` instead (noisy tones, stems, mixed tracks): the frames its decoder calls unvoiced hold
+    the last voiced height, there is no median (the decoder has done that work), ``voicing`` is ignored, and ``return_voicing`` returns
+    the envelope of the voiced probability."""
+    if method not in ("yin", "pyin"):
+        raise ValueError(f"pitch: unknown method {method!r}: use 'yin' or 'pyin'")
     y = harmonic(audio, margin=margin) if margin else audio
     if bandpass:
         y = y.detach().cpu().numpy() if isinstance(y, th.Tensor) else np.asarray(y)
         y = scipy.signal.sosfilt(scipy.signal.butter(12, [fmin, fmax], "bp", fs=sr, output="sos"), y).astype(np.float32)
-    f0, confidence = raw_pitch(y, sr, fmin=fmin, fmax=fmax)
+    if method == "pyin":
+        f0, voiced, confidence = raw_pyin(y, sr, fmin=fmin, fmax=fmax)
+    else:
+        f0, confidence = raw_pitch(y, sr, fmin=fmin, fmax=fmax)
+        voiced = confidence >= voicing
     height = (th.log2(f0 / float(fmin)) / math.log2(fmax / fmin)).clamp(0.0, 1.0)
-    held = hold_fill(height, confidence >= voicing)
+    held = hold_fill(height, voiced)
     if held is None:
-        warnings.warn(f"pitch: no frame reaches the voicing confidence {voicing} between {fmin} and {fmax} Hz; returning zeros", stacklevel=2)
+        if method == "pyin":
+            warnings.warn(f"pitch: the decoder finds no voiced frame between {fmin} and {fmax} Hz; returning zeros", stacklevel=2)
+        else:
+            warnings.warn(f"pitch: no frame reaches the voicing confidence {voicing} between {fmin} and {fmax} Hz; returning zeros", stacklevel=2)
         height = th.zeros_like(height)
     else:
-        height = _median5(held)
+        height = held if method == "pyin" else _median5(held)
     out_device = device if device is not None else "cpu"
     height = gaussian_filter(lerp_resize(height, n_frames), smooth).to(out_device)
     if not return_voicing:
