@@ -35,6 +35,15 @@ int maua_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
 int maua_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int in_h, int in_w, int minor,
                        int kh, int kw, int up_x, int up_y, int down_x, int down_y,
                        int pad_x0, int pad_x1, int pad_y0, int pad_y1, void* stream);
+/* The plan alone: writes which kernel instance maua_upfirdn2d_f32 would launch for these 14 geometry integers (the same host function
+ * picks it) and returns 0, or returns MAUA_EINVAL for exactly the geometries that call refuses (a negative major, a size, tap count or
+ * factor below 1, a negative span on either axis, more than 2^31 - 1 tiles) and for a null or too short buf.  The text is the instance,
+ * then for the tiled ones the workgroups per plane as columns x rows: "tile4.wx2 1x3" (fir_tile_kernel<4, 4, 2, false, 24>, taps 2 .. 4),
+ * "up2.wx4 3x2" (fir_up2_kernel<4, 16>), "down2.wx1 1x1" (fir_down2_kernel<1, 8>), each with wx 1, 2 or 4; "generic" (fir_generic_kernel);
+ * "none" for major == 0, which launches nothing.  Geometry only: no pointer of the op is looked at, no HIP call is made, nothing needs a
+ * GPU.  (Additive: the ABI version is unchanged.) */
+int maua_upfirdn2d_plan_instance(int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                                 int pad_x0, int pad_x1, int pad_y0, int pad_y1, char* buf, int buf_len);
 
 /* The same op for half / double tensors — the reference dispatches half, float and double (upfirdn2d_kernel.cu:313-359,
  * fused_bias_act_kernel.cu:79).  Generic kernels (fp32 accumulation for half); the fp32 entries above are the tuned path.

@@ -78,6 +78,7 @@ _SIGNATURES = {
     "maua_abi_version": (c_int, []),
     "maua_device_info": (c_int, [POINTER(c_int), POINTER(c_int), c_char_p, c_int]),
     "maua_upfirdn2d_f32": (c_int, [_P, _P, _P] + [c_int] * 14 + [_P]),
+    "maua_upfirdn2d_plan_instance": (c_int, [c_int] * 14 + [c_char_p, c_int]),
     "maua_fused_bias_act_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
     "maua_fused_bias_act_f16": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
     "maua_fused_bias_act_f64": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
@@ -259,6 +260,20 @@ def planned_modconv_instance(batch, cin, cout, h, w, mode):
     buf = ctypes.create_string_buffer(128)
     rc = load().maua_modconv_plan_instance(batch, cin, cout, h, w, mode, buf, 128)
     return rc, (buf.value.decode() if rc == 0 else None)
+
+
+def planned_upfirdn2d_instance(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
+    """(rc, name, tiles_x, tiles_y): the instance maua_upfirdn2d_f32 would launch for the geometry ("tile4.wx2", "up2.wx4", "down2.wx1",
+    "generic"; "none" for major == 0) and its workgroups per plane (0, 0 where there are no tiles), or its refusal (name None).
+    Geometry only, no launch: works without a GPU."""
+    buf = ctypes.create_string_buffer(64)
+    rc = load().maua_upfirdn2d_plan_instance(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1,
+                                             buf, 64)
+    if rc != 0:
+        return rc, None, 0, 0
+    name, _, tiles = buf.value.decode().partition(" ")
+    tiles_x, tiles_y = (int(v) for v in tiles.split("x")) if tiles else (0, 0)
+    return rc, name, tiles_x, tiles_y
 
 
 class HipEvent:

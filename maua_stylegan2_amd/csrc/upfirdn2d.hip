@@ -22,6 +22,7 @@
 #include "conv_device.h"
 
 #include <hip/hip_fp16.h>
+#include <string.h>
 
 namespace {
 
@@ -542,87 +543,146 @@ int launch_fir_typed(const void* x, const void* k, void* y, int major, int in_h,
     return 0;
 }
 
-template <int KH, int KW, bool TAIL>
-int launch_fir_tile(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w,
-                    int pad_x0, int pad_y0, const FirTail& tail, hipStream_t st) {
-    auto go = [&](auto wx_tag, auto th_tag) -> int {
-        constexpr int WX = decltype(wx_tag)::value, TH = decltype(th_tag)::value;
+// ---------------------------------------------------------------------------------------------------------------- host plan
+// Which kernel a call runs is decided HERE and nowhere else: fir_tiling() picks the strip layout (WX) and the tile counts of a tiled launch
+// from the output shape, plan_upfirdn2d_f32() the kernel family of maua_upfirdn2d_f32 from its 14 geometry integers.  The launchers below
+// take the decision as an argument; maua_upfirdn2d_plan_instance answers from the same plan without a device call.
+struct FirTiling {
+    int wx;                // wave strips side by side in a workgroup (4 / wx on top of each other)
+    int tiles_x, tiles_y;  // workgroups per plane
+};
+
+// wave_cols: output columns of one wave strip (64; 128 for fir_up2_kernel's column pairs); th: output rows of one wave strip
+inline FirTiling fir_tiling(int out_h, int out_w, int wave_cols, int th) {
+    const int wx = out_w <= wave_cols ? 1 : out_w <= 2 * wave_cols ? 2 : 4;
+    return FirTiling{wx, ceil_div(out_w, wave_cols * wx), ceil_div(out_h, (4 / wx) * th)};
+}
+
+// (the tiled kernels address a plane through 32-bit buffer offsets)
+inline bool fir_planes_fit(int in_h, int in_w, int out_h, int out_w) {
+    return (int64_t)in_h * in_w * 4 < 0x7fffffffLL && (int64_t)out_h * out_w * 4 < 0x7fffffffLL;
+}
+
+enum FirFamily { FIR_NONE, FIR_TILE, FIR_UP2, FIR_DOWN2, FIR_GENERIC };
+
+struct FirPlan {
+    int rc;         // 0, or the code the call returns without launching
+    int family;     // FIR_NONE: major == 0, nothing to launch
+    int taps;       // FIR_TILE: KH == KW
+    int out_h, out_w;
+    FirTiling tl;   // the tiled families
+};
+
+inline FirPlan plan_upfirdn2d_f32(int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x, int down_y,
+                                  int pad_x0, int pad_x1, int pad_y0, int pad_y1) {
+    FirPlan pl{};
+    pl.rc = MAUA_EINVAL;
+    if (major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
+        return pl;
+    const int span_h = in_h * up_y + pad_y0 + pad_y1 - kh, span_w = in_w * up_x + pad_x0 + pad_x1 - kw;
+    if (span_h < 0 || span_w < 0) return pl;  // (C division would round a negative span toward one output row)
+    const int out_h = pl.out_h = span_h / down_y + 1, out_w = pl.out_w = span_w / down_x + 1;
+    pl.rc = 0;
+    pl.family = FIR_NONE;
+    if (major == 0) return pl;
+    // (planes of 2 GiB and more take the generic gather)
+    const bool tiled = minor == 1 && fir_planes_fit(in_h, in_w, out_h, out_w);
+    if (tiled && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh == kw && kh >= 2 && kh <= 4) {
+        pl.family = FIR_TILE, pl.taps = kh, pl.tl = fir_tiling(out_h, out_w, 64, FIR_ROWS_PLAIN);
+    } else if (tiled && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2 && kh <= 4 && kw <= 4) {
+        pl.family = FIR_DOWN2, pl.tl = fir_tiling(out_h, out_w, 64, FIR_DOWN2_ROWS);
+    } else if (tiled && up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4) {
+        pl.family = FIR_UP2, pl.tl = fir_tiling(out_h, out_w, 128, FIR_UP2_ROWS);
+    } else {
+        pl.family = FIR_GENERIC;
+        return pl;
+    }
+    if ((int64_t)major * pl.tl.tiles_x * pl.tl.tiles_y > 0x7fffffff) pl.rc = MAUA_EINVAL;  // (one workgroup per tile: the grid's x limit)
+    return pl;
+}
+
+template <int KH, int KW, bool TAIL, int TH>
+int launch_fir_tile(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w, int pad_x0,
+                    int pad_y0, const FirTail& tail, const FirTiling& tl, hipStream_t st) {
+    auto go = [&](auto wx_tag) -> int {
+        constexpr int WX = decltype(wx_tag)::value;
         constexpr int WY = 4 / WX;
         constexpr int RH = WY * TH + KH - 1, RW = 64 * WX + KW - 1;
-        const int tiles_x = ceil_div(out_w, 64 * WX), tiles_y = ceil_div(out_h, WY * TH);
-        const int64_t nblocks = (int64_t)planes * tiles_x * tiles_y;
+        const int64_t nblocks = (int64_t)planes * tl.tiles_x * tl.tiles_y;
         if (nblocks <= 0) return 0;
         if (nblocks > 0x7fffffff) return MAUA_EINVAL;
         const size_t lds_bytes = (size_t)RH * RW * sizeof(float);
         hipLaunchKernelGGL((fir_tile_kernel<KH, KW, WX, TAIL, TH>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, x, k, y, planes,
-                           in_h, in_w, out_h, out_w, pad_x0, pad_y0, tiles_x, tiles_y, tail);
+                           in_h, in_w, out_h, out_w, pad_x0, pad_y0, tl.tiles_x, tl.tiles_y, tail);
         MAUA_LAUNCH_CHECK();
         return 0;
     };
-    auto go_wx = [&](auto wx_tag) -> int {
-        if constexpr (!TAIL) {  // (constexpr: the strip heights of the other form are never instantiated)
-            return go(wx_tag, std::integral_constant<int, FIR_ROWS_PLAIN>{});
-        } else {
-            if (out_h <= FIR_TAIL_SMALL_MAX_H) return go(wx_tag, std::integral_constant<int, FIR_ROWS_TAIL_SMALL>{});
-            return go(wx_tag, std::integral_constant<int, FIR_ROWS_TAIL>{});
-        }
-    };
-    // (the kernel addresses a plane through 32-bit buffer offsets)
-    if ((int64_t)in_h * in_w * 4 >= 0x7fffffffLL || (int64_t)out_h * out_w * 4 >= 0x7fffffffLL) return MAUA_ENOSYS;
-    if (out_w <= 64) return go_wx(std::integral_constant<int, 1>{});
-    if (out_w <= 128) return go_wx(std::integral_constant<int, 2>{});
-    return go_wx(std::integral_constant<int, 4>{});
+    if (tl.wx == 1) return go(std::integral_constant<int, 1>{});
+    if (tl.wx == 2) return go(std::integral_constant<int, 2>{});
+    return go(std::integral_constant<int, 4>{});
 }
 
-template <bool TAIL>
-int dispatch_fir_tile(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w,
-                      int kh, int kw, int pad_x0, int pad_y0, const FirTail& tail, hipStream_t st) {
-    if (kh == 4 && kw == 4) return launch_fir_tile<4, 4, TAIL>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
-    if (kh == 3 && kw == 3) return launch_fir_tile<3, 3, TAIL>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
-    if (kh == 2 && kw == 2) return launch_fir_tile<2, 2, TAIL>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
+// the plain op: the plan has chosen taps and tiling
+int launch_fir_tile_plain(const float* x, const float* k, float* y, int planes, int in_h, int in_w, const FirPlan& pl, int pad_x0,
+                          int pad_y0, hipStream_t st) {
+    const FirTail none{};
+    if (pl.taps == 4) return launch_fir_tile<4, 4, false, FIR_ROWS_PLAIN>(x, k, y, planes, in_h, in_w, pl.out_h, pl.out_w, pad_x0, pad_y0, none, pl.tl, st);
+    if (pl.taps == 3) return launch_fir_tile<3, 3, false, FIR_ROWS_PLAIN>(x, k, y, planes, in_h, in_w, pl.out_h, pl.out_w, pad_x0, pad_y0, none, pl.tl, st);
+    return launch_fir_tile<2, 2, false, FIR_ROWS_PLAIN>(x, k, y, planes, in_h, in_w, pl.out_h, pl.out_w, pad_x0, pad_y0, none, pl.tl, st);
+}
+
+// the fused tail (maua_blur_noise_act_f32): no generic form behind it, strip height by map size
+template <int KH, int KW>
+int launch_fir_tile_tail(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w, int pad_x0,
+                         int pad_y0, const FirTail& tail, hipStream_t st) {
+    if (!fir_planes_fit(in_h, in_w, out_h, out_w)) return MAUA_ENOSYS;
+    if (out_h <= FIR_TAIL_SMALL_MAX_H)
+        return launch_fir_tile<KH, KW, true, FIR_ROWS_TAIL_SMALL>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail,
+                                                                  fir_tiling(out_h, out_w, 64, FIR_ROWS_TAIL_SMALL), st);
+    return launch_fir_tile<KH, KW, true, FIR_ROWS_TAIL>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail,
+                                                        fir_tiling(out_h, out_w, 64, FIR_ROWS_TAIL), st);
+}
+
+int dispatch_fir_tile_tail(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w, int kh, int kw,
+                           int pad_x0, int pad_y0, const FirTail& tail, hipStream_t st) {
+    if (kh == 4 && kw == 4) return launch_fir_tile_tail<4, 4>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
+    if (kh == 3 && kw == 3) return launch_fir_tile_tail<3, 3>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
+    if (kh == 2 && kw == 2) return launch_fir_tile_tail<2, 2>(x, k, y, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, tail, st);
     return MAUA_ENOSYS;
 }
 
 // (up, down) = (2, 1), taps up to 4 x 4: the tiled polyphase kernel
-int launch_fir_up2(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w, int kh, int kw,
+int launch_fir_up2(const float* x, const float* k, float* y, int planes, int in_h, int in_w, const FirPlan& pl, int kh, int kw,
                    int pad_x0, int pad_y0, hipStream_t st) {
-    if ((int64_t)in_h * in_w * 4 >= 0x7fffffffLL || (int64_t)out_h * out_w * 4 >= 0x7fffffffLL) return MAUA_ENOSYS;
     auto go = [&](auto wx_tag) -> int {
         constexpr int WX = decltype(wx_tag)::value, TH = FIR_UP2_ROWS, WY = 4 / WX;
-        const int tiles_x = ceil_div(out_w, 128 * WX), tiles_y = ceil_div(out_h, WY * TH);
-        const int64_t nblocks = (int64_t)planes * tiles_x * tiles_y;
-        if (nblocks <= 0) return 0;
-        if (nblocks > 0x7fffffff) return MAUA_EINVAL;
+        const int64_t nblocks = (int64_t)planes * pl.tl.tiles_x * pl.tl.tiles_y;
         const size_t lds_bytes = sizeof(float) * (size_t)(WY * (TH / 2) + 2) * (64 * WX + 2);
-        hipLaunchKernelGGL((fir_up2_kernel<WX, TH>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, x, k, y, in_h, in_w, out_h, out_w,
-                           kh, kw, pad_x0, pad_y0, tiles_x, tiles_y);
+        hipLaunchKernelGGL((fir_up2_kernel<WX, TH>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, x, k, y, in_h, in_w, pl.out_h,
+                           pl.out_w, kh, kw, pad_x0, pad_y0, pl.tl.tiles_x, pl.tl.tiles_y);
         MAUA_LAUNCH_CHECK();
         return 0;
     };
-    if (out_w <= 128) return go(std::integral_constant<int, 1>{});
-    if (out_w <= 256) return go(std::integral_constant<int, 2>{});
+    if (pl.tl.wx == 1) return go(std::integral_constant<int, 1>{});
+    if (pl.tl.wx == 2) return go(std::integral_constant<int, 2>{});
     return go(std::integral_constant<int, 4>{});
 }
 
 // (up, down) = (1, 2), taps up to 4 x 4
-int launch_fir_down2(const float* x, const float* k, float* y, int planes, int in_h, int in_w, int out_h, int out_w, int kh, int kw,
+int launch_fir_down2(const float* x, const float* k, float* y, int planes, int in_h, int in_w, const FirPlan& pl, int kh, int kw,
                      int pad_x0, int pad_y0, hipStream_t st) {
-    if ((int64_t)in_h * in_w * 4 >= 0x7fffffffLL || (int64_t)out_h * out_w * 4 >= 0x7fffffffLL) return MAUA_ENOSYS;
     auto go = [&](auto wx_tag) -> int {
         constexpr int WX = decltype(wx_tag)::value, TH = FIR_DOWN2_ROWS, WY = 4 / WX;
-        const int tiles_x = ceil_div(out_w, 64 * WX), tiles_y = ceil_div(out_h, WY * TH);
-        const int64_t nblocks = (int64_t)planes * tiles_x * tiles_y;
-        if (nblocks <= 0) return 0;
-        if (nblocks > 0x7fffffff) return MAUA_EINVAL;
+        const int64_t nblocks = (int64_t)planes * pl.tl.tiles_x * pl.tl.tiles_y;
         const size_t lds_bytes = sizeof(float) * (size_t)(2 * WY * TH + 2) * (128 * WX + 2);
         static_assert(sizeof(float) * (2 * WY * TH + 2) * (128 * WX + 2) <= 64 * 1024, "dynamic LDS beyond 64 KB needs the launch attribute");
-        hipLaunchKernelGGL((fir_down2_kernel<WX, TH>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, x, k, y, in_h, in_w, out_h, out_w,
-                           kh, kw, pad_x0, pad_y0, tiles_x, tiles_y);
+        hipLaunchKernelGGL((fir_down2_kernel<WX, TH>), dim3((unsigned)nblocks), dim3(256), lds_bytes, st, x, k, y, in_h, in_w, pl.out_h,
+                           pl.out_w, kh, kw, pad_x0, pad_y0, pl.tl.tiles_x, pl.tl.tiles_y);
         MAUA_LAUNCH_CHECK();
         return 0;
     };
-    if (out_w <= 64) return go(std::integral_constant<int, 1>{});
-    if (out_w <= 128) return go(std::integral_constant<int, 2>{});
+    if (pl.tl.wx == 1) return go(std::integral_constant<int, 1>{});
+    if (pl.tl.wx == 2) return go(std::integral_constant<int, 2>{});
     return go(std::integral_constant<int, 4>{});
 }
 
@@ -631,33 +691,43 @@ int launch_fir_down2(const float* x, const float* k, float* y, int planes, int i
 extern "C" int maua_upfirdn2d_f32(const float* x, const float* k, float* y, int major, int in_h, int in_w, int minor,
                                   int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1,
                                   int pad_y0, int pad_y1, void* stream) {
-    if (!x || !k || !y || major < 0 || in_h <= 0 || in_w <= 0 || minor <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 ||
-        up_y <= 0 || down_x <= 0 || down_y <= 0)
-        return MAUA_EINVAL;
-    const int span_h = in_h * up_y + pad_y0 + pad_y1 - kh, span_w = in_w * up_x + pad_x0 + pad_x1 - kw;
-    if (span_h < 0 || span_w < 0) return MAUA_EINVAL;  // (C division would round a negative span toward one output row)
-    const int out_h = span_h / down_y + 1, out_w = span_w / down_x + 1;
-    if (major == 0) return 0;
+    if (!x || !k || !y) return MAUA_EINVAL;
+    const FirPlan pl = plan_upfirdn2d_f32(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (pl.rc) return pl.rc;
     hipStream_t st = (hipStream_t)stream;
-    if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh == kw && kh >= 2 && kh <= 4) {
-        FirTail none{};
-        const int rc = dispatch_fir_tile<false>(x, k, y, major, in_h, in_w, out_h, out_w, kh, kw, pad_x0, pad_y0, none, st);
-        if (rc != MAUA_ENOSYS) return rc;  // (planes of 2 GiB and more take the generic gather below)
+    switch (pl.family) {
+        case FIR_NONE: return 0;
+        case FIR_TILE: return launch_fir_tile_plain(x, k, y, major, in_h, in_w, pl, pad_x0, pad_y0, st);
+        case FIR_DOWN2: return launch_fir_down2(x, k, y, major, in_h, in_w, pl, kh, kw, pad_x0, pad_y0, st);
+        case FIR_UP2: return launch_fir_up2(x, k, y, major, in_h, in_w, pl, kh, kw, pad_x0, pad_y0, st);
+        default: break;
     }
-    if (minor == 1 && up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2 && kh <= 4 && kw <= 4) {
-        const int rc = launch_fir_down2(x, k, y, major, in_h, in_w, out_h, out_w, kh, kw, pad_x0, pad_y0, st);
-        if (rc != MAUA_ENOSYS) return rc;
-    }
-    if (minor == 1 && up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && kh <= 4 && kw <= 4) {
-        const int rc = launch_fir_up2(x, k, y, major, in_h, in_w, out_h, out_w, kh, kw, pad_x0, pad_y0, st);
-        if (rc != MAUA_ENOSYS) return rc;
-    }
-    const int64_t total = (int64_t)major * out_h * out_w * minor;
+    const int64_t total = (int64_t)major * pl.out_h * pl.out_w * minor;
     const int64_t blocks = ceil_div64(total, 256);
     const unsigned grid = (unsigned)(blocks < 256 * 32 ? blocks : 256 * 32);
     hipLaunchKernelGGL(fir_generic_kernel, dim3(grid), dim3(256), 0, st, x, k, y, major, in_h, in_w, minor, kh, kw,
-                       up_x, up_y, down_x, down_y, pad_x0, pad_y0, out_h, out_w, total);
+                       up_x, up_y, down_x, down_y, pad_x0, pad_y0, pl.out_h, pl.out_w, total);
     MAUA_LAUNCH_CHECK();
+    return 0;
+}
+
+// The plan of maua_upfirdn2d_f32 without the launch: the instance that call would run for this geometry, or its refusal.  No HIP call.
+extern "C" int maua_upfirdn2d_plan_instance(int major, int in_h, int in_w, int minor, int kh, int kw, int up_x, int up_y, int down_x,
+                                            int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, char* buf, int buf_len) {
+    if (!buf || buf_len <= 0) return MAUA_EINVAL;
+    const FirPlan pl = plan_upfirdn2d_f32(major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1);
+    if (pl.rc) return pl.rc;
+    char name[64];
+    int n;
+    switch (pl.family) {
+        case FIR_NONE: n = snprintf(name, sizeof name, "none"); break;
+        case FIR_TILE: n = snprintf(name, sizeof name, "tile%d.wx%d %dx%d", pl.taps, pl.tl.wx, pl.tl.tiles_x, pl.tl.tiles_y); break;
+        case FIR_UP2: n = snprintf(name, sizeof name, "up2.wx%d %dx%d", pl.tl.wx, pl.tl.tiles_x, pl.tl.tiles_y); break;
+        case FIR_DOWN2: n = snprintf(name, sizeof name, "down2.wx%d %dx%d", pl.tl.wx, pl.tl.tiles_x, pl.tl.tiles_y); break;
+        default: n = snprintf(name, sizeof name, "generic"); break;
+    }
+    if (n + 1 > buf_len) return MAUA_EINVAL;  // (a truncated name would name another instance)
+    memcpy(buf, name, (size_t)n + 1);
     return 0;
 }
 
@@ -679,8 +749,7 @@ extern "C" int maua_blur_noise_act_f32(const float* x, const float* k, float* y,
 #endif
     FirTail tail{gain, noise, noise_w, bias, noise_batch_stride, channels, src, noise_slot, out_h <= MAUA_FIR_PLANE_MAJOR_MAX_H ? 1 : 0,
                  post_s, post_stride};
-    return dispatch_fir_tile<true>(x, k, y, batch * channels, in_h, in_w, out_h, out_w, kh, kw, pad0, pad0, tail,
-                                   (hipStream_t)stream);
+    return dispatch_fir_tile_tail(x, k, y, batch * channels, in_h, in_w, out_h, out_w, kh, kw, pad0, pad0, tail, (hipStream_t)stream);
 }
 
 extern "C" int maua_upfirdn2d_f16(const void* x, const void* k, void* y, int major, int in_h, int in_w, int minor, int kh, int kw,

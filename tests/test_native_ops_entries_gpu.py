@@ -21,6 +21,7 @@ import torch
 
 from maua_stylegan2_amd import _lib
 from redzone import CANARY_BITS, Guard
+from upfirdn_ref import pad_crop, upfirdn_out_shape, upfirdn_ref  # noqa: F401  (the float64 reference, shared with test_upfirdn2d_entries_*)
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -181,33 +182,6 @@ UPFIRDN_CASES = {
 UPFIRDN_GRID_ELEMENTS = 8192 * 256
 
 
-def pad_crop(a, p0, p1, axis):
-    """Zero padding of ``a`` along ``axis`` by p0 in front and p1 behind; a negative pad crops."""
-    a = np.moveaxis(a, axis, 0)
-    if p0 < 0:
-        a, p0 = a[-p0:], 0
-    if p1 < 0:
-        a, p1 = a[:max(a.shape[0] + p1, 0)], 0
-    z = lambda n: np.zeros((n,) + a.shape[1:], a.dtype)  # noqa: E731
-    return np.moveaxis(np.concatenate([z(p0), a, z(p1)]), 0, axis)
-
-
-def upfirdn_ref(x, k, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
-    """x [major, in_h, in_w, minor], k [kh, kw], float64."""
-    major, in_h, in_w, minor = x.shape
-    kh, kw = k.shape
-    canvas = np.zeros((major, in_h * up_y, in_w * up_x, minor))
-    canvas[:, ::up_y, ::up_x] = x
-    canvas = pad_crop(pad_crop(canvas, pad_y0, pad_y1, 1), pad_x0, pad_x1, 2)
-    oh, ow = canvas.shape[1] - kh + 1, canvas.shape[2] - kw + 1
-    kf = k[::-1, ::-1]
-    out = np.zeros((major, oh, ow, minor))
-    for i in range(kh):
-        for j in range(kw):
-            out += kf[i, j] * canvas[:, i:i + oh, j:j + ow]
-    return out[:, ::down_y, ::down_x]
-
-
 def upfirdn_ref_and_bound(x, k, params, suffix):
     """(want, bound) for operands already rounded to the tensor type."""
     x8, k8 = x.astype(np.float64), k.astype(np.float64)
@@ -223,11 +197,6 @@ def upfirdn_operands(case, out_type):
     major, in_h, in_w, minor, kh, kw = case[:6]
     r = np.random.default_rng(in_h * 131 + in_w * 7 + kh + minor)
     return r.standard_normal((major, in_h, in_w, minor)).astype(out_type), (0.5 * r.standard_normal((kh, kw))).astype(out_type)
-
-
-def upfirdn_out_shape(case):
-    major, in_h, in_w, minor, kh, kw, up_x, up_y, down_x, down_y, px0, px1, py0, py1 = case
-    return (major, (in_h * up_y + py0 + py1 - kh) // down_y + 1, (in_w * up_x + px0 + px1 - kw) // down_x + 1, minor)
 
 
 @pytest.mark.parametrize("name", list(UPFIRDN_CASES))
