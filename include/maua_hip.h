@@ -599,6 +599,42 @@ int maua_pyin_viterbi_f64(const float* logobs_voiced, const float* logobs_unvoic
                           double* delta_last /*[2 n_bins]*/, uint16_t* backptr /*[n_frames, 2 n_bins]*/, int32_t* states /*[n_frames]*/,
                           void* stream);
 
+/* Predominant local pulse (audioreactive raw_plp / tempogram / pulse / tempo / beats / beat_phase; csrc/pulse.hip; additive: the ABI
+ * version is unchanged).  Grosche & Mueller, "Extracting predominant local pulse information from music recordings", IEEE TASLP 2011,
+ * in two entries behind an onset envelope.  tests/pulse_ref.py restates both in numpy.
+ *
+ * maua_tempogram_peak_f32: the strongest tempo of every frame of a Fourier tempogram on an arbitrary tempo grid.  env [n] is the
+ * envelope; table [n_tempi][win][2] (8-byte aligned) holds tab[b][k] = w[k] (cos(omega_b k), -sin(omega_b k)), built by the host in
+ * float64 and rounded once, w >= 0 the window and omega_b the grid in radians per frame; prior [n_tempi] >= 0, NULL for all ones.
+ *   Frame t reads x[k] = env[t - win / 2 + k] (integer division), k = 0 .. win - 1, 0 outside [0, n).
+ *   F[t, b] = sum_k x[k] tab[b][k]: per component one fp32 chain acc = fmaf(x[k], tab, acc) from 0 in ascending k, clipped taps added
+ *     as zeros, so a frame's result does not depend on where it lies in the envelope or in the launch.
+ *   S[t, b] = (Re Re + Im Im) prior[b], every operation rounded on its own (without a prior the last product is left out).
+ *   Peak.  best = 0, bin = -1; walking b upwards, b is taken when S > best (an fp32 compare): the lowest b wins ties, a frame without
+ *     energy and a frame whose scores are all NaN keep bin = -1.
+ *   Outputs.  bin [n]; phase [n] = atan2f(Im, Re) of the winner, 0 for bin = -1; power [n] = best; tgram [n][n_tempi] = S when the
+ *     pointer is not NULL.  Every element is written.  A NaN in env reaches exactly the frames whose window covers it.
+ *
+ * maua_pulse_synth_f32: the overlap-add of every frame's windowed sinusoid, in gather form.  bin, phase [n] as above, window [win] =
+ * w, omega [n_tempi].  A bin outside [0, n_tempi) counts as -1 and indexes nothing.  For output sample m, walking k = 0 .. win - 1 and
+ * t = m + win / 2 - k, frames outside [0, n) skipped:
+ *     den = den + w[k];   for bin[t] >= 0:  num = num + w[k] cosf(omega[bin[t]] (float)k + phase[t])
+ *   every operation an fp32 operation rounded on its own, cosf accurate to a few ulp at every argument (they reach win omega + pi).
+ *   pulse[m] = num / den where den > 0 and the quotient is > 0, else 0: a steady pulse reaches about 1, and there is no normalisation
+ *   over the clip.  Every element of pulse [n] is written.
+ *
+ * Both: MAUA_EINVAL, without a launch, on a NULL pointer (other than prior and tgram), n outside 1 .. MAUA_PULSE_MAX_FRAMES, win outside
+ * 2 .. MAUA_PULSE_MAX_WIN, n_tempi outside 1 .. MAUA_PULSE_MAX_TEMPI.  No atomics, no workspace, no allocation or synchronisation:
+ * capturable, and the result is a function of the arguments alone, bit for bit. */
+#define MAUA_PULSE_MAX_FRAMES (1 << 22)
+#define MAUA_PULSE_MAX_WIN 2048
+#define MAUA_PULSE_MAX_TEMPI 1024
+int maua_tempogram_peak_f32(const float* env, int n, const float* table /*[n_tempi][win][2]*/, int win, int n_tempi,
+                            const float* prior /*[n_tempi] or NULL*/, int* bin /*[n]*/, float* phase /*[n]*/, float* power /*[n]*/,
+                            float* tgram /*[n][n_tempi] or NULL*/, void* stream);
+int maua_pulse_synth_f32(const int* bin, const float* phase, int n, const float* window /*[win]*/, int win,
+                         const float* omega /*[n_tempi]*/, int n_tempi, float* pulse /*[n]*/, void* stream);
+
 /* Spectrogram factorisation (audioreactive nmf / decompose / components; csrc/nmf.hip; additive: the ABI version is unchanged).
  * Non-negative matrix factorisation V [F, T] ~ W [F, K] . H [K, T] under the generalised Kullback-Leibler divergence by multiplicative
  * updates (Lee & Seung 2000), in place, all fp32 and contiguous: V with frames contiguous, W contiguous in k, H contiguous in t.
