@@ -635,6 +635,50 @@ int maua_tempogram_peak_f32(const float* env, int n, const float* table /*[n_tem
 int maua_pulse_synth_f32(const int* bin, const float* phase, int n, const float* window /*[win]*/, int win,
                          const float* omega /*[n_tempi]*/, int n_tempi, float* pulse /*[n]*/, void* stream);
 
+/* Hidden Markov models with a dense transition matrix (audioreactive viterbi / hmm_posterior / raw_chords / chords; csrc/hmm.hip;
+ * additive: the ABI version is unchanged).  Two entries over S = n_states states and T = n_frames frames: the most probable path
+ * (Viterbi) and the per-frame state posteriors (scaled forward-backward; Rabiner, "A tutorial on hidden Markov models and selected
+ * applications in speech recognition", Proc. IEEE 1989, III.A-B and V.A).  Matrices are row-major with row = source state i and
+ * column = target state j; observations are fp32 and widened exactly, everything else is float64.  tests/hmm_ref.py restates both in
+ * numpy, bit for bit.
+ *
+ * maua_hmm_viterbi_f64: logobs [T, S], log_trans [S, S], log_init [S] are logarithms.  Every operation is a double addition or compare:
+ *   Frame 0.  delta[j] = log_init[j] + logobs[0, j]; backptr[0, j] = j.
+ *   Frame t >= 1, target j.  best = delta[0] + log_trans[0][j] with index 0; then i = 1 .. S - 1 ascending, the candidate
+ *     delta[i] + log_trans[i][j] replacing best (and the index) only when strictly greater: ties go to the lowest i, a NaN never
+ *     replaces (and a NaN at i = 0 is never replaced).  delta'[j] = best + logobs[t, j]; backptr[t, j] = the index.
+ *   End.  states[T - 1] = the first maximum of the final delta under the same rule (from state 0, replaced only by a strictly greater
+ *     one); states[t - 1] = backptr[t][states[t]].
+ * delta_last [S] (the final delta), every element of backptr [T, S] and of states [T] are written.  -inf is legal anywhere (forbidden
+ * transitions; a frame of nothing but -inf decodes to the lowest index); a NaN does not fault, the rules above define what it does.
+ *
+ * maua_hmm_posterior_f64: obs [T, S] are likelihoods >= 0 up to a factor per frame, trans [S, S] and init [S] probabilities.  Every
+ * product, sum and quotient below is one float64 operation rounded on its own (no fused multiply-add anywhere):
+ *   Forward, frame 0.  a[j] = init[j] * obs[0, j].
+ *   Forward, frame t >= 1.  p[j] = the chain acc = acc + alpha_{t-1}[i] * trans[i][j] from acc = 0.0 over i = 0 .. S - 1 ascending;
+ *     a[j] = p[j] * obs[t, j].
+ *   Both.  c_t = the chain acc = acc + a[j] from 0.0 over j ascending; alpha_t[j] = a[j] / c_t.
+ *   Backward, from beta_{T-1}[i] = 1, t = T - 2 .. 0.  u[j] = obs[t + 1, j] * beta_{t+1}[j]; q[i] = the chain
+ *     acc = acc + trans[i][j] * u[j] from 0.0 over j ascending; beta_t[i] = q[i] / c_{t+1}.
+ *   Outputs.  gamma[t, i] = alpha_t[i] * beta_t[i], not renormalised (its rows sum to 1 within rounding); gamma[T - 1] = alpha_{T-1},
+ *     no product.  scale[t] = c_t: the sum of their logarithms is the log-likelihood of the observations (plus the logarithms of
+ *     whatever factors the caller took out of the rows of obs).
+ * gamma holds alpha between the two sweeps: there is no workspace.  Every element of gamma [T, S] and scale [T] is written.  A frame
+ * whose likelihoods are all zero gives c_t = 0 and IEEE NaN from that frame on in alpha and scale, and in all of gamma; nothing faults.
+ *
+ * Both: MAUA_EINVAL, without a launch and with the outputs untouched, on a NULL pointer, n_frames outside 1 .. MAUA_HMM_MAX_FRAMES,
+ * n_states outside 1 .. MAUA_HMM_MAX_STATES.  No atomics, no workspace, no allocation or synchronisation: capturable, and the result is
+ * a function of the arguments alone, bit for bit and run to run.  One workgroup each, a lane per state, the transition matrix staged
+ * once in LDS: latency-bound by construction (one or two barriers per frame), like maua_pyin_viterbi_f64. */
+#define MAUA_HMM_MAX_STATES 128
+#define MAUA_HMM_MAX_FRAMES (1 << 22)
+int maua_hmm_viterbi_f64(const float* logobs /*[n_frames, n_states]*/, const double* log_trans /*[n_states, n_states]*/,
+                         const double* log_init /*[n_states]*/, int n_frames, int n_states, double* delta_last /*[n_states]*/,
+                         uint8_t* backptr /*[n_frames, n_states]*/, int32_t* states /*[n_frames]*/, void* stream);
+int maua_hmm_posterior_f64(const float* obs /*[n_frames, n_states]*/, const double* trans /*[n_states, n_states]*/,
+                           const double* init /*[n_states]*/, int n_frames, int n_states, double* gamma /*[n_frames, n_states]*/,
+                           double* scale /*[n_frames]*/, void* stream);
+
 /* Spectrogram factorisation (audioreactive nmf / decompose / components; csrc/nmf.hip; additive: the ABI version is unchanged).
  * Non-negative matrix factorisation V [F, T] ~ W [F, K] . H [K, T] under the generalised Kullback-Leibler divergence by multiplicative
  * updates (Lee & Seung 2000), in place, all fp32 and contiguous: V with frames contiguous, W contiguous in k, H contiguous in t.

@@ -148,6 +148,8 @@ _SIGNATURES = {
     "maua_pyin_viterbi_f64": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_double, c_double, c_double, _P, _P, _P, _P]),
     "maua_tempogram_peak_f32": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "maua_pulse_synth_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
+    "maua_hmm_viterbi_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
+    "maua_hmm_posterior_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
     "maua_nmf_kl_f32": (c_int, [_P, _P, _P] + [c_int] * 6 + [c_float, _P]),
     "maua_nmf_kl_div_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
     "maua_nmf_separate_f32": (c_int, [_P, _P, _P, _P, POINTER(ctypes.c_int32)] + [c_int] * 7 + [_P, _P, _P]),
