@@ -758,6 +758,56 @@ int maua_knn_links_f32(const float* x, int d, int s, int k, int width, float* li
  * j' = j + s reflected at the edges (d c b a | a b c d), 0 for a row outside [0, s). */
 int maua_rec_affinity_f32(const float* links, int s, float bandwidth, float* rec, float* rec_filt, void* stream);
 
+/* Recursive (IIR) filters (audioreactive filters: sosfilt, sosfiltfilt, bandpass, bands, envelope; csrc/iir.hip; additive: the ABI
+ * version is unchanged).
+ *
+ * maua_sosfilt_f64: n_filters (F) filters in one call, each a cascade of n_sections second-order sections sos [F, n_sections, 6] in
+ * scipy's layout [b0 b1 b2 a0 a1 a2]; a0 is taken as 1 and never read (the caller normalises).  Filter f runs over its own signal
+ * x[f, 0 .. n) (n_signals == F) or all filters over one signal (n_signals == 1, the filter bank).  Exactly one of x_f32 / x_f64 is set
+ * (a float sample is widened exactly); y_f64 and / or y_f32 [F, n] receive the result, y_f32 the round-to-nearest-even of the double that
+ * y_f64 receives.  zi / zf [F, n_sections, 2] are the optional initial / final states (z1, z2) of every section; zi == NULL starts from 0.
+ * Per sample, section by section (the input of section s + 1 is the y of section s), every operation in double, each line ONE rounding:
+ *     y  = fma(b0, x, z1)
+ *     z1 = fma(-a1, y, fma(b1, x, z2))
+ *     z2 = fma(-a2, y, b2 * x)
+ * which is scipy.signal.sosfilt's transposed direct form II  y = b0 x + z1;  z1 = b1 x - a1 y + z2;  z2 = b2 x - a2 y  with fused roundings.
+ * Time is cut into nc = ceil(n / chunk) chunks of `chunk` samples (the last may be shorter); chunk == 0 selects
+ * maua_sosfilt_default_chunk(n).  With D = 2 n_sections and the state vector (z1, z2 of section 0, z1, z2 of section 1, ...):
+ *   1. A [D, D] per filter: column j is the state after `chunk` samples of zero input from the unit state e_j (the recurrence above);
+ *   2. Z_c, c < nc - 1: the state after chunk c filtered from the zero state;
+ *   3. S_0 = zi (or 0);  S_{c+1}[i] = acc + Z_c[i]  with  acc = 0;  acc = fma(A[i][j], S_c[j], acc)  for j ascending;
+ *   4. chunk c is filtered again from S_c and y is written; zf is the state after the last sample.
+ * Exact in exact arithmetic, whatever the chunk length; the order above is fixed, nothing is reduced across lanes and there are no
+ * atomics, so two calls give identical bits (a result does depend on `chunk`, in its last bits).  A NaN in x[t] leaves every output before
+ * t with the bits of the NaN-free call and, for a filter whose b0 are non-zero, makes every output from t on a NaN.
+ * ws: maua_sosfilt_ws_doubles(F, n_sections, n, chunk) doubles of device memory (A, Z and S; -1 for arguments the entry refuses).  The
+ * entry enqueues four launches on `stream` (two where nc == 1), never allocates, never synchronises and can be captured.  n == 0 is a
+ * successful no-op that sets zf = zi (0 without zi).
+ * maua_sosfilt_default_chunk(n): the smallest power of two p in [64, 4096] with MAUA_SOS_CHUNK_BALANCE p^2 >= n (4096 beyond): the
+ * serial carry costs time per chunk, the passes per sample of a chunk, and their sum is least near chunk = sqrt(n / 4) as measured
+ * (DESIGN.md 4.22); this is the power of two nearest to it in ratio: 64 up to 32 768 samples, 1024 for 2.1 M .. 8.4 M (a 240 s clip).
+ * MAUA_EINVAL, without a launch: n_sections outside 1 .. MAUA_SOS_MAX_SECTIONS, F outside 1 .. MAUA_SOS_MAX_FILTERS, n_signals not 1 or F,
+ * n < 0, chunk < 0 or > MAUA_SOS_MAX_CHUNK, both or neither of x_f32 / x_f64, neither y_f64 nor y_f32, a null sos or ws. */
+#define MAUA_SOS_MAX_SECTIONS 16
+#define MAUA_SOS_MAX_FILTERS 64
+#define MAUA_SOS_MAX_CHUNK 65536
+#define MAUA_SOS_CHUNK_BALANCE 8
+int maua_sosfilt_default_chunk(int n);
+int64_t maua_sosfilt_ws_doubles(int n_filters, int n_sections, int n, int chunk);
+int maua_sosfilt_f64(const double* sos /*[F, n_sections, 6]*/, int n_filters, int n_sections, const float* x_f32, const double* x_f64,
+                     int n_signals /*1 or F*/, int n, int chunk, const double* zi, double* y_f64, float* y_f32, double* zf, double* ws,
+                     void* stream);
+/* maua_env_follow_f32: attack / release envelope follower over x [n_frames, n_cols] (frames outermost), one lane per column:
+ *     d = x[t] - y[t-1];  k = x[t] > y[t-1] ? attack_coef : release_coef;  p = k * d;  y[t] = y[t-1] + p
+ * three float32 operations — a subtraction, a product, a sum — each rounded to nearest once and never fused (the kernel is compiled
+ * with `#pragma clang fp contract(off)`; the __fmul_rn / __fadd_rn intrinsics are not enough, the compiler fuses them into an fma), so a
+ * numpy float32 restatement gives the same bits.  y[-1] = y0[col] where
+ * y0 is given, else x[0][col] (so y[0] = x[0]).  A NaN in x[t] makes the comparison false: the release branch is taken and the NaN
+ * stays in that column from t on (other columns keep their bits).  y must not overlap x.  n_frames == 0 is a successful no-op.
+ * MAUA_EINVAL, without a launch: a null x or y, n_frames < 0, n_cols < 1, a coefficient outside [0, 1] or NaN. */
+int maua_env_follow_f32(const float* x, const float* y0 /*[n_cols] or NULL*/, float* y, int n_frames, int n_cols, float attack_coef,
+                        float release_coef, void* stream);
+
 /* 3-D tileable Perlin noise (audioreactive/latent.py:188-246): grad [r0+1,r1+1,r2+1,3] -> out [n0,n1,n2]. */
 int maua_perlin3d_f32(const float* grad, float* out, int n0, int n1, int n2, int r0, int r1, int r2, void* stream);
 

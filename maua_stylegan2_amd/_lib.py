@@ -150,6 +150,10 @@ _SIGNATURES = {
     "maua_pulse_synth_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
     "maua_hmm_viterbi_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
     "maua_hmm_posterior_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
+    "maua_sosfilt_default_chunk": (c_int, [c_int]),
+    "maua_sosfilt_ws_doubles": (c_int64, [c_int] * 4),
+    "maua_sosfilt_f64": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "maua_env_follow_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, _P]),
     "maua_nmf_kl_f32": (c_int, [_P, _P, _P] + [c_int] * 6 + [c_float, _P]),
     "maua_nmf_kl_div_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
     "maua_nmf_separate_f32": (c_int, [_P, _P, _P, _P, POINTER(ctypes.c_int32)] + [c_int] * 7 + [_P, _P, _P]),

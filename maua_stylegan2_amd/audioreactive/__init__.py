@@ -4,6 +4,7 @@ from . import signal as _signal_module
 from .beat import *  # noqa: F401,F403  (raw_plp, tempogram, pulse, tempo, beats, beat_phase: the predominant local pulse, no counterpart in the reference)
 from .bend import *  # noqa: F401,F403
 from .decompose import *  # noqa: F401,F403  (nmf, decompose, components: spectrogram factorisation, no counterpart in the reference)
+from .filters import *  # noqa: F401,F403  (sosfilt, sosfiltfilt, bandpass, envelope, bands: recursive filters on the device, no counterpart in the reference)
 from .harmony import *  # noqa: F401,F403  (viterbi, hmm_posterior, chord_vocabulary, raw_chords, chords, key: chords and key, no counterpart in the reference)
 from .latent import *  # noqa: F401,F403
 from .noise import *  # noqa: F401,F403  (NoiseSynth, noise_term: synthesised noise slots, no counterpart in the reference)

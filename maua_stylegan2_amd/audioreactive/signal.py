@@ -38,6 +38,19 @@ def set_SMF(smf):
     SMF = smf
 
 
+FILTER = "host"  # where rms / pitch run their Butterworth band-pass: "host" (scipy.signal.sosfilt, the reference's path) or "device"
+
+
+def set_filter(where):
+    """Choose where :func:`rms` and :func:`pitch` run their band-pass: ``"host"`` (the default: scipy on one core, today's numbers) or
+    ``"device"`` (the same coefficients through ``ar.sosfilt``, csrc/iir.hip).  :func:`rms` mirrors the reference's signature and takes
+    no keyword for it; ``pitch(filter=)`` overrides the setting for one call."""
+    global FILTER
+    if where not in ("host", "device"):
+        raise ValueError(f"unknown filter {where!r} (expected 'host' or 'device')")
+    FILTER = where
+
+
 def _dev():
     return th.device("cuda", th.cuda.current_device())
 
@@ -406,10 +419,24 @@ def onsets(audio, sr, n_frames, margin=8, fmin=20, fmax=8000, smooth=1, clip=100
     return onset.to(device if device is not None else "cpu")
 
 
+def _butter_bandpass(y, sr, fmin, fmax, filter):
+    """The 12-section Butterworth band-pass of :func:`rms` and :func:`pitch` as float32: ``filter="host"`` runs scipy.signal.sosfilt on
+    one core (the clip travels to the host and back), ``"device"`` the same coefficients through :func:`filters.sosfilt` (csrc/iir.hip)."""
+    sos = scipy.signal.butter(12, [fmin, fmax], "bp", fs=sr, output="sos")
+    if filter == "host":
+        y = y.detach().cpu().numpy() if isinstance(y, th.Tensor) else np.asarray(y)
+        return scipy.signal.sosfilt(sos, y).astype(np.float32)
+    if filter == "device":
+        from .filters import sosfilt
+
+        return sosfilt(sos, _to_dev(y).reshape(-1))
+    raise ValueError(f"unknown filter {filter!r} (expected 'host' or 'device')")
+
+
 def rms(y, sr, n_frames, fmin=20, fmax=8000, smooth=180, clip=50, power=6, device=None):
-    y_filt = scipy.signal.sosfilt(scipy.signal.butter(12, [fmin, fmax], "bp", fs=sr, output="sos"), np.asarray(y))
+    y_filt = _butter_bandpass(y, sr, fmin, fmax, FILTER)  # (:func:`set_filter`)
     n_fft = 2048
-    p = stft_power(y_filt.astype(np.float32), n_fft, 512)
+    p = stft_power(y_filt, n_fft, 512)
     wts = np.ones((1, n_fft // 2 + 1), np.float32)
     wts[0, 0] = wts[0, -1] = 0.5
     env = th.sqrt(project(wts * (2.0 / n_fft ** 2), p))[0]
@@ -739,7 +766,7 @@ def lerp_resize(x, num):
 
 
 def pitch(audio, sr, n_frames, fmin=65.0, fmax=2100.0, margin=8, bandpass=False, voicing=0.5, smooth=2, return_voicing=False, device=None,
-          method="yin"):
+          method="yin", filter=None):
     """Pitch height of the melody in [0, 1] per video frame (0 = ``fmin``, 1 = ``fmax``, logarithmic), a CPU tensor unless ``device=`` is
     given: harmonic separation (``margin``; None / 0 skips it) -> optionally the Butterworth band-pass of :func:`rms` over [fmin, fmax]
     (a bass line under a lead) -> :func:`raw_pitch` -> log height -> frames less confident than ``voicing`` hold the last voiced height
@@ -748,13 +775,13 @@ def pitch(audio, sr, n_frames, fmin=65.0, fmax=2100.0, margin=8, bandpass=False,
     ``return_voicing`` adds the confidence envelope, interpolated and smoothed the same way.
     ``method="pyin"`` tracks with :func:`raw_pyin` instead (noisy tones, stems, mixed tracks): the frames its decoder calls unvoiced hold
     the last voiced height, there is no median (the decoder has done that work), ``voicing`` is ignored, and ``return_voicing`` returns
-    the envelope of the voiced probability."""
+    the envelope of the voiced probability.  ``filter="device"`` / ``"host"`` says where the band-pass runs for this call (default:
+    :func:`set_filter`'s setting)."""
     if method not in ("yin", "pyin"):
         raise ValueError(f"pitch: unknown method {method!r}: use 'yin' or 'pyin'")
     y = harmonic(audio, margin=margin) if margin else audio
     if bandpass:
-        y = y.detach().cpu().numpy() if isinstance(y, th.Tensor) else np.asarray(y)
-        y = scipy.signal.sosfilt(scipy.signal.butter(12, [fmin, fmax], "bp", fs=sr, output="sos"), y).astype(np.float32)
+        y = _butter_bandpass(y, sr, fmin, fmax, FILTER if filter is None else filter)
     if method == "pyin":
         f0, voiced, confidence = raw_pyin(y, sr, fmin=fmin, fmax=fmax)
     else:
