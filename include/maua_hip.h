@@ -794,6 +794,16 @@ int maua_rec_affinity_f32(const float* links, int s, float bandwidth, float* rec
 #define MAUA_SOS_CHUNK_BALANCE 8
 int maua_sosfilt_default_chunk(int n);
 int64_t maua_sosfilt_ws_doubles(int n_filters, int n_sections, int n, int chunk);
+/* maua_sosfilt_plan: what a maua_sosfilt_f64 call with these shape arguments does, computed on the host from the entry's own constants
+ * and checks; nothing is launched and no device is needed (the tests prove with it what their case lists reach).  MAUA_EINVAL where the
+ * entry refuses the same four arguments (n_sections, F, n, chunk as listed above) and for a null out; else 0 and
+ *   out[0] the chunk length used (maua_sosfilt_default_chunk(n) for chunk == 0);   out[1] nc = ceil(n / out[0]);
+ *   out[2] launches: 4, 2 where nc == 1, and at n == 0 the one that sets zf (none where zf == NULL);
+ *   out[3] workgroups per filter of the zero-state pass, ceil((nc - 1) / 64): a lane per chunk before the last (0: no such launch);
+ *   out[4] workgroups per filter of the final pass, ceil(nc / 64);
+ *   out[5] 16-sample tiles a lane walks through a full chunk, ceil(out[0] / 16);   out[6] samples in the last of them, 1 .. 16;
+ *   out[7] length of the last chunk, 1 .. out[0] (0 at n == 0). */
+int maua_sosfilt_plan(int n_filters, int n_sections, int n, int chunk, int32_t* out /*[8]*/);
 int maua_sosfilt_f64(const double* sos /*[F, n_sections, 6]*/, int n_filters, int n_sections, const float* x_f32, const double* x_f64,
                      int n_signals /*1 or F*/, int n, int chunk, const double* zi, double* y_f64, float* y_f32, double* zf, double* ws,
                      void* stream);

@@ -152,6 +152,7 @@ _SIGNATURES = {
     "maua_hmm_posterior_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
     "maua_sosfilt_default_chunk": (c_int, [c_int]),
     "maua_sosfilt_ws_doubles": (c_int64, [c_int] * 4),
+    "maua_sosfilt_plan": (c_int, [c_int] * 4 + [POINTER(ctypes.c_int32)]),
     "maua_sosfilt_f64": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "maua_env_follow_f32": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, _P]),
     "maua_nmf_kl_f32": (c_int, [_P, _P, _P] + [c_int] * 6 + [c_float, _P]),
@@ -282,6 +283,17 @@ def planned_upfirdn2d_instance(major, in_h, in_w, minor, kh, kw, up_x, up_y, dow
     name, _, tiles = buf.value.decode().partition(" ")
     tiles_x, tiles_y = (int(v) for v in tiles.split("x")) if tiles else (0, 0)
     return rc, name, tiles_x, tiles_y
+
+
+SOSFILT_PLAN_FIELDS = ("chunk", "nc", "launches", "zero_groups", "final_groups", "tiles", "last_tile", "last_chunk")
+
+
+def planned_sosfilt(n_filters, n_sections, n, chunk=0):
+    """(rc, plan): what maua_sosfilt_f64 would do with these shape arguments, as a dict over SOSFILT_PLAN_FIELDS (rc 0), or its refusal
+    (plan None).  Shapes only, no launch: works without a GPU."""
+    out = (ctypes.c_int32 * 8)()
+    rc = load().maua_sosfilt_plan(n_filters, n_sections, n, chunk, out)
+    return rc, (dict(zip(SOSFILT_PLAN_FIELDS, out)) if rc == 0 else None)
 
 
 class HipEvent:

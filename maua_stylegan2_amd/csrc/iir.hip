@@ -220,6 +220,11 @@ __global__ __launch_bounds__(64) void env_follow_kernel(const float* __restrict_
     }
 }
 
+// nc = ceil(n / chunk) and the workgroups of a pass over `chunks` chunks, a lane each, for any n an int holds (n + chunk - 1 and
+// nc + 63 need not fit one).
+int sos_chunks(int n, int chunk) { return (int)ceil_div64(n, chunk); }
+int sos_groups(int chunks) { return (int)ceil_div64(chunks, SOS_LANES); }
+
 struct SosArgs {
     const double* sos;
     const float* xf;
@@ -234,11 +239,11 @@ struct SosArgs {
 
 template <int NS>
 int sos_launch(const SosArgs& a) {
-    const dim3 grid_final(ceil_div(a.nc, SOS_LANES), a.F);
+    const dim3 grid_final(sos_groups(a.nc), a.F);
     if (a.nc > 1) {
         hipLaunchKernelGGL(sos_trans_kernel<NS>, dim3(a.F), dim3(SOS_LANES), 0, a.st, a.sos, a.chunk, a.A);
         MAUA_LAUNCH_CHECK();
-        const dim3 grid_zero(ceil_div(a.nc - 1, SOS_LANES), a.F);
+        const dim3 grid_zero(sos_groups(a.nc - 1), a.F);
         hipLaunchKernelGGL((sos_pass_kernel<NS, false>), grid_zero, dim3(SOS_LANES), 0, a.st, a.sos, a.xf, a.xd, a.shared_signal, a.n, a.chunk,
                            a.nc, (const double*)nullptr, a.Z, (double*)nullptr, (float*)nullptr, (double*)nullptr);
         MAUA_LAUNCH_CHECK();
@@ -267,8 +272,25 @@ extern "C" int maua_sosfilt_default_chunk(int n) {
 extern "C" int64_t maua_sosfilt_ws_doubles(int n_filters, int n_sections, int n, int chunk) {
     if (!sos_shape_ok(n_filters, n_sections, n, chunk)) return -1;
     if (chunk == 0) chunk = maua_sosfilt_default_chunk(n);
-    const int64_t D = 2 * n_sections, nc = ceil_div64(n, chunk);
+    const int64_t D = 2 * n_sections, nc = sos_chunks(n, chunk);
     return n_filters * (D * D + 2 * nc * D);
+}
+
+// What a call with these shape arguments does, from the constants and the checks of the entry below; nothing is launched.
+extern "C" int maua_sosfilt_plan(int n_filters, int n_sections, int n, int chunk, int32_t* out) {
+    if (!out || !sos_shape_ok(n_filters, n_sections, n, chunk)) return MAUA_EINVAL;
+    if (chunk == 0) chunk = maua_sosfilt_default_chunk(n);
+    const int nc = sos_chunks(n, chunk);
+    const int last_tile = chunk % SOS_TILE ? chunk % SOS_TILE : SOS_TILE;
+    out[0] = chunk;
+    out[1] = nc;
+    out[2] = n == 0 ? 1 : nc == 1 ? 2 : 4;                    // (at n == 0 the one launch copies zi to zf, where zf is asked for)
+    out[3] = n == 0 ? 0 : sos_groups(nc - 1);                 // zero-state pass, grid.x (none at nc == 1)
+    out[4] = n == 0 ? 0 : sos_groups(nc);                     // final pass, grid.x
+    out[5] = ceil_div(chunk, SOS_TILE);                       // LDS tiles a lane walks per full chunk
+    out[6] = last_tile;                                       // samples in the last of them
+    out[7] = n == 0 ? 0 : n - (nc - 1) * chunk;               // length of the last chunk
+    return 0;
 }
 
 extern "C" int maua_sosfilt_f64(const double* sos, int n_filters, int n_sections, const float* x_f32, const double* x_f64, int n_signals,
@@ -286,7 +308,7 @@ extern "C" int maua_sosfilt_f64(const double* sos, int n_filters, int n_sections
         return 0;
     }
     if (chunk == 0) chunk = maua_sosfilt_default_chunk(n);
-    const int nc = ceil_div(n, chunk);
+    const int nc = sos_chunks(n, chunk);
     SosArgs a{sos, x_f32, x_f64, n_signals == 1 ? 1 : 0, n, chunk, nc, F, zi, y_f64, y_f32, zf, ws, ws + (int64_t)F * D * D,
               ws + (int64_t)F * D * D + (int64_t)F * nc * D, st};
     switch (n_sections) {

@@ -62,7 +62,8 @@ def chunked(sos, x, chunk, zi=None, variant=None):
     """The chunked algorithm of maua_sosfilt_f64 in float64, in the defined order: transition matrix from unit states, zero-state pass,
     carry with every dot product summed in ascending index order, final pass.  -> (y [F, n], zf [F, ns, 2]).
     ``variant`` names a deliberately WRONG version (the host test shows that the comparisons catch each): "carry_dropped",
-    "carry_late", "sections_reversed", "zi_swapped"."""
+    "carry_late", "sections_reversed", "zi_swapped", "zi_of_filter_0" (every filter starts from filter 0's state), "last_chunk_full"
+    (a short last chunk is walked on, over zeros, to the full length before zf is taken)."""
     sos = as_bank(sos)
     F, ns = sos.shape[:2]
     D = 2 * ns
@@ -72,6 +73,8 @@ def chunked(sos, x, chunk, zi=None, variant=None):
     z0 = np.zeros((F, ns, 2)) if zi is None else np.array(zi, dtype=np.float64).reshape(F, ns, 2)
     if variant == "zi_swapped":
         z0 = z0[:, :, ::-1]
+    elif variant == "zi_of_filter_0":
+        z0 = np.repeat(z0[:1], F, axis=0)
     if n == 0:
         return np.empty((F, 0)), z0.copy()
     order = range(ns - 1, -1, -1) if variant == "sections_reversed" else range(ns)
@@ -112,7 +115,7 @@ def chunked(sos, x, chunk, zi=None, variant=None):
     y = np.empty((F, nc, chunk))
     z1 = [S[:, :, 2 * s].copy() for s in range(ns)]
     z2 = [S[:, :, 2 * s + 1].copy() for s in range(ns)]
-    last = n - (nc - 1) * chunk
+    last = chunk if variant == "last_chunk_full" else n - (nc - 1) * chunk
     _walk(co, lambda t: xc[:, :, t], z1, z2, last, out=y)
     if last < chunk:
         full1, full2 = [a[:, :-1] for a in z1], [a[:, :-1] for a in z2]
@@ -255,3 +258,148 @@ def exact_signal(n, seed=3):
 def same_bits(a, b):
     a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ every instance, every chunk-grid edge
+# maua_sosfilt_f64 dispatches on n_sections to 16 template instances with their own register arrays and strides; the lists below reach
+# each of them, and every edge of the chunk grid, on purpose (tests/test_iir_host.py proves it through maua_sosfilt_plan).
+ALL_NS = tuple(range(1, 17))
+
+# Integer sections [b0 b1 b2 1 a1 a2]: three FIRs of two taps or three, two integrators (one over every other sample) and three
+# differences that keep the integrators from growing.  Small integers stay integers: every order of summation gives the same bits.
+PATTERN = np.array([[1.0, 2, 1, 1, 0, 0], [1, -1, 0, 1, 0, 0], [1, 0, 0, 1, -1, 0], [1, 1, 0, 1, 0, 0],
+                    [1, 0, -1, 1, 0, 0], [1, 0, 0, 1, 0, -1], [2, -1, 1, 1, 0, 0], [1, -2, 1, 1, 0, 0]])
+
+
+def cascade(ns, F=1):
+    """sos [F, ns, 6]: section s of filter f is PATTERN[(s + f) % 8] — filter f is the pattern rotated by f."""
+    return np.stack([PATTERN[(np.arange(ns) + f) % len(PATTERN)] for f in range(F)])
+
+
+def cascade_zi(F, ns):
+    """zi [F, ns, 2] = 1, 2, 3, ... over the whole array: every filter, section and state starts from another number."""
+    return np.arange(1, 2 * F * ns + 1, dtype=np.float64).reshape(F, ns, 2)
+
+
+def exact_signals(F, n, seed=3):
+    return np.random.default_rng(seed).integers(-8, 9, (F, n)).astype(np.float64)
+
+
+INSTANCE_N = 203
+INSTANCE_CHUNKS = (5, 17, 64)
+
+
+def instance_case(ns):
+    """(sos [2, ns, 6], x [2, INSTANCE_N], zi [2, ns, 2]) of test_sosfilt_every_instance_on_integers[ns]."""
+    return cascade(ns, 2), exact_signals(2, INSTANCE_N, seed=100 + ns), cascade_zi(2, ns)
+
+
+# Butterworth band-passes of n_sections sections (order n_sections: a band-pass doubles it), the bands of `pitch`, `mid12` and `mid16`.
+BP_BANDS = ((65, 2100), (200, 2000), (300, 3000))
+BP_N = 3000
+BP_CHUNKS = (17, 64, 0)
+BP_MODES = ("bank_shared", "bank_own")
+_BP_PAIRS = ((0, 0), (1, 0), (2, 0), (1, 1), (2, 2))  # (band, signal): the bank over signal 0 and over its own signals
+
+
+@functools.lru_cache(maxsize=None)
+def bp_bank(ns):
+    """sos [3, ns, 6]: butter(ns, band, "bp") for the three bands."""
+    return np.stack([_butter(ns, list(band), "bp") for band in BP_BANDS])
+
+
+def bp_signals(mode):
+    return (0, 0, 0) if mode == "bank_shared" else (0, 1, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _bp_longdouble_all():
+    """Every (n_sections, band, signal) of the list through the long-double loop in ONE walk over BP_N samples, the filters padded to 16
+    sections with identity sections (exact)."""
+    keys = [(ns, b, s) for ns in ALL_NS for b, s in _BP_PAIRS]
+    sos = np.stack([np.concatenate([bp_bank(ns)[b], np.tile(IDENTITY, (16 - ns, 1))]) for ns, b, _ in keys])
+    x = np.stack([signals()[s, :BP_N] for _, _, s in keys])
+    y, _ = sequential(sos, x, dtype=np.longdouble)
+    return {k: y[i] for i, k in enumerate(keys)}
+
+
+def bp_longdouble(ns, band, sig):
+    return _bp_longdouble_all()[(ns, band, sig)]
+
+
+def errors_sos(sos, x, chunk, ref):
+    """`errors` for any filter: (err_chunked_f64, err_sequential_f64) of sos [ns, 6] over x against the long-double result ``ref``,
+    relative to max |ref|; the sequential one is scipy's own."""
+    x = np.asarray(x, dtype=np.float64)
+    return rel_err(chunked(sos, x, chunk)[0][0], ref), rel_err(scipy.signal.sosfilt(sos, x), ref)
+
+
+@functools.lru_cache(maxsize=None)
+def _bp_errors(ns, chunk):
+    """(band, signal) -> (err_chunked_f64, err_sequential_f64) over BP_N samples; the five filters of an order in one chunked walk."""
+    sos = np.stack([bp_bank(ns)[b] for b, _ in _BP_PAIRS])
+    x = np.stack([signals()[s, :BP_N] for _, s in _BP_PAIRS]).astype(np.float64)
+    y = chunked(sos, x, chunk)[0]
+    return {(b, s): (rel_err(y[i], bp_longdouble(ns, b, s)), rel_err(scipy.signal.sosfilt(sos[i], x[i]), bp_longdouble(ns, b, s)))
+            for i, (b, s) in enumerate(_BP_PAIRS)}
+
+
+def bp_allowance(ns, band, sig, chunk):
+    """The rule of `allowance`, unchanged, for a filter of this list: 4 max(err_chunked_f64, err_sequential_f64, 16 * 2^-53) of the case
+    itself (0: the default chunk for BP_N samples), from the numpy restatements alone."""
+    return 4.0 * max(*_bp_errors(ns, chunk or default_chunk(BP_N))[(band, sig)], 16 * EPS)
+
+
+# The chunk grid.  Every class is a bank of two integer cascades (3 or 5 sections) over their own signals from a non-zero state, unless
+# it says otherwise: name -> dict(ns, F, n, chunk, shared, sos, zi), the signal from `geometry_operands`.
+SOS_TILE, SOS_LANES, SOS_AHEAD = 16, 64, 8  # the documented constants of csrc/iir.hip
+MAX_CHUNK, MAX_FILTERS = 65536, 64          # MAUA_SOS_MAX_CHUNK, MAUA_SOS_MAX_FILTERS
+LARGEST_CHUNK = MAX_CHUNK                   # the chunk of the largest-chunk class (profiles/iir.md records the time of its call)
+TILE_CHUNKS = (1, 15, 16, 17, 31, 33, 100)
+NC_AT_5 = (1, 2, 8, 9, 10, 16, 17, 18, 64, 65, 66, 128, 129, 130)
+NC_AT_17 = (9, 65, 66)
+
+
+def _geometry():
+    g = {}
+    for chunk in TILE_CHUNKS:  # three chunks, the last 1, chunk - 1 or chunk samples long
+        for last in sorted({1, chunk} | ({chunk - 1} if chunk - 1 > 1 else set())):
+            g[f"chunk{chunk}_last{last}"] = dict(chunk=chunk, n=2 * chunk + last)
+    for chunk, counts in ((5, NC_AT_5), (17, NC_AT_17)):  # the carry's look-ahead and the workgroup counts; the last chunk 3 long
+        for nc in counts:
+            g[f"nc{nc}_chunk{chunk}"] = dict(chunk=chunk, n=(nc - 1) * chunk + 3)
+    for turn, (name, case) in enumerate(g.items()):
+        ns = (3, 5)[turn % 2]
+        case.update(ns=ns, F=2, shared=False, sos=cascade(ns, 2), zi=cascade_zi(2, ns))
+    mix = np.stack([EXACT["mix"], EXACT["mix"][::-1]])
+    g["chunk4096"] = dict(chunk=4096, n=3 * 4096 + 5, ns=2, F=2, shared=False, sos=mix, zi=cascade_zi(2, 2))
+    g["chunk4096_zero_state"] = dict(chunk=4096, n=3 * 4096 + 5, ns=2, F=2, shared=False, sos=mix, zi=None)
+    g["largest_chunk"] = dict(chunk=LARGEST_CHUNK, n=2 * LARGEST_CHUNK + 3, ns=1, F=1, shared=True, sos=EXACT["running_sum"][None], zi=None)
+    for shared in (True, False):
+        g[f"filters64_{'shared' if shared else 'own'}"] = dict(chunk=17, n=203, ns=3, F=MAX_FILTERS, shared=shared,
+                                                               sos=cascade(3, MAX_FILTERS), zi=cascade_zi(MAX_FILTERS, 3))
+    return g
+
+
+GEOMETRY = _geometry()
+
+
+def geometry_operands(name):
+    """(sos [F, ns, 6], x [n] or [F, n], zi or None) of a class."""
+    case = GEOMETRY[name]
+    x = exact_signals(case["F"], case["n"], seed=sorted(GEOMETRY).index(name))
+    return case["sos"], (x[0] if case["shared"] else x), case["zi"]
+
+
+@functools.lru_cache(maxsize=None)
+def geometry_reference(name):
+    """(y [F, n], zf [F, ns, 2]) in float64, exact: the sequential loop (on these integers it has the bits of the long-double one), but
+    for the two classes that start from the zero state y is the vectorised cumsum(convolve(x, [1, 2, 1])) (either order of the two
+    sections: they commute from a zero state) and cumsum(x), and the state behind the longest chunk is the sum itself."""
+    sos, x, zi = geometry_operands(name)
+    if name == "largest_chunk":
+        y = np.cumsum(x)[None]
+        return y, np.array([[[y[0, -1], 0.0]]])
+    if name == "chunk4096_zero_state":
+        return np.stack([np.cumsum(np.convolve(row, [1.0, 2.0, 1.0])[: len(row)]) for row in x]), sequential(sos, x)[1]
+    return sequential(sos, x, zi=zi)

@@ -5,6 +5,9 @@ chunk in {4, 64, default} x n around the chunk length (1, 2, chunk - 1, chunk, c
 20 000, the six combinations of input and output type taking turns.  Every call runs twice into
 separate windows and must give identical bits; the double output must lie within allow * max|y| of the long-double loop (iir_ref.allowance:
 what the float64 algorithms themselves lose, times 4), the float output must be the double one rounded once.  Integer filters bit for bit.
+Every instance — n_sections 1 .. 16 — runs a bank of integer cascades bit for bit and a bank of three Butterworth band-passes against
+long double; every edge of the chunk grid (partial tiles, the carry's look-ahead, workgroups with one live chunk, chunks of 4096 and
+65 536 samples, 64 filters with their own zi and zf) runs on integers, bit for bit.
 Every case ends with Guard.check: red zones intact, every output element written."""
 import numpy as np
 import pytest
@@ -69,16 +72,25 @@ def run_twice(gpu, sos, x, inp="f64", outp="f64", chunk=0, zi=None, want_zf=Fals
 
 def judge(gpu, got, names, sig, n, chunk, inp, outp, sos, x):
     """The outputs of one call against the long-double reference and against each other."""
+    refs = [q.longdouble(name, s)[:n] for name, s in zip(names, sig)]
+    allows = [q.allowance(name, chunk, s, n) for name, s in zip(names, sig)]
+    return judge_bank(gpu, got, names, refs, allows, n, chunk, inp, outp, sos, x)
+
+
+def judge_bank(gpu, got, names, refs, allows, n, chunk, inp, outp, sos, x):
+    """`judge` for any bank: refs[f] the long-double output of filter f, allows[f] its allowance.  -> the worst error / bound."""
     y64 = got.get("y64")
     if y64 is None:  # the double this float must be the rounding of: the same call with the double output
         y64 = run_twice(gpu, sos, x, inp, "f64", chunk)["y64"]
-    for f, (name, s) in enumerate(zip(names, sig)):
-        ref = q.longdouble(name, s)[:n]
+    worst = 0.0
+    for f, (name, ref, allow) in enumerate(zip(names, refs, allows)):
         err = float(np.max(np.abs(y64[f].astype(np.longdouble) - ref)))
-        bound = q.allowance(name, chunk, s, n) * float(np.max(np.abs(ref)))
+        bound = allow * float(np.max(np.abs(ref)))
         assert err <= bound, f"{name} n={n} chunk={chunk} {inp}->{outp}: |y - long double| = {err:.3e} > {bound:.3e}"
+        worst = max(worst, err / bound)
     if "y32" in got:
         assert q.same_bits(got["y32"], y64.astype(np.float32)), f"n={n} {inp}->{outp}: the float output is not the rounded double"
+    return worst
 
 
 CASES = [(ns, mode, chunk) for ns in (1, 2, 12, 16) for mode in q.MODES for chunk in q.CHUNKS]
@@ -248,6 +260,60 @@ def test_sosfilt_is_capturable(gpu):
     for f, name in enumerate(names):
         ref = q.longdouble(name, f)[:n]
         assert float(np.max(np.abs(replays[0]["y64"][f].astype(np.longdouble) - ref))) <= q.allowance(name, chunk, f, n) * float(np.max(np.abs(ref)))
+
+
+# --- every instance (n_sections 1 .. 16 have their own register arrays, v_readlane chains and strides) and every edge of the chunk grid;
+# tests/test_iir_host.py proves through maua_sosfilt_plan that the lists reach them
+@pytest.mark.parametrize("ns", q.ALL_NS)
+def test_sosfilt_every_instance_on_integers(gpu, ns):
+    """A bank of two rotations of the integer cascade over their own signals, with and without zi: y, its float rounding and zf have
+    the bits of the sequential loop."""
+    sos, x, zi = q.instance_case(ns)
+    for z in (None, zi):
+        want, want_zf = q.sequential(sos, x, zi=z)
+        for i, chunk in enumerate(q.INSTANCE_CHUNKS):
+            got = run_twice(gpu, sos, x, ("f32", "f64")[(ns + i) % 2], "both", chunk, zi=z, want_zf=True)
+            assert q.same_bits(got["y64"], want), f"chunk {chunk}: y"
+            assert q.same_bits(got["y32"], want.astype(np.float32)), f"chunk {chunk}: the float y"
+            assert q.same_bits(got["zf"], want_zf), f"chunk {chunk}: zf"
+
+
+@pytest.mark.parametrize("ns", q.ALL_NS)
+def test_sosfilt_every_instance_against_long_double(gpu, ns):
+    """The three Butterworth band-passes of n_sections sections over one signal and over their own, judged as `judge` does."""
+    sos = q.bp_bank(ns)
+    names = [f"butter({ns}, {list(band)})" for band in q.BP_BANDS]
+    worst, turn = 0.0, ns
+    for mode in q.BP_MODES:
+        sig = q.bp_signals(mode)
+        x = q.signals()[0, :q.BP_N] if mode == "bank_shared" else q.signals()[list(sig), :q.BP_N]
+        refs = [q.bp_longdouble(ns, band, s) for band, s in enumerate(sig)]
+        for chunk in q.BP_CHUNKS:
+            inp, outp = q.IO[turn % len(q.IO)]
+            turn += 1
+            allows = [q.bp_allowance(ns, band, s, chunk) for band, s in enumerate(sig)]
+            got = run_twice(gpu, sos, x, inp, outp, chunk)
+            worst = max(worst, judge_bank(gpu, got, names, refs, allows, q.BP_N, chunk, inp, outp, sos, x))
+    print(f"n_sections {ns}: worst |y - long double| / allowance = {worst:.3f}")
+
+
+@pytest.mark.parametrize("name", list(q.GEOMETRY))
+def test_sosfilt_chunk_grid(gpu, name):
+    """One class of the chunk grid on integers, from a non-zero state where the class has one: both outputs and zf bit for bit; the
+    class's turn of single output type as well."""
+    case = q.GEOMETRY[name]
+    sos, x, zi = q.geometry_operands(name)
+    want, want_zf = q.geometry_reference(name)
+    inp, outp = q.IO[list(q.GEOMETRY).index(name) % len(q.IO)]
+    if name == "largest_chunk":  # (a serial walk of 65 536 samples per lane: one call pair)
+        inp, outp = "f32", "both"
+    for o in sorted({"both", outp}):
+        got = run_twice(gpu, sos, x, inp, o, case["chunk"], zi=zi, want_zf=True)
+        if "y64" in got:
+            assert q.same_bits(got["y64"], want), f"{inp}->{o}: y"
+        if "y32" in got:
+            assert q.same_bits(got["y32"], want.astype(np.float32)), f"{inp}->{o}: the float y"
+        assert q.same_bits(got["zf"], want_zf), f"{inp}->{o}: zf"
 
 
 # ------------------------------------------------------------------------------------------------ maua_env_follow_f32
