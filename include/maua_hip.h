@@ -679,6 +679,60 @@ int maua_hmm_posterior_f64(const float* obs /*[n_frames, n_states]*/, const doub
                            const double* init /*[n_states]*/, int n_frames, int n_states, double* gamma /*[n_frames, n_states]*/,
                            double* scale /*[n_frames]*/, void* stream);
 
+/* Bar-pointer model (audioreactive bar_viterbi / raw_bars / downbeats / metre / bar_phase / bar_beats; csrc/bar.hip; additive: the ABI
+ * version is unchanged).  The most probable path through the hidden Markov model over (tempo, beat in the bar, position in the beat) of
+ * Whiteley, Cemgil & Godsill (ISMIR 2006) on the state space of Krebs, Boeck & Widmer (ISMIR 2015), for n_models bar lengths in one
+ * call, decoded WITHOUT writing the states out.  tests/bar_ref.py restates it in numpy, bit for bit, and expands it to the dense model
+ * of maua_hmm_viterbi_f64 for comparison.
+ *
+ * Model.  K = n_tempi tempi, tempo k a beat of interval[k] envelope frames (strictly ascending integers in 1 .. MAUA_BAR_MAX_INTERVAL);
+ * B = beats_per_bar[m] beats in the bar of model m.  A state is (k, b, j), b in 0 .. B - 1, j in 0 .. interval[k] - 1.  Transitions:
+ * (k, b, j - 1) -> (k, b, j) with log-probability 0, and (k', (b - 1) mod B, interval[k'] - 1) -> (k, b, 0) with log_change[k'][k]
+ * (row = source, float64, -inf legal); nothing else.  Every state starts with log-probability 0.  Observations: logobs [T, 3] fp32,
+ * widened exactly, column 0 "no beat", 1 "beat", 2 "downbeat"; state (k, b, j) reads column c(b) = (b == 0 ? 2 : 1) when j < width[k]
+ * and column 0 otherwise, 1 <= width[k] <= interval[k].
+ *
+ * Every operation is a float64 addition, subtraction or compare, in this order (T = n_frames):
+ *   Prefix sums.  P_c[0] = 0, P_c[n + 1] = P_c[n] + logobs[n][c] for n = 0 .. T - 1 ascending, c = 0, 1, 2.
+ *   A beat (k, b) entered at frame e (any sign), seen up to frame `end` exclusive:  a0 = max(e, 0), a1 = min(max(e + width[k], 0), end),
+ *     seg(k, b, e, end) = (P_c(b)[a1] - P_c(b)[a0]) + (P_0[end] - P_0[a1]).
+ *   Entry values.  V[e][k][b] = 0 for e <= 0 (the path began inside that beat).  For t = 1 .. T - 1 ascending:
+ *     X[k'][b'] = V[t - interval[k']][k'][b'] + seg(k', b', t - interval[k'], t)      (leaving beat (k', b') behind frame t - 1)
+ *     V[t][k][b]: best = X[0][b'] + log_change[0][k] with index 0, b' = (b - 1) mod B; then k' = 1 .. K - 1 ascending, the candidate
+ *     X[k'][b'] + log_change[k'][k] replacing best (and the index) only when strictly greater: ties go to the lowest k', a NaN never
+ *     replaces (and a NaN at k' = 0 is never replaced).  The index is the back pointer of (t, k, b).
+ *   End.  Final value of state (k, b, j), with e = T - 1 - j:  V[e][k][b] + seg(k, b, e, T).  The final state is the first maximum in
+ *     ascending (k, b, j): from best = -inf at state (0, 0, 0), a value replaces only when strictly greater (so a NaN is never chosen,
+ *     and nothing but -inf and NaN ends in (0, 0, 0) with score -inf).  score[m] = that best.
+ *   Walk back.  The final state (k, b, j) at frame t = T - 1 entered its beat at e = t - j: path[f] = (k, b, f - e) for f = max(e, 0)
+ *     .. t.  While e > 0: k = the back pointer of (e, k, b), b = (b - 1) mod B, j = interval[k] - 1, t = e - 1, and again.
+ * Every element of score [n_models] and path [n_models, T, 3] is written.  Work per frame: K * K * B additions.
+ *
+ * ws: maua_bar_ws_bytes(n_frames, n_tempi, max_beats, n_models) bytes of device memory, 16-byte aligned (the prefix sums, a byte of
+ * back pointer per (t, k, b), the segment list of the walk back; per model, so that the workgroups share nothing); -1 for arguments
+ * the entry refuses.  max_beats is the largest beats_per_bar.  maua_bar_lds_bytes(n_tempi, max_beats, max_interval): the LDS of the
+ * launch — log_change at a row stride of K | 1 doubles, two buffers of K * max_beats exit values, a ring of max_interval entry values
+ * per lane — or 0 where the counts are outside their limits or the plan is more than the 160 KiB of one CU.
+ *
+ * interval, width and beats_per_bar are HOST arrays, read during the call (they travel as kernel arguments); everything else is device
+ * memory.  MAUA_EINVAL, without a launch and with the outputs untouched: a NULL pointer, n_frames outside 1 .. MAUA_BAR_MAX_FRAMES,
+ * n_tempi outside 1 .. MAUA_BAR_MAX_TEMPI, n_models outside 1 .. MAUA_BAR_MAX_MODELS, an interval outside 1 .. MAUA_BAR_MAX_INTERVAL or
+ * not above the one before, a width outside 1 .. interval, a beats_per_bar outside 1 .. MAUA_BAR_MAX_BEATS, n_tempi * max_beats >
+ * 1024, maua_bar_lds_bytes(n_tempi, max_beats, interval[n_tempi - 1]) == 0.  No atomics, no allocation, no synchronisation, no copy:
+ * capturable, and the result is a function of the arguments alone, bit for bit and run to run.  One workgroup per model, a lane per
+ * (k, b), one barrier per frame: latency-bound by construction, like maua_hmm_viterbi_f64. */
+#define MAUA_BAR_MAX_FRAMES (1 << 22)
+#define MAUA_BAR_MAX_TEMPI 128
+#define MAUA_BAR_MAX_BEATS 8          /* K * B <= 1024 lanes */
+#define MAUA_BAR_MAX_INTERVAL 1024
+#define MAUA_BAR_MAX_MODELS 8
+int64_t maua_bar_lds_bytes(int n_tempi, int max_beats, int max_interval);
+int64_t maua_bar_ws_bytes(int n_frames, int n_tempi, int max_beats, int n_models);
+int maua_bar_viterbi_f64(const float* logobs /*[n_frames, 3]*/, int n_frames, const int32_t* interval /*host [n_tempi]*/,
+                         const int32_t* width /*host [n_tempi]*/, const double* log_change /*[n_tempi, n_tempi]*/, int n_tempi,
+                         const int32_t* beats_per_bar /*host [n_models]*/, int n_models, void* ws, double* score /*[n_models]*/,
+                         int32_t* path /*[n_models, n_frames, 3]*/, void* stream);
+
 /* Spectrogram factorisation (audioreactive nmf / decompose / components; csrc/nmf.hip; additive: the ABI version is unchanged).
  * Non-negative matrix factorisation V [F, T] ~ W [F, K] . H [K, T] under the generalised Kullback-Leibler divergence by multiplicative
  * updates (Lee & Seung 2000), in place, all fp32 and contiguous: V with frames contiguous, W contiguous in k, H contiguous in t.

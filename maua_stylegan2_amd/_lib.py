@@ -150,6 +150,10 @@ _SIGNATURES = {
     "maua_pulse_synth_f32": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
     "maua_hmm_viterbi_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P]),
     "maua_hmm_posterior_f64": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
+    "maua_bar_lds_bytes": (c_int64, [c_int] * 3),
+    "maua_bar_ws_bytes": (c_int64, [c_int] * 4),
+    "maua_bar_viterbi_f64": (c_int, [_P, c_int, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), _P, c_int, POINTER(ctypes.c_int32), c_int,
+                                     _P, _P, _P, _P]),
     "maua_sosfilt_default_chunk": (c_int, [c_int]),
     "maua_sosfilt_ws_doubles": (c_int64, [c_int] * 4),
     "maua_sosfilt_plan": (c_int, [c_int] * 4 + [POINTER(ctypes.c_int32)]),

@@ -1,6 +1,7 @@
 """Drop-in for the reference's ``audioreactive`` package: everything star-exported as ``ar.*``
 (/root/reference/audioreactive/__init__.py:1-5)."""
 from . import signal as _signal_module
+from .bars import *  # noqa: F401,F403  (bar_model, bar_viterbi, raw_bars, downbeats, metre, bar_phase, bar_beats: the bar-pointer model, no counterpart in the reference)
 from .beat import *  # noqa: F401,F403  (raw_plp, tempogram, pulse, tempo, beats, beat_phase: the predominant local pulse, no counterpart in the reference)
 from .bend import *  # noqa: F401,F403
 from .decompose import *  # noqa: F401,F403  (nmf, decompose, components: spectrogram factorisation, no counterpart in the reference)

@@ -168,11 +168,23 @@ def pulse(audio, sr, n_frames, smooth=0, power=1, device=None):
     return curve.to(device if device is not None else "cpu")
 
 
-def tempo(audio, sr, n_frames, smooth=0, device=None):
+def tempo(audio, sr, n_frames, smooth=0, device=None, method="plp"):
     """The local tempo in BPM per video frame, a CPU tensor unless ``device=`` is given: frames without a tempo hold the last one
     (leading ones take the first) -> 5-tap median -> linear interpolation -> Gaussian smoothing when ``smooth`` > 0.  Zeros, with a
-    warning, when no frame has a tempo (silence)."""
-    _, bpm, _ = raw_plp(audio, sr)
+    warning, when no frame has a tempo (silence).  ``method="bar"``: the tempo path of the bar-pointer model instead of the tempogram's
+    per-frame maximum, measured bar by bar (``bars.Bars.bar_tempo``: the model's beats are whole frames long, a grid 1 / 21 wide at
+    120 BPM, which a bar of them averages out); a clip without one whole bar falls back on the per-beat steps."""
+    if method == "bar":
+        from . import bars
+
+        res = bars.raw_bars(audio, sr)
+        bpm = res.bar_tempo()
+        if res.metre > 0 and bool(th.isnan(bpm).all()):
+            bpm = res.tempo
+    elif method == "plp":
+        _, bpm, _ = raw_plp(audio, sr)
+    else:
+        raise ValueError(f"tempo: unknown method {method!r}: use 'plp' or 'bar'")
     held = _sig.hold_fill(bpm, ~th.isnan(bpm))
     if held is None:
         warnings.warn("tempo: no frame of the clip has a pulse; returning zeros", stacklevel=2)
@@ -201,7 +213,8 @@ def pick_beats(curve, fr, threshold=0.1):
 def beats(audio, sr, method="plp", threshold=0.1):
     """Beat times in seconds, a float64 numpy array.  ``method="plp"``: the maxima above ``threshold`` of the pulse curve of
     :func:`raw_plp`, refined between frames — follows tempo changes.  ``method="dp"``: the frames of ``segment.beat_track`` (one global
-    tempo, dynamic programming; what ``laplacian_segmentation`` uses) times 512 / sr."""
+    tempo, dynamic programming; what ``laplacian_segmentation`` uses) times 512 / sr.  ``method="bar"``: the beats of the bar-pointer
+    model (``bars.raw_bars``), the ones its downbeats are counted on."""
     if method == "plp":
         s = _plp_stages(audio, sr)
         return pick_beats(s["pulse"], s["fr"], threshold).cpu().numpy()
@@ -210,7 +223,11 @@ def beats(audio, sr, method="plp", threshold=0.1):
         env, _ = _seg.onset_envelope(audio, sr)
         _, frames = _seg.beat_track(env, sr)
         return np.asarray(frames, dtype=np.float64) * _seg.HOP / float(sr)
-    raise ValueError(f"beats: unknown method {method!r}: use 'plp' or 'dp'")
+    if method == "bar":
+        from . import bars
+
+        return bars.raw_bars(audio, sr).beat_times()
+    raise ValueError(f"beats: unknown method {method!r}: use 'plp', 'dp' or 'bar'")
 
 
 def beat_phase_from_times(times, duration, n_frames, division=1):
