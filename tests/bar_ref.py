@@ -160,7 +160,7 @@ DENSE_CASES = [([2, 3], 2, 1), ([2, 3], 2, 2), ([2, 3], 2, 40), ([3, 4, 5, 7], 3
 
 def random_operands(intervals, T, seed=0, widths="random", matrix="dirichlet", obs="normal"):
     """(logobs fp32 [T, 3], interval, width, log_change) of a case: random widths in 1 .. interval, Dirichlet rows with an occasional
-    -inf, observations 3 N(0, 1) rounded to fp32."""
+    -inf, observations 3 N(0, 1) rounded to fp32; ``matrix`` / ``obs`` name the other kinds below."""
     rng = np.random.default_rng(seed)
     I = np.asarray(intervals, np.int32)
     K = len(I)
@@ -186,6 +186,8 @@ def random_operands(intervals, T, seed=0, widths="random", matrix="dirichlet", o
         lo[T // 2, 1] = np.nan
     if obs == "inf":
         lo[T // 3, 2] = np.inf
+    if matrix == "integer":   # small integers: with obs="integer" every sum is exact, whatever its order (drawn last: the other kinds keep their draws)
+        lc = rng.integers(-3, 1, (K, K)).astype(np.float64)
     return lo, I, W, lc
 
 

@@ -40,12 +40,43 @@ def viterbi(logobs, log_trans, log_init, variant=None):
         for k in range(1, S):
             if (delta[k] >= top) if variant == "ties_high" else (delta[k] > top):
                 s, top = k, delta[k]
+    if variant in CHUNK_VARIANTS:
+        return delta, back, walk_back(back, s, variant)
     states = np.zeros(T, np.int32)
     states[T - 1] = s
     for t in range(T - 1, 0, -1):
         s = int(back[t - 1 if variant == "shifted_backptr" else t][s])
         states[t - 1] = s
     return delta, back, states
+
+
+TRACE_ROWS = 1024   # HMM_TRACE_ROWS of csrc/hmm.hip: the frames of back pointers per chunk of the walk back
+CHUNK_VARIANTS = ("chunk_repeat", "chunk_drop")  # wrong walks back that only more than one chunk shows (not in VARIANTS: T <= 6 there)
+
+
+def chunks(T, rows=TRACE_ROWS, step=None):
+    """The (lo, n) of every chunk of the kernel's walk back over T frames, last chunk first: hi = T - 1, lo = max(hi - (rows - 1), 0),
+    n = hi - lo + 1, then hi -= rows (``step``: what a wrong kernel subtracts instead)."""
+    out, hi = [], T - 1
+    while hi >= 0:
+        lo = max(hi - (rows - 1), 0)
+        out.append((lo, hi - lo + 1))
+        hi -= rows if step is None else step
+    return out
+
+
+def walk_back(back, s, variant=None):
+    """states [T] int32 by the kernel's chunked walk from the final state ``s``.  None: the definition, whatever the chunking.
+    chunk_repeat: the next chunk starts ON the row the last one ended with (hi -= rows - 1), which is then followed twice;
+    chunk_drop: it starts one row too low (hi -= rows + 1), and the row between is neither followed nor written (it reads 0)."""
+    T = back.shape[0]
+    states = np.zeros(T, np.int32)
+    step = {None: None, "chunk_repeat": TRACE_ROWS - 1, "chunk_drop": TRACE_ROWS + 1}[variant]
+    for lo, n in chunks(T, step=step):
+        for r in range(n - 1, -1, -1):
+            states[lo + r] = s
+            s = int(back[lo + r][s])   # (row 0 of backptr holds each state's own index)
+    return states
 
 
 def _chain(values):
@@ -125,6 +156,20 @@ def cases(kinds):
 
 def case_id(case):
     return f"{case['kind']}-S{case['S']}-T{case['T']}"
+
+
+# (S, T) pairs, not a cross, on the edges the kernels compute: T = 1024 is one exactly full chunk of the walk back, 1025 leaves a last
+# chunk of one row, 2048 is two full chunks, 2049 two and a row, 1023 and 2047 one row short of each; S = 63 / 65 put one dead / one
+# live lane in the second wave, 127 is the largest S whose S | 1 stride equals S, 3 / 4 / 5 lie either side of the unroll-by-4 remainder.
+# Both parities of T: the posterior's backward sweep alternates two buffers by frame parity.
+EDGE_CASES = ((3, 1023), (4, 1024), (5, 1025), (63, 2047), (64, 1023), (65, 2048), (127, 2049), (128, 1024), (128, 1025), (128, 2048))
+EDGE_VITERBI_KINDS = ("integer", "random")
+EDGE_POSTERIOR_KINDS = ("integer", "zeros")
+SWEEP_STATES = (1, 2, 3, 4, 5, 63, 64, 65, 127, 128)   # the wave and unroll edges the random-shape tests mix into their draws
+
+
+def edge_cases(kinds):
+    return [dict(S=S, T=T, kind=kind, seed=5000 + 10 * n + k) for k, kind in enumerate(kinds) for n, (S, T) in enumerate(EDGE_CASES)]
 
 
 def _stochastic(rng, S):

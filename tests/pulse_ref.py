@@ -401,7 +401,8 @@ def _case(n, win, n_tempi, kind, seed, **kw):
 
 
 def a_cases():
-    """n: 1, W - 1, W, W + 1, one tile, two tiles + 5, 20 000; W: 2, 3, 33, 384, 2048; B: 1, 2, 63, 64, 65, 271, 1024; random, click and
+    """n: 1, W - 1, W, W + 1, one tile, two tiles + 5, 20 000; W: 2, 3, 33, 384, 2048; B: 1, 2, 63, 64, 65, 271, 1024 and, round the
+    48 tempi of one round of the waves, 3, 4, 47, 48, 49, 97; random, click and
     zero envelopes, with and without prior and tgram.  (A frame whose window holds one non-zero sample scores the same on every tempo up
     to rounding: the cases with one-sample windows have one tempo, or few enough such frames for the cap.)"""
     return [
@@ -429,6 +430,13 @@ def a_cases():
         _case(2049, 2048, 2, "random", 19),
         _case(2 * TILE + 5, 384, 1024, "random", 20, prior=True),
         _case(TILE, 384, 1024, "click", 21, tgram=True),
+        # the kernel hands three tempi at a time to sixteen waves, 48 a round: a part round, one short of a round, a round, one over, two and one
+        _case(65, 33, 3, "random", 26, prior=True),
+        _case(65, 33, 4, "random", 27, tgram=True),
+        _case(65, 33, 47, "random", 28, prior=True, tgram=True),
+        _case(65, 33, 48, "random", 29, tgram=True),
+        _case(65, 33, 49, "random", 30, prior=True),
+        _case(65, 33, 97, "random", 31, prior=True, tgram=True),
     ]
 
 

@@ -324,12 +324,15 @@ def viterbi_loop(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_swi
     return delta, back, states
 
 
-def viterbi(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_switch):
+def viterbi(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_switch, reach=None):
     """The same decoder vectorised over the target bins (a frame at a time, both voicings at once).  np.argmax returns the first
-    maximum, which is the scan's rule while no NaN is involved; a window of nothing but -inf keeps its first element.  Frames that meet a
-    NaN go through the scalar rule."""
+    maximum, which is the scan's rule while no NaN is involved; a window of nothing but -inf keeps its first element.  A NaN among the
+    observations follows the scalar rule in vector form — a NaN is never strictly greater and nothing is strictly greater than one, so a
+    window whose first candidate is a NaN keeps it and a NaN further on is passed over; a NaN in a table goes through the scalar loop
+    (tests/test_pyin_host.py and tests/test_decoders_host.py hold the two together bit for bit).  ``reach`` (None: the definition) is the deliberate defect of tests/test_decoders_host.py: the
+    kernel's scan clamp — it walks the offsets -reach .. reach, the definition's being min(W, P - 1) — set to another value (no NaN)."""
     lov32, lou32 = np.asarray(lov, np.float32), np.asarray(lou, np.float32)
-    if np.isnan(lov32).any() or np.isnan(lou32).any() or np.isnan(log_tri).any() or np.isnan(log_norm).any():
+    if np.isnan(log_tri).any() or np.isnan(log_norm).any():
         return viterbi_loop(lov32, lou32, width, log_tri, log_norm, log_init, log_stay, log_switch)
     lov, lou = lov32.astype(np.float64), lou32.astype(np.float64)
     T, P = lov.shape
@@ -345,6 +348,8 @@ def viterbi(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_switch):
     i0 = np.maximum(0, j - W)
     valid = (j[:, None] - W + np.arange(2 * W + 1)[None, :] >= 0) & (j[:, None] - W + np.arange(2 * W + 1)[None, :] <= P - 1)
     masked = not np.isfinite(log_tri).all()  # (-inf + a finite weight stays -inf outside the window; any other table entry must not leak in)
+    if reach is not None:
+        valid, masked = valid & (np.abs(np.arange(2 * W + 1) - W) <= reach)[None, :], True
     buf = np.empty((2, P, 2 * W + 1))
     for t in range(1, T):
         pad[0, W:W + P] = delta[:P] - log_norm
@@ -352,10 +357,16 @@ def viterbi(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_switch):
         np.add(win, tri, out=buf)
         if masked:
             buf[:, ~valid] = -np.inf
+        stuck = None
+        if np.isnan(pad).any():  # the window's first candidate (element i0 - j + W) decides; every other NaN loses like -inf
+            stuck = np.isnan(np.take_along_axis(buf, np.broadcast_to((i0 - j + W)[None, :, None], (2, P, 1)), axis=2)[:, :, 0])
+            buf[np.isnan(buf)] = -np.inf
         k = buf.argmax(axis=2)
         best = np.take_along_axis(buf, k[:, :, None], axis=2)[:, :, 0]
         idx = j[None, :] - W + k
         idx = np.where(best == -np.inf, i0[None, :], idx)
+        if stuck is not None:
+            best, idx = np.where(stuck, np.nan, best), np.where(stuck, i0[None, :], idx)
         bv, bu, iv, iu = best[0], best[1], idx[0], idx[1]
         a, b = bv + log_stay, bu + log_switch
         sw = b > a
@@ -365,7 +376,7 @@ def viterbi(lov, lou, width, log_tri, log_norm, log_init, log_stay, log_switch):
         sw = b > a
         back[t, P:] = np.where(sw, P + iu, iv)
         delta = np.concatenate([voiced, lou[t] + np.where(sw, b, a)])
-    s = int(np.argmax(delta)) if not (delta == -np.inf).all() else 0
+    s = 0 if np.isnan(delta[0]) or (delta == -np.inf).all() else int(np.argmax(np.where(np.isnan(delta), -np.inf, delta)))
     states = np.zeros(T, np.int32)
     states[T - 1] = s
     for t in range(T - 1, 0, -1):
@@ -424,6 +435,9 @@ def make_logobs(case):
     T, P, kind = case["n_frames"], case["n_bins"], case["kind"]
     if kind == "integer":
         lov, lou = -rng.integers(0, 4, (T, P)).astype(np.float32), -rng.integers(0, 4, T).astype(np.float32)
+    elif kind == "corners":  # all voiced mass in bin 0 on the even frames and in bin P - 1 on the odd ones: where W >= P - 1 the best
+        lov, lou = np.full((T, P), -40.0, np.float32), np.full(T, -30.0, np.float32)  # path takes the widest step there is, every frame
+        lov[np.arange(T), np.where(np.arange(T) % 2 == 0, 0, P - 1)] = -rng.integers(0, 2, T).astype(np.float32)
     else:
         lov, lou = np.log(rng.random((T, P)) + 1e-6).astype(np.float32), np.log(rng.random(T) * 0.5 + 1e-6).astype(np.float32)
     if kind == "inf_rows":  # bins that never carry mass, frames without any voiced mass, frames that cannot be unvoiced
@@ -446,6 +460,47 @@ def b_constants(case):
 def b_reference(case):
     lov, lou = make_logobs(case)
     return viterbi(lov, lou, case["width"], *b_constants(case))
+
+
+# (P, W) pairs, not a cross, on the clamp reach = min(W, P - 1) of the kernel's scan: W = P - 2, P - 1 and >= P with one wave (P = 63,
+# 64), across the 64 / 65 boundary (P = 65) and with two waves and the first lane of a third (P = 127, 128, 129).
+EDGE_CASES = ((63, 62), (64, 63), (64, 64), (65, 63), (65, 64), (65, 65), (127, 126), (127, 128), (128, 127), (128, 128), (129, 128),
+              (64, 62), (128, 126))   # (the last two: W = P - 2 with one full wave and with two, which the pairs before them lack)
+EDGE_FRAMES = (2, 3, 257)
+EDGE_KINDS = ("integer", "random", "corners")   # (with the first two alone a scan one offset short goes unnoticed: the far source never wins)
+
+
+def edge_cases():
+    """Every pair with every kind; T rotates, so that every pair meets all three lengths."""
+    return [{"n_bins": P, "width": W, "n_frames": EDGE_FRAMES[(n + k) % len(EDGE_FRAMES)], "kind": kind, "seed": 9500 + 3 * n + k}
+            for n, (P, W) in enumerate(EDGE_CASES) for k, kind in enumerate(EDGE_KINDS)]
+
+
+def integer_constants(n_bins, width):
+    """(log_tri, log_norm, log_init, log_stay, log_switch), all integer-valued: with the integer kind of make_logobs every sum of the
+    recursion is exact, so ties are real ties and two orders of the same additions give the same bits."""
+    d = np.arange(-width, width + 1)
+    return -np.abs(d).astype(np.float64), np.arange(n_bins, dtype=np.float64) % 2, -1.0, 0.0, -1.0
+
+
+def expand(n_bins, width, log_tri, log_norm, log_init, log_stay, log_switch):
+    """(log_trans [2 P, 2 P], log_init [2 P]) of the model with every state written out, voiced 0 .. P - 1 then unvoiced P .. 2 P - 1:
+    the operands of hmm_ref.viterbi, whose observations are [lov | lou repeated P times].  Entry (i, j) is (-log_norm[i % P] +
+    log_tri[(j % P) - (i % P) + W]) + (log_stay within a voicing, log_switch across), -inf where the bins lie further than W apart."""
+    P, W = n_bins, width
+    tri, norm = np.asarray(log_tri, np.float64), np.asarray(log_norm, np.float64)
+    lt = np.full((2 * P, 2 * P), -np.inf)
+    for i in range(2 * P):
+        for j in range(2 * P):
+            d = j % P - i % P
+            if abs(d) <= W:
+                lt[i, j] = (-norm[i % P] + tri[d + W]) + (log_stay if (i < P) == (j < P) else log_switch)
+    return lt, np.full(2 * P, np.float64(log_init))
+
+
+def dense_observations(lov, lou):
+    lov, lou = np.asarray(lov, np.float32), np.asarray(lou, np.float32)
+    return np.concatenate([lov, np.repeat(lou[:, None], lov.shape[1], axis=1)], axis=1)
 
 
 # ------------------------------------------------------------------------------------------------ the whole tracker on the host

@@ -1,7 +1,8 @@
 """GPU: the two hidden-Markov-model entries (csrc/hmm.hip) called through the C ABI between red zones, over the case lists of
 tests/hmm_ref.py: S in {1, 2, 25, 64, 97, 128} x T in {1, 2, 3, 257, 2000} x every operand kind — one lane and one frame, the last
 partial wave (97), the padded LDS stride and the byte back pointer at their limits (128), more frames than one chunk of the walk back
-(2000).  Every output of both entries bit for bit against the float64 restatement, two runs identical.  The one exception is written
+(2000) — and over hmm_ref.EDGE_CASES, the (S, T) pairs on the edges of that chunking (T = 1023 .. 2049) and of the waves, the stride and
+the unroll (S = 3 .. 128).  Every output of both entries bit for bit against the float64 restatement, two runs identical.  The one exception is written
 down in hmm_ref.same_bits_or_nan: where the posterior's definition yields a NaN (a NaN operand, an all-zero frame) the positions of
 the NaNs are compared, not their payload.  Every case ends with Guard.check: red zones intact, every output element written."""
 import numpy as np
@@ -108,6 +109,19 @@ def test_posterior_bit_for_bit(gpu, case):
     if not yields_nan:
         assert np.isfinite(ref[0]).all() and np.isfinite(ref[1]).all() and np.abs(ref[0].sum(1) - 1).max() < 1e-12
     assert_posterior(a, ref, q.case_id(case), exact=not yields_nan)
+
+
+@pytest.mark.parametrize("case", q.edge_cases(q.EDGE_VITERBI_KINDS), ids=q.case_id)
+def test_viterbi_chunk_and_wave_edges(gpu, case):
+    """hmm_ref.EDGE_CASES: the walk back with an exactly full chunk, a last chunk of one row, two full chunks and two and a row, at
+    the S either side of the second wave, of the S | 1 stride and of the unroll remainder."""
+    test_viterbi_bit_for_bit(gpu, case)
+
+
+@pytest.mark.parametrize("case", q.edge_cases(q.EDGE_POSTERIOR_KINDS), ids=q.case_id)
+def test_posterior_parity_and_wave_edges(gpu, case):
+    """The same (S, T) pairs through the posterior: both parities of T for the two buffers of its backward sweep."""
+    test_posterior_bit_for_bit(gpu, case)
 
 
 def test_viterbi_twenty_thousand_frames(gpu):

@@ -4,13 +4,13 @@ broadly than the hand-picked parametrisations; example counts are small so that 
 import numpy as np
 import pytest
 import torch
-from hypothesis import HealthCheck, given, settings, strategies as st
+from hypothesis import given, settings, strategies as st
 
+from decoder_cases import COMMON  # (the settings live beside the strategies that host tests import too: no torch, no oracle there)
 from oracle import ops_oracle, stylegan2_oracle as so
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-COMMON = dict(deadline=None, derandomize=True, suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
 
 
 @settings(max_examples=40, **COMMON)

@@ -171,6 +171,9 @@ def test_case_lists_cover_the_shapes_and_keep_the_exempt_cap():
     for w in (2, 3, 33, 384, 2048):
         assert {w - 1, w, w + 1} <= {c["n"] for c in cases if c["win"] == w}, w
     assert {1, 2, 63, 64, 65, 271, 1024} <= {c["n_tempi"] for c in cases}
+    rounds = [c for c in cases if c["n_tempi"] in (3, 4, 47, 48, 49, 97)]   # three tempi per wave, sixteen waves: 48 a round
+    assert {c["n_tempi"] for c in rounds} == {3, 4, 47, 48, 49, 97} and all((c["n"], c["win"]) == (65, 33) for c in rounds)
+    assert sum(bool(c.get("prior")) for c in rounds) >= 2 and sum(bool(c.get("tgram")) for c in rounds) >= 2
     assert {"random", "click", "zero"} <= {c["kind"] for c in cases}
     for flag in ("prior", "tgram"):
         assert any(c.get(flag) for c in cases) and any(not c.get(flag) for c in cases)

@@ -3,7 +3,8 @@
 maua_pyin_candidates_f32 on host-built d' rows against the float32 restatement: obs and voiced_prob within n 2^-24 1.01 (n = the
 summands of the element), obs bit for bit where an element has at most one summand, period within 4 x the float32-against-float64
 figure, bins exact except on the frames (decided on the CPU, at most 2 % of a case) where a refined period lies within twice that
-tolerance of a bin edge.  maua_pyin_viterbi_f64 against the float64 restatement, bit for bit in delta_last, backptr and states.  Every
+tolerance of a bin edge.  maua_pyin_viterbi_f64 against the float64 restatement, bit for bit in delta_last, backptr and states, over
+b_cases() and over pyin_ref.EDGE_CASES, the (P, W) pairs either side of the scan's clamp at one wave, 64 / 65 and two waves.  Every
 case ends with Guard.check: red zones intact, every output element written."""
 import numpy as np
 import pytest
@@ -140,6 +141,26 @@ def test_viterbi_bit_for_bit(gpu, case):
         assert np.array_equal(got["backptr"][:at + 1], clean["backptr"][:at + 1])  # (row `at` is decided by the frames before it)
     if case["kind"] == "inf_frame" and case["n_frames"] > 1:
         assert np.isneginf(got["delta_last"]).all() and got["states"][-1] == 0
+
+
+@pytest.mark.parametrize("case", q.edge_cases(), ids=q.b_case_id)
+def test_viterbi_reach_clamp_edges(gpu, case):
+    """pyin_ref.EDGE_CASES: W = P - 2, P - 1 and >= P (either side of the scan's clamp reach = min(W, P - 1)) with one wave, across the
+    64 / 65 boundary and with two waves; two runs identical."""
+    ref = q.b_reference(case)
+    with torch.cuda.device(gpu):
+        g = Guard(gpu)
+        ops, _ = b_operands(g, case)
+        runs = []
+        for tag in ("a", "b"):
+            out = b_windows(g, case, tag)
+            assert b_call(*ops, case, out) == 0
+            runs.append(out)
+        g.check(written=[f"{k}.{tag}" for tag in ("a", "b") for k in B_OUT])
+        a, b = (b_host(out, case) for out in runs)
+    for key in B_OUT:
+        assert same_bits(a[key], b[key]), f"{key}: two runs differ"
+    assert_b_equal(a, ref, q.b_case_id(case))
 
 
 def test_viterbi_twenty_thousand_frames(gpu):
