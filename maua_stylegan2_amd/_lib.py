@@ -7,6 +7,7 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -223,6 +224,49 @@ def check(rc, what):
 
 def stream_ptr(device=None):
     return torch.cuda.current_stream(device).cuda_stream
+
+
+_I32P = POINTER(ctypes.c_int32)
+
+
+def call(name, *args, device=None):
+    """Launch the native entry ``name`` on the current stream of its tensors' device: the one way the audio modules reach the library.
+
+    ``args`` are the entry's arguments WITHOUT the trailing ``void* stream``; each is converted by its slot in ``_SIGNATURES[name]``:
+    a ``void*`` slot takes a contiguous CUDA tensor (passed as ``data_ptr()``), None (NULL) or an int (an address the caller computed,
+    passed through unchecked); an ``int32*`` slot takes a contiguous int32 numpy array (a host table); every other slot passes through.
+    All tensors must be on one device, which is the launch device; ``device=`` names it when no argument is a tensor and must agree
+    with the tensors otherwise.  Every refusal names the entry and the argument position and is raised before any HIP call."""
+    slots = _SIGNATURES[name][1]
+    if not slots or slots[-1] is not c_void_p:
+        raise TypeError(f"{name} takes no stream: it is a host query, call it on load() directly")
+    if len(args) + 1 != len(slots):
+        raise TypeError(f"{name} takes {len(slots) - 1} arguments before the stream (got {len(args)})")
+    dev = None if device is None else torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    conv = []
+    for i, (a, slot) in enumerate(zip(args, slots)):
+        if slot is c_void_p and isinstance(a, torch.Tensor):
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: argument {i} must be contiguous (shape {tuple(a.shape)}, strides {a.stride()})")
+            if not a.is_cuda:
+                raise RuntimeError(f"{name}: argument {i} must be a CUDA (HIP) tensor")
+            if dev is None:
+                dev = a.device
+            elif a.device != dev:
+                raise ValueError(f"{name}: argument {i} is on {a.device}, the launch goes to {dev}")
+            a = a.data_ptr()
+        elif slot is c_void_p and a is not None and not isinstance(a, int):
+            raise TypeError(f"{name}: argument {i} must be a tensor, None or an address (got {type(a).__name__})")
+        elif slot is _I32P:
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+                raise TypeError(f"{name}: argument {i} must be a contiguous int32 numpy array")
+            a = a.ctypes.data_as(_I32P)
+        conv.append(a)
+    if dev is None:
+        raise ValueError(f"{name}: no tensor argument names the launch device: pass device=")
+    fn = getattr(load(), name)
+    with torch.cuda.device(dev):
+        check(fn(*conv, stream_ptr(dev)), name)
 
 
 def ptr(t):

@@ -112,14 +112,10 @@ def bar_viterbi(logobs, interval, width, log_change, beats_per_bar=(3, 4)):
     dev = logobs.device
     K, n_models = len(interval), len(beats)
     lc = _sig._const_dev(np.asarray(log_change.cpu() if isinstance(log_change, th.Tensor) else log_change, dtype=np.float64))
-    lib = _lib.load()
-    ws = th.empty(lib.maua_bar_ws_bytes(n_frames, K, int(beats.max()), n_models), dtype=th.uint8, device=dev)
+    ws = th.empty(_lib.load().maua_bar_ws_bytes(n_frames, K, int(beats.max()), n_models), dtype=th.uint8, device=dev)
     score = th.empty(n_models, dtype=th.float64, device=dev)
     path = th.empty((n_models, n_frames, 3), dtype=th.int32, device=dev)
-    as_c = lambda a: a.ctypes.data_as(_lib.POINTER(_lib.ctypes.c_int32))  # noqa: E731
-    with th.cuda.device(dev):
-        _lib.check(lib.maua_bar_viterbi_f64(logobs.data_ptr(), n_frames, as_c(interval), as_c(width), lc.data_ptr(), K, as_c(beats), n_models,
-                                            ws.data_ptr(), score.data_ptr(), path.data_ptr(), _lib.stream_ptr(dev)), "maua_bar_viterbi_f64")
+    _lib.call("maua_bar_viterbi_f64", logobs, n_frames, interval, width, lc, K, beats, n_models, ws, score, path)
     return score, path
 
 

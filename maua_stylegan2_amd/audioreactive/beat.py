@@ -75,10 +75,7 @@ def tempogram_peak(env, table, prior=None, want_tgram=False):
         prior = prior.float().contiguous()
         if prior.numel() != n_tempi:
             raise ValueError(f"prior: {prior.numel()} values for {n_tempi} tempi")
-    with th.cuda.device(env.device):
-        _lib.check(_lib.load().maua_tempogram_peak_f32(env.data_ptr(), n, table.data_ptr(), win, n_tempi, _lib.ptr(prior), bins.data_ptr(),
-                                                       phase.data_ptr(), power.data_ptr(), _lib.ptr(tgram), _lib.stream_ptr(env.device)),
-                   "maua_tempogram_peak_f32")
+    _lib.call("maua_tempogram_peak_f32", env, n, table, win, n_tempi, prior, bins, phase, power, tgram)
     return bins, phase, power, tgram
 
 
@@ -88,9 +85,7 @@ def pulse_synth(bins, phase, window, omega):
     window, omega = window.float().contiguous(), omega.float().contiguous()
     n = bins.numel()
     out = th.empty(n, dtype=th.float32, device=bins.device)
-    with th.cuda.device(bins.device):
-        _lib.check(_lib.load().maua_pulse_synth_f32(bins.data_ptr(), phase.data_ptr(), n, window.data_ptr(), window.numel(), omega.data_ptr(),
-                                                    omega.numel(), out.data_ptr(), _lib.stream_ptr(bins.device)), "maua_pulse_synth_f32")
+    _lib.call("maua_pulse_synth_f32", bins, phase, n, window, window.numel(), omega, omega.numel(), out)
     return out
 
 

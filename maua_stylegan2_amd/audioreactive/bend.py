@@ -124,10 +124,7 @@ class AffineReflectWarp(th.nn.Module):
 
     def _launch(self, x, y, m, nz, xmap, ymap, src):
         b, c, h, w = x.shape
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().maua_affine_reflect_warp_mapped_f32(
-                x.data_ptr(), m.data_ptr(), y.data_ptr(), b, c, h, w, self.pads[0], self.pads[1], self.pads[2], self.pads[3],
-                _lib.ptr(nz), _lib.ptr(xmap), _lib.ptr(ymap), src, _lib.stream_ptr(x.device)), "maua_affine_reflect_warp_mapped_f32")
+        _lib.call("maua_affine_reflect_warp_mapped_f32", x, m, y, b, c, h, w, *self.pads, nz, xmap, ymap, src)
         return y
 
     def forward(self, x):
@@ -223,10 +220,7 @@ class PointBend(_ChannelBend):
 
     def _launch(self, x, y, params, mask, src):
         b, c = x.shape[:2]
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().maua_bend_point_f32(x.data_ptr(), y.data_ptr(), b, c, x[0, 0].numel(), self.op, _lib.ptr(params),
-                                                       self.sequence_rows, _lib.ptr(mask), src, _lib.stream_ptr(x.device)),
-                       "maua_bend_point_f32")
+        _lib.call("maua_bend_point_f32", x, y, b, c, x[0, 0].numel(), self.op, params, self.sequence_rows, mask, src)
         return y
 
 
@@ -250,10 +244,7 @@ class MorphBend(_ChannelBend):
 
     def _launch(self, x, y, radii, mask, src):
         b, c, h, w = x.shape
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().maua_bend_morph_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, self.op, radii.data_ptr(),
-                                                       self.sequence_rows, _lib.ptr(mask), src, _lib.stream_ptr(x.device)),
-                       "maua_bend_morph_f32")
+        _lib.call("maua_bend_morph_f32", x, y, b, c, h, w, self.op, radii, self.sequence_rows, mask, src)
         return y
 
 
@@ -314,10 +305,7 @@ class Pad(th.nn.Module):
         if b > 64 or c > 65535:
             raise RuntimeError(f"bends serve batches of up to 64 frames and maps of up to 65535 channels (got {b} x {c})")
         nz = self._noise_plane(x, y.shape)
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().maua_bend_pad_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, *self.padding, _PAD_MODES[self.mode],
-                                                     self.value, _lib.ptr(nz), 0 if nz is None else nz.shape[0],
-                                                     _lib.stream_ptr(x.device)), "maua_bend_pad_f32")
+        _lib.call("maua_bend_pad_f32", x, y, b, c, h, w, *self.padding, _PAD_MODES[self.mode], self.value, nz, 0 if nz is None else nz.shape[0])
         return y
 
     def forward(self, x):
@@ -490,10 +478,7 @@ class RemapBend(_ChannelBend):
                 self._field_dev[key] = self.field.to(x.device).contiguous()
             field = self._field_dev[key]
         frames, fh, fw = (0, 0, 0) if field is None else (field.shape[0], field.shape[2], field.shape[3])
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().maua_bend_remap_f32(x.data_ptr(), y.data_ptr(), b, c, h, w, self.op, self.border, table.data_ptr(),
-                                                       self.sequence_rows, _lib.ptr(field), frames, fh, fw, _lib.ptr(mask), src,
-                                                       _lib.stream_ptr(x.device)), "maua_bend_remap_f32")
+        _lib.call("maua_bend_remap_f32", x, y, b, c, h, w, self.op, self.border, table, self.sequence_rows, field, frames, fh, fw, mask, src)
         return y
 
 

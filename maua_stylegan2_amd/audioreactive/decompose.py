@@ -12,7 +12,6 @@ formulation to fall back to.
   * :func:`separate`    the SOUND of every source: soft masks from the factorisation on the complex STFT (csrc/separate.hip behind
                         maua_nmf_separate_f32), one inverse STFT per stem; a stem goes into every ``ar.*`` feature like the clip itself
 """
-import ctypes
 import math
 import warnings
 
@@ -32,9 +31,7 @@ _CHECK_EVERY = 10        # iterations between two evaluations of the divergence 
 
 def _iterate(V, W, H, n_iter, update_w, update_h, eps):
     F, T = V.shape
-    with th.cuda.device(V.device):
-        _lib.check(_lib.load().maua_nmf_kl_f32(V.data_ptr(), W.data_ptr(), H.data_ptr(), F, T, W.shape[1], int(n_iter), int(update_w),
-                                               int(update_h), float(eps), _lib.stream_ptr(V.device)), "maua_nmf_kl_f32")
+    _lib.call("maua_nmf_kl_f32", V, W, H, F, T, W.shape[1], int(n_iter), int(update_w), int(update_h), float(eps))
 
 
 def nmf_divergence(V, W, H, eps=1e-12):
@@ -42,9 +39,7 @@ def nmf_divergence(V, W, H, eps=1e-12):
     device tensor (maua_nmf_kl_div_f32: P in fp32 as the updates compute it, the terms and the sums in double).  Does not synchronise."""
     F, T = V.shape
     cols = th.empty(T, dtype=th.float64, device=V.device)
-    with th.cuda.device(V.device):
-        _lib.check(_lib.load().maua_nmf_kl_div_f32(V.data_ptr(), W.data_ptr(), H.data_ptr(), F, T, W.shape[1], float(eps), cols.data_ptr(),
-                                                   _lib.stream_ptr(V.device)), "maua_nmf_kl_div_f32")
+    _lib.call("maua_nmf_kl_div_f32", V, W, H, F, T, W.shape[1], float(eps), cols)
     return cols.sum()
 
 
@@ -198,10 +193,7 @@ def _resolve_groups(groups, n_components):
 def _masked_spectra(re, im, W, H, group, G, power, g0, n_out, out_re, out_im):
     F, T = re.shape
     ids = np.ascontiguousarray(group, np.int32)
-    with th.cuda.device(re.device):
-        _lib.check(_lib.load().maua_nmf_separate_f32(re.data_ptr(), im.data_ptr(), W.data_ptr(), H.data_ptr(), ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                     F, T, W.shape[1], G, power, g0, n_out, out_re.data_ptr(), out_im.data_ptr(),
-                                                     _lib.stream_ptr(re.device)), "maua_nmf_separate_f32")
+    _lib.call("maua_nmf_separate_f32", re, im, W, H, ids, F, T, W.shape[1], G, power, g0, n_out, out_re, out_im)
 
 
 def separate(audio, sr, n_components=8, groups=None, power=2, n_iter=200, seed=0, W=None, update_w=True, device=None, return_model=False,
@@ -239,13 +231,10 @@ def separate(audio, sr, n_components=8, groups=None, power=2, n_iter=200, seed=0
         out_im = th.empty_like(out_re)
         win = _signal._hann(2048, dev)
         frames_ws = th.empty((T, 2048), dtype=th.float32, device=dev)
-        lib = _lib.load()
         for g0 in range(0, G, per_call):
             n_out = min(per_call, G - g0)
             _masked_spectra(re, im, Wd, Hd, group, G, int(power), g0, n_out, out_re, out_im)
-            with th.cuda.device(dev):
-                for j in range(n_out):
-                    _lib.check(lib.maua_istft_f32(out_re[j].data_ptr(), out_im[j].data_ptr(), win.data_ptr(), 2048, 512, T, frames_ws.data_ptr(),
-                                                  stems[g0 + j].data_ptr(), n, _lib.stream_ptr(dev)), "maua_istft_f32")
+            for j in range(n_out):
+                _lib.call("maua_istft_f32", out_re[j], out_im[j], win, 2048, 512, T, frames_ws, stems[g0 + j], n)
     out = stems.to(device) if device is not None else stems.cpu().numpy()
     return (out, Wd, Hd, group) if return_model else out

@@ -80,10 +80,7 @@ def _run(sos, x, zi, chunk, want64, want32, want_zf):
     y32 = th.empty((F, n), dtype=th.float32, device=dev) if want32 else None
     zf = th.empty((F, ns, 2), dtype=th.float64, device=dev) if want_zf else None
     is64 = x.dtype == th.float64
-    with th.cuda.device(dev):
-        _lib.check(lib.maua_sosfilt_f64(sos_d.data_ptr(), F, ns, None if is64 else x.data_ptr(), x.data_ptr() if is64 else None,
-                                        1 if shared else F, n, chunk, _lib.ptr(zi), _lib.ptr(y64), _lib.ptr(y32), _lib.ptr(zf),
-                                        ws.data_ptr(), _lib.stream_ptr(dev)), "maua_sosfilt_f64")
+    _lib.call("maua_sosfilt_f64", sos_d, F, ns, None if is64 else x, x if is64 else None, 1 if shared else F, n, chunk, zi, y64, y32, zf, ws)
     return y64, y32, zf
 
 
@@ -253,9 +250,7 @@ def envelope(x, attack, release, y0=None):
             raise ValueError(f"envelope: y0 must have {c} entries (got {y0d.numel()})")
     y = th.empty_like(xd)
     if t and c:
-        with th.cuda.device(xd.device):
-            _lib.check(_lib.load().maua_env_follow_f32(xd.data_ptr(), _lib.ptr(y0d), y.data_ptr(), t, c, envelope_coefficient(attack),
-                                                       envelope_coefficient(release), _lib.stream_ptr(xd.device)), "maua_env_follow_f32")
+        _lib.call("maua_env_follow_f32", xd, y0d, y, t, c, envelope_coefficient(attack), envelope_coefficient(release))
     return y.to(src_device)
 
 

@@ -69,10 +69,7 @@ def viterbi(logobs, log_trans, log_init):
     delta_last = th.empty(n_states, dtype=th.float64, device=dev)
     backptr = th.empty((n_frames, n_states), dtype=th.uint8, device=dev)
     states = th.empty(n_frames, dtype=th.int32, device=dev)
-    with th.cuda.device(dev):
-        _lib.check(_lib.load().maua_hmm_viterbi_f64(logobs.data_ptr(), log_trans.data_ptr(), log_init.data_ptr(), n_frames, n_states,
-                                                    delta_last.data_ptr(), backptr.data_ptr(), states.data_ptr(), _lib.stream_ptr(dev)),
-                   "maua_hmm_viterbi_f64")
+    _lib.call("maua_hmm_viterbi_f64", logobs, log_trans, log_init, n_frames, n_states, delta_last, backptr, states)
     return states, delta_last
 
 
@@ -81,9 +78,7 @@ def _posterior(obs, trans, init):
     n_frames, n_states = obs.shape
     gamma = th.empty((n_frames, n_states), dtype=th.float64, device=obs.device)
     scale = th.empty(n_frames, dtype=th.float64, device=obs.device)
-    with th.cuda.device(obs.device):
-        _lib.check(_lib.load().maua_hmm_posterior_f64(obs.data_ptr(), trans.data_ptr(), init.data_ptr(), n_frames, n_states, gamma.data_ptr(),
-                                                      scale.data_ptr(), _lib.stream_ptr(obs.device)), "maua_hmm_posterior_f64")
+    _lib.call("maua_hmm_posterior_f64", obs, trans, init, n_frames, n_states, gamma, scale)
     return gamma, scale
 
 

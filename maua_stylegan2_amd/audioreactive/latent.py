@@ -208,7 +208,7 @@ def _loop_sequence(selection, key_rows, frames, n_loops, n_frames, kind, loop, s
         return out
     key_idx = np.asarray([list(rows) + list(rows[:1] if loop else []) for rows in key_rows], dtype=np.int32).reshape(len(frames), m)
     blocks, bases, n_rows, shared = [], [], 0, {}
-    with th.cuda.device(dev):
+    with th.cuda.device(dev):  # (kept: _const_dev below allocates on the current device)
         for s, (f, period) in enumerate(zip(frames, periods)):
             if f == 0:
                 bases.append(0)
@@ -227,9 +227,7 @@ def _loop_sequence(selection, key_rows, frames, n_loops, n_frames, kind, loop, s
         bank = (sel.reshape(n_sel, -1) if kind == "spline" else sel[:, :1].expand(-1, tail[0], -1).reshape(n_sel, -1)).contiguous()
         row_of_frame, sec_of_frame = loop_frame_tables(frames, periods, n_frames, bases, dev)
         idx = th.from_numpy(key_idx).to(dev)
-        _lib.check(_lib.load().maua_keyframe_blend_f32(bank.data_ptr(), n_sel, bank.shape[1], idx.data_ptr(), weights.data_ptr(),
-                                                       row_of_frame.data_ptr(), sec_of_frame.data_ptr(), out.data_ptr(), n_frames,
-                                                       len(frames), n_rows, m, _lib.stream_ptr(dev)), "maua_keyframe_blend_f32")
+        _lib.call("maua_keyframe_blend_f32", bank, n_sel, bank.shape[1], idx, weights, row_of_frame, sec_of_frame, out, n_frames, len(frames), n_rows, m)
     return out
 
 
@@ -366,12 +364,9 @@ def perlin_noise(shape, res, tileable=(True, False, False), interpolant=None, gr
         raise NotImplementedError("the HIP Perlin kernel implements the default quintic interpolant")
     if any(s % r for s, r in zip(shape, res)):
         raise ValueError("shape must be a multiple of res")
-    lib = _lib.load()
     dev = th.device("cuda", th.cuda.current_device())
     g = perlin_gradients(res, tileable) if gradients is None else np.asarray(gradients, dtype=np.float32)
     gd = th.from_numpy(np.ascontiguousarray(g)).to(dev)
     out = th.empty(tuple(shape), dtype=th.float32, device=dev)
-    with th.cuda.device(dev):
-        _lib.check(lib.maua_perlin3d_f32(gd.data_ptr(), out.data_ptr(), shape[0], shape[1], shape[2], res[0], res[1],
-                                         res[2], _lib.stream_ptr(dev)), "maua_perlin3d_f32")
+    _lib.call("maua_perlin3d_f32", gd, out, shape[0], shape[1], shape[2], res[0], res[1], res[2])
     return out

@@ -190,13 +190,11 @@ class NoiseSynth:
             raise ValueError(f"NoiseSynth.frames: [{frame0}, {frame0 + batch}) is outside the recipe's {n} frames")
         if self.device.type != "cuda":
             raise RuntimeError("NoiseSynth.frames needs the recipe on a HIP device; there is no CPU fallback")
-        with th.cuda.device(self.device):
-            out = th.empty((batch, 1, self.height, self.width), dtype=th.float32, device=self.device)
-            host = self.table_entry(out.data_ptr(), slot, first=frame0)
-            table = th.frombuffer(bytearray(bytes(host)), dtype=th.uint8).to(self.device)
-            _lib.check(_lib.load().maua_noise_synth_f32(table.data_ptr(), 1, batch, self.offset + frame0, None, _lib.stream_ptr(self.device)),
-                       "maua_noise_synth_f32")
-            table.record_stream(th.cuda.current_stream(self.device))
+        out = th.empty((batch, 1, self.height, self.width), dtype=th.float32, device=self.device)
+        host = self.table_entry(out.data_ptr(), slot, first=frame0)
+        table = th.frombuffer(bytearray(bytes(host)), dtype=th.uint8).to(self.device)
+        _lib.call("maua_noise_synth_f32", table, 1, batch, self.offset + frame0, None)
+        table.record_stream(th.cuda.current_stream(self.device))
         return out
 
     def materialize(self, n_frames=None, slot=0, chunk=64):

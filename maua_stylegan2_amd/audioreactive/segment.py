@@ -176,27 +176,21 @@ def onset_envelope(audio, sr, n_mels=128):
 
 def tempogram(env, win):
     """Mean autocorrelation tempogram tg[win] of a device onset envelope (maua_tempogram_f32)."""
-    lib = _lib.load()
     env = env.float().contiguous()
     n = env.numel()
-    ws = th.empty(lib.maua_tempogram_ws_doubles(n, win), dtype=th.float64, device=env.device)
+    ws = th.empty(_lib.load().maua_tempogram_ws_doubles(n, win), dtype=th.float64, device=env.device)
     tg = th.empty(win, dtype=th.float32, device=env.device)
-    with th.cuda.device(env.device):
-        _lib.check(lib.maua_tempogram_f32(env.data_ptr(), n, win, ws.data_ptr(), tg.data_ptr(), _lib.stream_ptr(env.device)),
-                   "maua_tempogram_f32")
+    _lib.call("maua_tempogram_f32", env, n, win, ws, tg)
     return tg
 
 
 def beat_dp(onset_norm, period):
     """(localscore, cumscore, backlink) device tensors of the beat search over a normalised fp64 envelope (maua_beat_track_f64)."""
-    lib = _lib.load()
     x = onset_norm.double().contiguous()
     n = x.numel()
     ls, cs = th.empty_like(x), th.empty_like(x)
     bl = th.empty(n, dtype=th.int32, device=x.device)
-    with th.cuda.device(x.device):
-        _lib.check(lib.maua_beat_track_f64(x.data_ptr(), n, int(period), ls.data_ptr(), cs.data_ptr(), bl.data_ptr(),
-                                           _lib.stream_ptr(x.device)), "maua_beat_track_f64")
+    _lib.call("maua_beat_track_f64", x, n, int(period), ls, cs, bl)
     return ls, cs, bl
 
 
@@ -222,26 +216,20 @@ def beat_track(env, sr, hop=HOP):
 
 def beat_sync(x, bounds, median):
     """[rows, len(bounds) - 1] np.median (``median``) or mean of x[rows, n_frames] over the spans (maua_beat_sync_f32)."""
-    lib = _lib.load()
     x = x.float().contiguous()
     rows, n = x.shape
     b = th.as_tensor(np.asarray(bounds, dtype=np.int32)).to(x.device)
     out = th.empty((rows, b.numel() - 1), dtype=th.float32, device=x.device)
-    with th.cuda.device(x.device):
-        _lib.check(lib.maua_beat_sync_f32(x.data_ptr(), rows, n, b.data_ptr(), b.numel() - 1, int(bool(median)), out.data_ptr(),
-                                          _lib.stream_ptr(x.device)), "maua_beat_sync_f32")
+    _lib.call("maua_beat_sync_f32", x, rows, n, b, b.numel() - 1, int(bool(median)), out)
     return out
 
 
 def knn_links(x, k, width=WIDTH):
     """[S, S] links of the columns of x[D, S]: the distance where row i links column j, -1 elsewhere (maua_knn_links_f32)."""
-    lib = _lib.load()
     x = x.float().contiguous()
     d, s = x.shape
     out = th.empty((s, s), dtype=th.float32, device=x.device)
-    with th.cuda.device(x.device):
-        _lib.check(lib.maua_knn_links_f32(x.data_ptr(), d, s, int(k), int(width), out.data_ptr(), _lib.stream_ptr(x.device)),
-                   "maua_knn_links_f32")
+    _lib.call("maua_knn_links_f32", x, d, s, int(k), int(width), out)
     return out
 
 
@@ -257,13 +245,10 @@ def link_bandwidth(links):
 
 def rec_affinity(links, bandwidth):
     """(R, Rf): mutual-link affinity exp(-d / bandwidth) and its time-lag median filter (maua_rec_affinity_f32)."""
-    lib = _lib.load()
     links = links.float().contiguous()
     s = links.shape[0]
     rec, filt = th.empty_like(links), th.empty_like(links)
-    with th.cuda.device(links.device):
-        _lib.check(lib.maua_rec_affinity_f32(links.data_ptr(), s, float(bandwidth), rec.data_ptr(), filt.data_ptr(),
-                                             _lib.stream_ptr(links.device)), "maua_rec_affinity_f32")
+    _lib.call("maua_rec_affinity_f32", links, s, float(bandwidth), rec, filt)
     return rec, filt
 
 
@@ -288,9 +273,7 @@ def spectral_embedding(rf, msync, k):
     ev32 = evecs.float().contiguous()
     filt = th.empty_like(ev32)
     s = ev32.shape[0]
-    with th.cuda.device(ev32.device):
-        _lib.check(_lib.load().maua_median_filter_f32(ev32.data_ptr(), filt.data_ptr(), s, s, 9, 0, _lib.stream_ptr(ev32.device)),
-                   "maua_median_filter_f32")
+    _lib.call("maua_median_filter_f32", ev32, filt, s, s, 9, 0)
     ev = filt.double()
     cnorm = th.sqrt((ev[:, :k] ** 2).sum(1))
     return ev[:, :k] / cnorm[:, None]

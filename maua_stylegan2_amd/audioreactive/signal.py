@@ -130,28 +130,21 @@ def chroma_filterbank(sr, n_fft=2048, n_chroma=12, ctroct=5.0, octwidth=2.0, tun
 # ------------------------------------------------------------------------------------------------ device primitives
 def stft_power(audio, n_fft=2048, hop=512):
     """|STFT|^2 on device: [n_fft/2+1, 1 + len/hop] float32 (centred, reflect-padded, periodic Hann)."""
-    lib = _lib.load()
     y = _to_dev(audio)
     n = y.numel()
     n_frames = 1 + n // hop
-    win = _hann(n_fft, y.device)
     p = th.empty((n_fft // 2 + 1, n_frames), dtype=th.float32, device=y.device)
-    with th.cuda.device(y.device):
-        _lib.check(lib.maua_stft_power_f32(y.data_ptr(), n, win.data_ptr(), n_fft, hop, p.data_ptr(), n_frames,
-                                           _lib.stream_ptr(y.device)), "maua_stft_power_f32")
+    _lib.call("maua_stft_power_f32", y, n, _hann(n_fft, y.device), n_fft, hop, p, n_frames)
     return p
 
 
 def project(fb, p, to_db=False, amin=1e-10):
     """fb [M,K] (numpy or tensor) @ p [K,N] on device, optional 10*log10(max(amin, .))."""
-    lib = _lib.load()
     fbt = _const_dev(fb, np.float32) if isinstance(fb, np.ndarray) else _to_dev(fb)
     m, k = fbt.shape
     n = p.shape[1]
     out = th.empty((m, n), dtype=th.float32, device=p.device)
-    with th.cuda.device(p.device):
-        _lib.check(lib.maua_filterbank_f32(fbt.data_ptr(), p.data_ptr(), out.data_ptr(), m, k, n, int(to_db), float(amin),
-                                           _lib.stream_ptr(p.device)), "maua_filterbank_f32")
+    _lib.call("maua_filterbank_f32", fbt, p, out, m, k, n, int(to_db), float(amin))
     return out
 
 
@@ -164,7 +157,6 @@ def hpss(audio, margin=1.0, kernel_size=31, power=2.0, n_fft=2048, hop=512):
     effects.percussive / effects.harmonic, signal.py:49,150): complex STFT -> |D| median-filtered along time
     (harmonic-enhanced) and along frequency (percussive-enhanced), soft masks with ``margin``, inverse STFT.
     Returns (y_harmonic, y_percussive) as device tensors of the input length."""
-    lib = _lib.load()
     y = _to_dev(audio)
     n = y.numel()
     n_frames = 1 + n // hop
@@ -174,27 +166,19 @@ def hpss(audio, margin=1.0, kernel_size=31, power=2.0, n_fft=2048, hop=512):
     re = th.empty((n_bins, n_frames), dtype=th.float32, device=dev)
     im = th.empty_like(re)
     outs = []
-    with th.cuda.device(dev):
-        st = _lib.stream_ptr(dev)
-        _lib.check(lib.maua_stft_complex_f32(y.data_ptr(), n, win.data_ptr(), n_fft, hop, re.data_ptr(), im.data_ptr(),
-                                             n_frames, st), "maua_stft_complex_f32")
-        mag = th.sqrt(re * re + im * im)
-        harm, perc = th.empty_like(mag), th.empty_like(mag)
-        _lib.check(lib.maua_median_filter_f32(mag.data_ptr(), harm.data_ptr(), n_bins, n_frames, kernel_size, 1, st),
-                   "maua_median_filter_f32")
-        _lib.check(lib.maua_median_filter_f32(mag.data_ptr(), perc.data_ptr(), n_bins, n_frames, kernel_size, 0, st),
-                   "maua_median_filter_f32")
-        split = int(margin == 1)
-        frames_ws = th.empty((n_frames, n_fft), dtype=th.float32, device=dev)
-        for own, other in ((harm, perc), (perc, harm)):
-            mre, mim = th.empty_like(re), th.empty_like(im)
-            _lib.check(lib.maua_softmask_apply_f32(re.data_ptr(), im.data_ptr(), own.data_ptr(), other.data_ptr(),
-                                                   float(margin), float(power), split, mre.data_ptr(), mim.data_ptr(),
-                                                   re.numel(), st), "maua_softmask_apply_f32")
-            out = th.empty(n, dtype=th.float32, device=dev)
-            _lib.check(lib.maua_istft_f32(mre.data_ptr(), mim.data_ptr(), win.data_ptr(), n_fft, hop, n_frames,
-                                          frames_ws.data_ptr(), out.data_ptr(), n, st), "maua_istft_f32")
-            outs.append(out)
+    _lib.call("maua_stft_complex_f32", y, n, win, n_fft, hop, re, im, n_frames)
+    mag = th.sqrt(re * re + im * im)
+    harm, perc = th.empty_like(mag), th.empty_like(mag)
+    _lib.call("maua_median_filter_f32", mag, harm, n_bins, n_frames, kernel_size, 1)
+    _lib.call("maua_median_filter_f32", mag, perc, n_bins, n_frames, kernel_size, 0)
+    split = int(margin == 1)
+    frames_ws = th.empty((n_frames, n_fft), dtype=th.float32, device=dev)
+    for own, other in ((harm, perc), (perc, harm)):
+        mre, mim = th.empty_like(re), th.empty_like(im)
+        _lib.call("maua_softmask_apply_f32", re, im, own, other, float(margin), float(power), split, mre, mim, re.numel())
+        out = th.empty(n, dtype=th.float32, device=dev)
+        _lib.call("maua_istft_f32", mre, mim, win, n_fft, hop, n_frames, frames_ws, out, n)
+        outs.append(out)
     return outs[0], outs[1]
 
 
@@ -209,14 +193,12 @@ def harmonic(audio, margin=1.0):
 def resample(x, num):
     """Fourier-method resampling along dim 0 (what scipy.signal.resample does at reference :68,152) on device:
     maua_resample_f64, float64 in and out like scipy."""
-    src = _to_dev(x, th.float64).contiguous()
+    src = _to_dev(x, th.float64)
     n = src.shape[0]
     num = int(num)
     out = th.empty((num,) + tuple(src.shape[1:]), dtype=th.float64, device=src.device)
     features = max(src.numel() // max(n, 1), 1)
-    with th.cuda.device(src.device):
-        _lib.check(_lib.load().maua_resample_f64(src.data_ptr(), n, features, out.data_ptr(), num,
-                                                 _lib.stream_ptr(src.device)), "maua_resample_f64")
+    _lib.call("maua_resample_f64", src, n, features, out, num)
     return out
 
 
@@ -225,7 +207,6 @@ TEMPORAL_FIR_MAX_RADIUS = 8143  # MAUA_TEMPORAL_FIR_MAX_RADIUS (include/maua_hip
 
 def gaussian_filter(x, sigma, causal=None):
     """Circular Gaussian smoothing along time (dim 0), HIP FIR kernel; same tap construction as reference :335-343."""
-    lib = _lib.load()
     src_device = x.device if isinstance(x, th.Tensor) else th.device("cpu")
     xd = _to_dev(x)
     dim = xd.dim()
@@ -247,9 +228,7 @@ def gaussian_filter(x, sigma, causal=None):
     if radius > TEMPORAL_FIR_MAX_RADIUS:  # (include/maua_hip.h: the taps live in LDS)
         raise RuntimeError(f"gaussian_filter: radius {radius} frames (sigma {sigma}) exceeds the device filter's {TEMPORAL_FIR_MAX_RADIUS} taps "
                            "each side — a Gaussian that wide is a mean over the clip; lower sigma")
-    with th.cuda.device(xd.device):
-        _lib.check(lib.maua_temporal_fir_f32(xd.data_ptr(), taps.data_ptr(), y.data_ptr(), n_frames, feats, radius,
-                                             _lib.stream_ptr(xd.device)), "maua_temporal_fir_f32")
+    _lib.call("maua_temporal_fir_f32", xd, taps, y, n_frames, feats, radius)
     if dim < 3:
         y = y.reshape(list(xd.shape) + [1] * (3 - dim)).squeeze()
     return y.to(src_device)
@@ -342,16 +321,12 @@ def onset_functions_sum(filt):
 
 def stft_complex(audio, n_fft=2048, hop=512):
     """Complex STFT on device as (re, im), each [n_fft/2+1, 1 + len/hop] float32 (centred, reflect-padded, periodic Hann)."""
-    lib = _lib.load()
     y = _to_dev(audio)
     n = y.numel()
     n_frames = 1 + n // hop
-    win = _hann(n_fft, y.device)
     re = th.empty((n_fft // 2 + 1, n_frames), dtype=th.float32, device=y.device)
     im = th.empty_like(re)
-    with th.cuda.device(y.device):
-        _lib.check(lib.maua_stft_complex_f32(y.data_ptr(), n, win.data_ptr(), n_fft, hop, re.data_ptr(), im.data_ptr(), n_frames,
-                                             _lib.stream_ptr(y.device)), "maua_stft_complex_f32")
+    _lib.call("maua_stft_complex_f32", y, n, _hann(n_fft, y.device), n_fft, hop, re, im, n_frames)
     return re, im
 
 
@@ -450,11 +425,9 @@ def rms(y, sr, n_frames, fmin=20, fmax=8000, smooth=180, clip=50, power=6, devic
 def cens(ch, win_len=41):
     """CENS post-processing of a [n_bins, T] chromagram on the device (maua_chroma_cens_f32): L1 normalise, quantise,
     Hann-smooth over ``win_len`` frames, L2 normalise — the steps of librosa.feature.chroma_cens after its chromagram."""
-    ch = _to_dev(ch).float().contiguous()
+    ch = _to_dev(ch)
     out = th.empty_like(ch)
-    with th.cuda.device(ch.device):
-        _lib.check(_lib.load().maua_chroma_cens_f32(ch.data_ptr(), out.data_ptr(), ch.shape[0], ch.shape[1], win_len,
-                                                    _lib.stream_ptr(ch.device)), "maua_chroma_cens_f32")
+    _lib.call("maua_chroma_cens_f32", ch, out, ch.shape[0], ch.shape[1], win_len)
     return out
 
 
@@ -462,18 +435,15 @@ def nn_filter(ch, width=1):
     """Nearest-neighbour median filter of a [n_bins, T] sequence on the device (maua_nn_median_f32): per frame, the median
     over the k = 2 ceil(sqrt(T - 2 width + 1)) most cosine-similar frames (reference signal.py:131).  Tracks whose similarity
     rows no longer fit LDS (> ~16k frames, 6 min of audio) run the same kernel on a device workspace."""
-    ch = _to_dev(ch).float().contiguous()
+    ch = _to_dev(ch)
     t = ch.shape[1]
     k = int(min(t - 1, 2 * math.ceil(math.sqrt(max(t - 2 * width + 1, 1)))))
     if k < 1:
         return ch
     out = th.empty_like(ch)
-    lib = _lib.load()
-    n_ws = lib.maua_nn_median_ws_doubles(ch.shape[0], t, k)
+    n_ws = _lib.load().maua_nn_median_ws_doubles(ch.shape[0], t, k)
     ws = th.empty(n_ws, dtype=th.float64, device=ch.device) if n_ws else None
-    with th.cuda.device(ch.device):
-        _lib.check(lib.maua_nn_median_f32(ch.data_ptr(), out.data_ptr(), ch.shape[0], t, k, width, _lib.ptr(ws),
-                                          _lib.stream_ptr(ch.device)), "maua_nn_median_f32")
+    _lib.call("maua_nn_median_f32", ch, out, ch.shape[0], t, k, width, ws)
     return out
 
 
@@ -535,7 +505,7 @@ CQT_FMIN = 32.70319566257483  # C1, librosa's default
 def cqt_magnitude(audio, sr, hop=512, n_bins=252, fmin=CQT_FMIN, bins_per_octave=36):
     """|constant-Q transform| on the device, [n_bins, 1 + len/hop] float32 (maua_cqt_mag_f32): 7 octaves x 36 bins from
     C1 as librosa.feature.chroma_cqt asks of librosa.cqt, evaluated directly from the definition."""
-    y = _to_dev(audio).float().contiguous()
+    y = _to_dev(audio)
     freqs = (fmin * 2.0 ** (np.arange(n_bins) / bins_per_octave))
     q = 1.0 / (2.0 ** (1.0 / bins_per_octave) - 1.0)
     lengths = np.ceil(q * sr / freqs).astype(np.int32)
@@ -543,10 +513,7 @@ def cqt_magnitude(audio, sr, hop=512, n_bins=252, fmin=CQT_FMIN, bins_per_octave
     out = th.empty((n_bins, n_frames), dtype=th.float32, device=y.device)
     f_dev = _const_dev(freqs.astype(np.float32))
     l_dev = _const_dev(lengths)
-    with th.cuda.device(y.device):
-        _lib.check(_lib.load().maua_cqt_mag_f32(y.data_ptr(), y.numel(), f_dev.data_ptr(), l_dev.data_ptr(), n_bins, hop,
-                                                float(sr), out.data_ptr(), n_frames, _lib.stream_ptr(y.device)),
-                   "maua_cqt_mag_f32")
+    _lib.call("maua_cqt_mag_f32", y, y.numel(), f_dev, l_dev, n_bins, hop, float(sr), out, n_frames)
     return out
 
 
@@ -623,10 +590,7 @@ def raw_pitch(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, thr
     lag = th.empty(n_frames, dtype=th.float32, device=y.device)
     aperiodicity = th.empty_like(lag)
     tau_int = th.empty(n_frames, dtype=th.int32, device=y.device)
-    with th.cuda.device(y.device):
-        _lib.check(_lib.load().maua_yin_f32(y.data_ptr(), n, int(frame_length), int(hop), tau_min, tau_max, float(threshold), lag.data_ptr(),
-                                            aperiodicity.data_ptr(), tau_int.data_ptr(), None, n_frames, _lib.stream_ptr(y.device)),
-                   "maua_yin_f32")
+    _lib.call("maua_yin_f32", y, n, int(frame_length), int(hop), tau_min, tau_max, float(threshold), lag, aperiodicity, tau_int, None, n_frames)
     return float(sr) / lag, 1.0 - aperiodicity.clamp(max=1.0)
 
 
@@ -692,20 +656,14 @@ def _pyin_stages(audio, sr, fmin=65.0, fmax=2100.0, frame_length=2048, hop=512, 
     delta_last = th.empty(2 * n_bins, dtype=th.float64, device=dev)
     backptr = th.empty(n_frames, 2 * n_bins, dtype=th.int16, device=dev)  # (the bits of uint16: values stay below 2048)
     states = th.empty(n_frames, dtype=th.int32, device=dev)
-    lib = _lib.load()
-    with th.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
-        _lib.check(lib.maua_yin_f32(y.data_ptr(), n, int(frame_length), int(hop), tau_min, tau_max, 0.1, lag.data_ptr(), aperiodicity.data_ptr(),
-                                    tau_int.data_ptr(), cmndf.data_ptr(), n_frames, stream), "maua_yin_f32")
-        _lib.check(lib.maua_pyin_candidates_f32(cmndf.data_ptr(), n_frames, tau_min, tau_max, cum_prior.data_ptr(), n_thr, float(no_trough_prob),
-                                                edge.data_ptr(), n_bins, obs.data_ptr(), period.data_ptr(), voiced_prob.data_ptr(), stream),
-                   "maua_pyin_candidates_f32")
-        tiny = float(np.finfo(np.float32).tiny)
-        logobs_voiced = obs.clamp(min=tiny).log().contiguous()
-        logobs_unvoiced = ((1.0 - voiced_prob) / float(n_bins)).clamp(min=tiny).log().contiguous()
-        _lib.check(lib.maua_pyin_viterbi_f64(logobs_voiced.data_ptr(), logobs_unvoiced.data_ptr(), n_frames, n_bins, width, log_tri.data_ptr(),
-                                             log_norm.data_ptr(), -math.log(2 * n_bins), math.log(1 - switch_prob), math.log(switch_prob),
-                                             delta_last.data_ptr(), backptr.data_ptr(), states.data_ptr(), stream), "maua_pyin_viterbi_f64")
+    _lib.call("maua_yin_f32", y, n, int(frame_length), int(hop), tau_min, tau_max, 0.1, lag, aperiodicity, tau_int, cmndf, n_frames)
+    _lib.call("maua_pyin_candidates_f32", cmndf, n_frames, tau_min, tau_max, cum_prior, n_thr, float(no_trough_prob), edge, n_bins, obs, period,
+              voiced_prob)
+    tiny = float(np.finfo(np.float32).tiny)
+    logobs_voiced = obs.clamp(min=tiny).log()
+    logobs_unvoiced = ((1.0 - voiced_prob) / float(n_bins)).clamp(min=tiny).log()
+    _lib.call("maua_pyin_viterbi_f64", logobs_voiced, logobs_unvoiced, n_frames, n_bins, width, log_tri, log_norm, -math.log(2 * n_bins),
+              math.log(1 - switch_prob), math.log(switch_prob), delta_last, backptr, states)
     voiced_flag = states < n_bins
     pitch_bin = th.where(voiced_flag, states, states - n_bins).long()
     per = period.gather(1, pitch_bin[:, None])[:, 0]
@@ -746,9 +704,7 @@ def _median5(x):
     """5-tap median along time on the device (maua_median_filter_f32, symmetric reflection at the ends)."""
     x = x.contiguous()
     out = th.empty_like(x)
-    with th.cuda.device(x.device):
-        _lib.check(_lib.load().maua_median_filter_f32(x.data_ptr(), out.data_ptr(), x.shape[0], 1, 5, 0, _lib.stream_ptr(x.device)),
-                   "maua_median_filter_f32")
+    _lib.call("maua_median_filter_f32", x, out, x.shape[0], 1, 5, 0)
     return out
 
 

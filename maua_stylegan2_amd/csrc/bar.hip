@@ -7,7 +7,7 @@
 //
 // One workgroup per model (blockIdx.x), lane = k * B + b, everything the recursion touches per frame in LDS:
 //   lc    [K][K | 1]      log_change, staged once; lane (k, b) walks the sources k' in order and reads lc[k' * stride + k]: the lanes of
-//                         one k broadcast, neighbouring k are neighbouring doubles (the stride of hmm.hip, conflict-free).
+//                         one k broadcast, neighbouring k are neighbouring doubles (dense_stride of wave.h, conflict-free).
 //   X     [2][lanes]      the exit values of the frame, published in two buffers in turn: one barrier per frame.  Lane (k, b) reads
 //                         X[k' * B + b']: B distinct runs, broadcast within each.
 //   ring  [slot][lanes]   per lane its last interval[k] entry values, slot = t mod interval[k]: V[t - interval[k]] is read from the
@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -38,8 +39,6 @@ struct BarModel {  // by value in the kernarg segment: 544 bytes
 struct BarSegment {  // frames max(e, 0) .. end of the path are (k, b, f - e)
     int32_t e, end, k, b;
 };
-
-__host__ __device__ constexpr int bar_stride(int K) { return K | 1; }
 
 // per-model regions of the workspace, in this order for all models: P [3][T + 1] doubles, segments [T + 1], back pointers [T][lanes]
 __host__ __device__ inline int64_t bar_ws_p(int T) { return 3 * ((int64_t)T + 1) * (int64_t)sizeof(double); }
@@ -59,7 +58,7 @@ __global__ __launch_bounds__(1024) void bar_viterbi_kernel(const float* __restri
     const int ll = live ? lane : 0;
     const int k = ll / B, b = ll % B;
     const int I = model.interval[k], W = model.width[k];
-    const int stride = bar_stride(K);
+    const int stride = dense_stride(K);
     double* lc = lds;
     double* X = lc + K * stride;
     double* ring = X + 2 * max_lanes;
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(1024) void bar_viterbi_kernel(const float* __restri
             p[n + 1] = acc;
         }
     }
-    for (int idx = lane; idx < K * K; idx += blockDim.x) lc[(idx / K) * stride + idx % K] = log_change[idx];
+    stage_dense(lc, log_change, K, stride);
     for (int idx = lane; idx < L * ring_len; idx += blockDim.x) ring[idx] = 0.0;
     __threadfence();  // the prefix sums, before the other waves read them
     __syncthreads();
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(1024) void bar_viterbi_kernel(const float* __restri
     __threadfence();  // the back pointers of every wave, before lane 0 reads them
     __syncthreads();
     if (lane == 0) {
-        double best = -INFINITY;
+        double best = -INFINITY;  // (not first_max: a NaN in X[0] is stepped over here and would stay there)
         int at = 0;
         for (int q = 0; q < L; ++q)
             if (X[q] > best) best = X[q], at = q;
@@ -171,7 +170,7 @@ extern "C" int64_t maua_bar_lds_bytes(int n_tempi, int max_beats, int max_interv
     if (!bar_counts_ok(n_tempi, max_beats) || max_interval < 1 || max_interval > MAUA_BAR_MAX_INTERVAL) return 0;
     const int64_t lanes = (int64_t)n_tempi * max_beats;
     // (two buffers of `lanes` doubles hold the lanes' first maxima as doubles, as ints, and one int more at the end: lanes >= 1)
-    const int64_t bytes = ((int64_t)n_tempi * bar_stride(n_tempi) + 2 * lanes + lanes * max_interval) * (int64_t)sizeof(double);
+    const int64_t bytes = ((int64_t)n_tempi * dense_stride(n_tempi) + 2 * lanes + lanes * max_interval) * (int64_t)sizeof(double);
     const int64_t padded = (bytes + 15) / 16 * 16;
     return padded <= BAR_LDS_LIMIT ? padded : 0;
 }

@@ -21,18 +21,13 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int HMM_BLOCK = 128;          // MAUA_HMM_MAX_STATES lanes: two waves
 constexpr int HMM_TRACE_ROWS = 1024;    // frames of back pointers per LDS chunk of the walk back
 static_assert(MAUA_HMM_MAX_STATES <= HMM_BLOCK && MAUA_HMM_MAX_STATES <= 256, "a lane per state, a byte per back pointer");
-
-__host__ __device__ constexpr int hmm_stride(int S) { return S | 1; }
-
-__device__ __forceinline__ void hmm_stage(double* tr, const double* __restrict__ src, int S, int stride) {
-    for (int idx = threadIdx.x; idx < S * S; idx += blockDim.x) tr[(idx / S) * stride + idx % S] = src[idx];
-}
 
 __global__ __launch_bounds__(HMM_BLOCK) void hmm_viterbi_kernel(const float* __restrict__ logobs, const double* __restrict__ log_trans,
                                                                 const double* __restrict__ log_init, int T, int S,
@@ -42,10 +37,10 @@ __global__ __launch_bounds__(HMM_BLOCK) void hmm_viterbi_kernel(const float* __r
     const int j = threadIdx.x;
     const bool live = j < S;
     const int jj = live ? j : 0;
-    const int stride = hmm_stride(S);
+    const int stride = dense_stride(S);
     double* tr = lds;
     double* dl = lds + S * stride;
-    hmm_stage(tr, log_trans, S, stride);
+    stage_dense(tr, log_trans, S, stride);
     double d = log_init[jj] + (double)logobs[jj];
     if (live) backptr[j] = (uint8_t)j;
     const double* col = tr + jj;
@@ -69,11 +64,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void hmm_viterbi_kernel(const float* __r
     __threadfence();  // the back pointers of both waves, before they are read back
     __syncthreads();
     int s = 0;
-    if (j == 0) {
-        double best = fin[0];
-        for (int k = 1; k < S; ++k)
-            if (fin[k] > best) best = fin[k], s = k;
-    }
+    if (j == 0) first_max(fin, S, s);
     __syncthreads();  // fin is read: the chunks may overlay everything
     uint8_t* rows = reinterpret_cast<uint8_t*>(lds);
     int32_t* st = reinterpret_cast<int32_t*>(rows + HMM_TRACE_ROWS * S);
@@ -101,11 +92,11 @@ __global__ __launch_bounds__(HMM_BLOCK) void hmm_posterior_kernel(const float* _
     const int j = threadIdx.x;
     const bool live = j < S;
     const int jj = live ? j : 0;
-    const int stride = hmm_stride(S);
+    const int stride = dense_stride(S);
     double* tr = lds;
     double* va = lds + S * stride;  // forward: alpha of the frame before; backward: u of the odd frames
     double* vs = va + S;            // forward: a of this frame;           backward: u of the even frames
-    hmm_stage(tr, trans, S, stride);
+    stage_dense(tr, trans, S, stride);
     const double* col = tr + jj;
     double a = init[jj] * (double)obs[jj];
     for (int t = 0; t < T; ++t) {
@@ -155,7 +146,7 @@ extern "C" int maua_hmm_viterbi_f64(const float* logobs, const double* log_trans
     if (!logobs || !log_trans || !log_init || !delta_last || !backptr || !states) return MAUA_EINVAL;
     if (!hmm_shape_ok(n_frames, n_states)) return MAUA_EINVAL;
     const int S = n_states;
-    const size_t forward = ((size_t)S * hmm_stride(S) + 2 * S) * sizeof(double);                  // 131 KiB at S = 128
+    const size_t forward = ((size_t)S * dense_stride(S) + 2 * S) * sizeof(double);                  // 131 KiB at S = 128
     const size_t walk = (size_t)HMM_TRACE_ROWS * S + (size_t)HMM_TRACE_ROWS * sizeof(int32_t);    // 132 KiB at S = 128
     const size_t lds = ((forward > walk ? forward : walk) + 15) / 16 * 16;
     static unsigned long long lds_ok = 0;
@@ -171,7 +162,7 @@ extern "C" int maua_hmm_posterior_f64(const float* obs, const double* trans, con
     if (!obs || !trans || !init || !gamma || !scale) return MAUA_EINVAL;
     if (!hmm_shape_ok(n_frames, n_states)) return MAUA_EINVAL;
     const int S = n_states;
-    const size_t lds = (((size_t)S * hmm_stride(S) + 2 * S) * sizeof(double) + 15) / 16 * 16;
+    const size_t lds = (((size_t)S * dense_stride(S) + 2 * S) * sizeof(double) + 15) / 16 * 16;
     static unsigned long long lds_ok = 0;
     if (int rc = maua_allow_full_lds(reinterpret_cast<const void*>(hmm_posterior_kernel), &lds_ok)) return rc;
     hipLaunchKernelGGL(hmm_posterior_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), lds, (hipStream_t)stream, obs, trans, init, n_frames, S,

@@ -44,6 +44,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 constexpr int kSegBytesPerMcu = 2496;
@@ -238,12 +239,7 @@ __global__ __launch_bounds__(256) void jpeg_dct_quant_kernel(const uint8_t* __re
 template <typename T>
 __device__ __forceinline__ T block_scan(T v, T* part, T& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = __shfl_up(x, d, 64);
-        if (lane >= d) x += up;
-    }
+    const T x = wave_incl_sum(v, lane);
     if (lane == 63) part[wave] = x;
     __syncthreads();
     T base = 0;

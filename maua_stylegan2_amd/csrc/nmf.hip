@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void nmf_w_kernel(const float* __restrict__ v,
     }
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        float x = i < FR * KP ? acc[i / KP][i % KP] : hs[i % KP];
+        float x = i < FR * KP ? acc[i / KP][i % KP] : hs[i % KP];  // (wave_sum of wave.h, spelled out: the call reschedules this kernel)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
         if (lane == 0) red[wave][i] = x;

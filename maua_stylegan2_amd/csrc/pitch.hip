@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void yin_kernel(const float* __restrict__ y, i
         float own = 0.f;
         for (int k = 0; k < per_lane; ++k)
             if (first + k <= tau_max) own += dp[first + k];
-        float inc = own;
+        float inc = own;  // (wave_incl_sum of wave.h, spelled out: the call reschedules this kernel)
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const float v = __shfl_up(inc, off, 64);
@@ -115,11 +116,7 @@ __global__ __launch_bounds__(256) void yin_kernel(const float* __restrict__ y, i
             found = tau;
             break;
         }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int o = __shfl_xor(found, off, 64);
-        found = o < found ? o : found;
-    }
+    found = wave_min(found);
     int tau;
     if (found != 0x7fffffff) {
         tau = found;

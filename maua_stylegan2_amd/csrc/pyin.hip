@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -56,12 +57,7 @@ __global__ __launch_bounds__(64) void pyin_candidates_kernel(const float* __rest
     float own = INFINITY;
     for (int tau = first; tau < last; ++tau)
         if (pyin_trough(r, tau, tau_min) && r[tau] < own) own = r[tau];
-    float inc = own;  // inclusive prefix-min over the lanes
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float v = __shfl_up(inc, off, 64);
-        if (lane >= off && v < inc) inc = v;
-    }
+    const float inc = wave_incl_min(own, lane);  // inclusive prefix-min over the lanes
     float before = __shfl_up(inc, 1, 64);
     if (lane == 0) before = INFINITY;
 
@@ -69,12 +65,7 @@ __global__ __launch_bounds__(64) void pyin_candidates_kernel(const float* __rest
     float m = before;
     for (int tau = first; tau < last; ++tau)
         if (pyin_trough(r, tau, tau_min) && r[tau] < m) m = r[tau], ++n_own;
-    int at = n_own;  // inclusive prefix sum of the record counts
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(at, off, 64);
-        if (lane >= off) at += v;
-    }
+    int at = wave_incl_sum(n_own, lane);  // inclusive prefix sum of the record counts
     const int n_rec = __shfl(at, 63, 64);
     at -= n_own;
     m = before;
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(1024) void pyin_viterbi_kernel(const float* __restr
     __threadfence();  // the back pointers of every wave, before lane 0 reads them
     __syncthreads();
     if (j == 0) {
-        double best = e[0];
+        double best = e[0];  // (first_max of wave.h, spelled out: the call reschedules this kernel)
         int s = 0;
         for (int k = 1; k < 2 * P; ++k)
             if (e[k] > best) best = e[k], s = k;

@@ -12,24 +12,11 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ wave / block helpers
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
 
 // Order-preserving map of a float onto an unsigned key (negative values reversed below the positive ones).
 __device__ __forceinline__ unsigned fkey(float v) {
@@ -85,7 +72,7 @@ __global__ __launch_bounds__(256) void tempogram_kernel(const float* __restrict_
             ac[m] = s;
             mx = fmax(mx, fabs(s));
         }
-        mx = wave_max_f64(mx);
+        mx = wave_max(mx);
         if (lane == 0) wmax[wid] = mx;
         __syncthreads();
         mx = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(64) void beat_dp_kernel(const double* __restrict__ 
     }
     double mx = -INFINITY;
     for (int i = lane; i < n; i += 64) mx = fmax(mx, ls[i]);
-    const double thr = 0.01 * wave_max_f64(mx);
+    const double thr = 0.01 * wave_max(mx);
     bool first = true;
     for (int i0 = 0; i0 < n; i0 += 64) {
         __syncthreads();
@@ -204,7 +191,7 @@ __device__ unsigned wave_select(const float* __restrict__ src, int L, int rank, 
             }
         __syncthreads();
         const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-        const int incl = wave_incl_scan(c0 + c1 + c2 + c3, lane);
+        const int incl = wave_incl_sum(c0 + c1 + c2 + c3, lane);
         const int excl = incl - (c0 + c1 + c2 + c3);
         const unsigned long long hit = __ballot(excl <= rank && rank < incl);
         int bin = 0, before = excl;
@@ -234,8 +221,7 @@ __global__ __launch_bounds__(256) void beat_sync_kernel(const float* __restrict_
     // before the end of the one before it)
     int b0 = 0;
     for (int q = lane; q <= s; q += 64) b0 = max(b0, bounds[q]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) b0 = max(b0, __shfl_xor(b0, off));
+    b0 = wave_max(b0);
     b0 = b0 > n_frames ? n_frames : b0;
     int b1 = bounds[s + 1];
     b1 = b1 < b0 ? b0 : (b1 > n_frames ? n_frames : b1);
@@ -256,8 +242,7 @@ __global__ __launch_bounds__(256) void beat_sync_kernel(const float* __restrict_
         double sum = 0.0;
         if (active)
             for (int i = lane; i < L; i += 64) sum += (double)src[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        sum = wave_sum(sum);
         v = (float)(sum / L);
     }
     if (active && lane == 0) out[(int64_t)r * n_spans + s] = v;
@@ -270,7 +255,7 @@ constexpr int KNN_MAX_D = 1024;
 // Block-wide exclusive scan of one int per thread (256 threads); wsum = 4 ints of LDS.
 __device__ __forceinline__ int block_excl_scan(int v, int* wsum, int* total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(v, lane);
+    const int incl = wave_incl_sum(v, lane);
     __syncthreads();
     if (lane == 63) wsum[wid] = incl;
     __syncthreads();

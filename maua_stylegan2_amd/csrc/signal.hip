@@ -12,6 +12,7 @@
 // register-tiled 16 outputs deep along time so each staged sample feeds 16 FMAs, lanes run along the contiguous
 // feature axis (dense 256-byte loads), taps are broadcast from LDS.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -96,19 +97,23 @@ __global__ __launch_bounds__(256) void temporal_fir_kernel(const float* __restri
         if (t0 + u < T) y[(int64_t)(t0 + u) * F + f] = acc[u];
 }
 
-// One workgroup = one STFT frame: radix-2 DIT FFT of n_fft (<= 4096) complex points in LDS, twiddles from a table
-// built once per workgroup with sincospif.
-__global__ __launch_bounds__(256) void stft_power_kernel(const float* __restrict__ y, int64_t n, const float* __restrict__ win,
-                                                         int n_fft, int log2n, int hop, float* __restrict__ p,
-                                                         int n_frames) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* re = sm;
-    float* im = sm + n_fft;
-    float* twc = sm + 2 * n_fft;  // cos(-2 pi k / n), k < n/2
-    float* tws = twc + n_fft / 2;
-    const int frame = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int64_t start = (int64_t)frame * hop - n_fft / 2;
+// ------------------------------------------------------------------------------------------------ LDS FFT: STFT and HPSS building blocks
+// Complex STFT / inverse STFT, 31-tap median filters along time and frequency, soft masks: the pieces of
+// librosa.effects.percussive / harmonic as called at /root/reference/audioreactive/signal.py:49,150.
+// The three FFT kernels share one LDS layout — re [n_fft], im [n_fft], twc, tws [n_fft / 2] — and the three pieces below.
+
+// cos / sin(-2 pi k / n_fft), k < n_fft / 2, built once per workgroup with sincospif
+__device__ __forceinline__ void lds_twiddles(float* twc, float* tws, int n_fft, int tid) {
+    for (int k = tid; k < n_fft / 2; k += 256) {
+        float s_, c_;
+        sincospif(-2.0f * (float)k / (float)n_fft, &s_, &c_);
+        twc[k] = c_, tws[k] = s_;
+    }
+}
+
+// the windowed real frame that starts at sample `start` of y[n], reflect-padded, in bit-reversed order
+__device__ __forceinline__ void lds_load_real_frame(float* re, float* im, const float* __restrict__ y, int64_t n,
+                                                    const float* __restrict__ win, int n_fft, int log2n, int64_t start, int tid) {
     for (int i = tid; i < n_fft; i += 256) {
         int64_t src = start + i;  // reflect padding (numpy 'reflect': no edge repeat)
         if (n > 1) {
@@ -123,35 +128,9 @@ __global__ __launch_bounds__(256) void stft_power_kernel(const float* __restrict
         re[rev] = y[src] * win[i];
         im[rev] = 0.f;
     }
-    for (int k = tid; k < n_fft / 2; k += 256) {
-        float s_, c_;
-        sincospif(-2.0f * (float)k / (float)n_fft, &s_, &c_);
-        twc[k] = c_;
-        tws[k] = s_;
-    }
-    __syncthreads();
-    for (int st = 1; st <= log2n; ++st) {
-        const int half = 1 << (st - 1);
-        const int tw_stride = n_fft >> st;
-        for (int bfly = tid; bfly < n_fft / 2; bfly += 256) {
-            const int grp = bfly / half, k = bfly - grp * half;
-            const int a = grp * 2 * half + k, b = a + half;
-            const float c_ = twc[k * tw_stride], s_ = tws[k * tw_stride];
-            const float br = re[b] * c_ - im[b] * s_;
-            const float bi = re[b] * s_ + im[b] * c_;
-            const float ar = re[a], ai = im[a];
-            re[a] = ar + br, im[a] = ai + bi;
-            re[b] = ar - br, im[b] = ai - bi;
-        }
-        __syncthreads();
-    }
-    for (int k = tid; k <= n_fft / 2; k += 256) p[(int64_t)k * n_frames + frame] = re[k] * re[k] + im[k] * im[k];
 }
 
-// ------------------------------------------------------------------------------------------------ HPSS building blocks
-// Complex STFT / inverse STFT (same LDS radix-2 FFT as stft_power_kernel), 31-tap median filters along time and
-// frequency, soft masks: the pieces of librosa.effects.percussive / harmonic as called at
-// /root/reference/audioreactive/signal.py:49,150.
+// radix-2 DIT FFT of n_fft (<= 4096) complex points in bit-reversed order
 __device__ __forceinline__ void lds_fft_radix2(float* re, float* im, const float* twc, const float* tws, int n_fft, int log2n,
                                                int tid) {
     for (int st = 1; st <= log2n; ++st) {
@@ -171,38 +150,38 @@ __device__ __forceinline__ void lds_fft_radix2(float* re, float* im, const float
     }
 }
 
-__global__ __launch_bounds__(256) void stft_complex_kernel(const float* __restrict__ y, int64_t n, const float* __restrict__ win,
-                                                           int n_fft, int log2n, int hop, float* __restrict__ out_re,
-                                                           float* __restrict__ out_im, int n_frames) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+// One workgroup = one STFT frame: the spectrum of frame blockIdx.x, left in re = sm, im = sm + n_fft.
+__device__ __forceinline__ void stft_frame(float* sm, const float* __restrict__ y, int64_t n, const float* __restrict__ win, int n_fft,
+                                           int log2n, int hop) {
     float* re = sm;
     float* im = sm + n_fft;
     float* twc = sm + 2 * n_fft;
     float* tws = twc + n_fft / 2;
     const int frame = blockIdx.x, tid = threadIdx.x;
-    const int64_t start = (int64_t)frame * hop - n_fft / 2;
-    for (int i = tid; i < n_fft; i += 256) {
-        int64_t src = start + i;
-        if (n > 1) {
-            const int64_t period = 2 * (n - 1);
-            src %= period;
-            if (src < 0) src += period;
-            if (src >= n) src = period - src;
-        } else {
-            src = 0;
-        }
-        const int rev = (int)(__brev((unsigned)i) >> (32 - log2n));
-        re[rev] = y[src] * win[i];
-        im[rev] = 0.f;
-    }
-    for (int k = tid; k < n_fft / 2; k += 256) {
-        float s_, c_;
-        sincospif(-2.0f * (float)k / (float)n_fft, &s_, &c_);
-        twc[k] = c_, tws[k] = s_;
-    }
+    lds_load_real_frame(re, im, y, n, win, n_fft, log2n, (int64_t)frame * hop - n_fft / 2, tid);
+    lds_twiddles(twc, tws, n_fft, tid);
     __syncthreads();
     lds_fft_radix2(re, im, twc, tws, n_fft, log2n, tid);
-    for (int k = tid; k <= n_fft / 2; k += 256) {
+}
+
+__global__ __launch_bounds__(256) void stft_power_kernel(const float* __restrict__ y, int64_t n, const float* __restrict__ win,
+                                                         int n_fft, int log2n, int hop, float* __restrict__ p,
+                                                         int n_frames) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    stft_frame(sm, y, n, win, n_fft, log2n, hop);
+    const float *re = sm, *im = sm + n_fft;
+    const int frame = blockIdx.x;
+    for (int k = threadIdx.x; k <= n_fft / 2; k += 256) p[(int64_t)k * n_frames + frame] = re[k] * re[k] + im[k] * im[k];
+}
+
+__global__ __launch_bounds__(256) void stft_complex_kernel(const float* __restrict__ y, int64_t n, const float* __restrict__ win,
+                                                           int n_fft, int log2n, int hop, float* __restrict__ out_re,
+                                                           float* __restrict__ out_im, int n_frames) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    stft_frame(sm, y, n, win, n_fft, log2n, hop);
+    const float *re = sm, *im = sm + n_fft;
+    const int frame = blockIdx.x;
+    for (int k = threadIdx.x; k <= n_fft / 2; k += 256) {
         out_re[(int64_t)k * n_frames + frame] = re[k];
         out_im[(int64_t)k * n_frames + frame] = im[k];
     }
@@ -229,11 +208,7 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
         re[rev] = r;
         im[rev] = -i_;  // conj before the forward transform
     }
-    for (int k = tid; k < n_fft / 2; k += 256) {
-        float s_, c_;
-        sincospif(-2.0f * (float)k / (float)n_fft, &s_, &c_);
-        twc[k] = c_, tws[k] = s_;
-    }
+    lds_twiddles(twc, tws, n_fft, tid);
     __syncthreads();
     lds_fft_radix2(re, im, twc, tws, n_fft, log2n, tid);
     const float inv = 1.0f / (float)n_fft;
@@ -623,7 +598,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const double* __restrict_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int f = 0; f < RS_F; ++f) {
-        double v = acc[f];
+        double v = acc[f];  // (wave_sum of wave.h, spelled out: the call reschedules this kernel)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
         if (lane == 0) part[wave][f] = v;

@@ -10,12 +10,12 @@
 // cancellation on 1024^2 planes), pass 3 writes; passes 2 and 3 re-read the plane through L2.  HBM-bound: 4 B read + 4 B
 // written per element (+ the shared noise plane).
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __syncthreads();
     if (lane == 0) red[wave] = v;

@@ -8,6 +8,7 @@
 // wave64 butterfly shuffles.  The forward waits on these two launches before its first conv, so they are sized for
 // latency (832 small workgroups), not for bandwidth.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -15,12 +16,6 @@ constexpr int BCHUNK = 16;   // frames staged in LDS per pass
 constexpr int MAX_PER_LANE = 16;  // style_dim <= 1024 (checked by the launcher); cin <= 1024 of a demodulated entry (checked where the table is built: include/maua_hip.h)
 constexpr int ROWS = 16;          // output rows per workgroup
 constexpr int RPW = ROWS / 4;     // rows per wave
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void style_affine_kernel(const float* __restrict__ latents, int batch, int n_latent,
                                                            int style_dim, const float* __restrict__ trunc,
