@@ -63,26 +63,32 @@ def _tables(win, tempo_min, tempo_max, tempo_step, fr):
 
 # ------------------------------------------------------------------------------------------------ device stages
 def tempogram_peak(env, table, prior=None, want_tgram=False):
-    """(bin int32 [N], phase [N], power [N], tgram [N, B] or None) of a device envelope against a device table [B, W, 2]
-    (maua_tempogram_peak_f32)."""
-    env = env.float().contiguous()
-    table = table.float().contiguous()
-    n, (n_tempi, win, _) = env.numel(), table.shape
+    """(bin int32 [N], phase [N], power [N], tgram [N, B] or None) on the device of an envelope [N] against a table [B, W, 2] and an
+    optional prior [B], numpy arrays or tensors on any device (maua_tempogram_peak_f32)."""
+    shape = tuple(table.shape)
+    if len(shape) != 3 or shape[2] != 2:
+        raise ValueError(f"tempogram_peak: the table must be [tempi, window, 2] (got {shape})")
+    n_tempi, win, _ = shape
+    if prior is not None and int(np.prod(prior.shape)) != n_tempi:
+        raise ValueError(f"tempogram_peak: prior has {int(np.prod(prior.shape))} values for {n_tempi} tempi")
+    env, table = _sig._to_dev(env).reshape(-1), _sig._to_dev(table)
+    n = env.numel()
     bins = th.empty(n, dtype=th.int32, device=env.device)
     phase, power = th.empty(n, dtype=th.float32, device=env.device), th.empty(n, dtype=th.float32, device=env.device)
     tgram = th.empty((n, n_tempi), dtype=th.float32, device=env.device) if want_tgram else None
     if prior is not None:
-        prior = prior.float().contiguous()
-        if prior.numel() != n_tempi:
-            raise ValueError(f"prior: {prior.numel()} values for {n_tempi} tempi")
+        prior = _sig._to_dev(prior).reshape(-1)
     _lib.call("maua_tempogram_peak_f32", env, n, table, win, n_tempi, prior, bins, phase, power, tgram)
     return bins, phase, power, tgram
 
 
 def pulse_synth(bins, phase, window, omega):
-    """pulse [N] of device (bin, phase) [N], window [W] and omega [B] (maua_pulse_synth_f32)."""
-    bins, phase = bins.int().contiguous(), phase.float().contiguous()
-    window, omega = window.float().contiguous(), omega.float().contiguous()
+    """pulse [N] on the device of (bin, phase) [N], window [W] and omega [B], numpy arrays or tensors on any device
+    (maua_pulse_synth_f32)."""
+    if int(np.prod(bins.shape)) != int(np.prod(phase.shape)):
+        raise ValueError(f"pulse_synth: {int(np.prod(bins.shape))} bins for {int(np.prod(phase.shape))} phases, need one of each per frame")
+    bins, phase = _sig._to_dev(bins, th.int32).reshape(-1), _sig._to_dev(phase).reshape(-1)
+    window, omega = _sig._to_dev(window).reshape(-1), _sig._to_dev(omega).reshape(-1)
     n = bins.numel()
     out = th.empty(n, dtype=th.float32, device=bins.device)
     _lib.call("maua_pulse_synth_f32", bins, phase, n, window, window.numel(), omega, omega.numel(), out)

@@ -36,8 +36,20 @@ def _iterate(V, W, H, n_iter, update_w, update_h, eps):
 
 def nmf_divergence(V, W, H, eps=1e-12):
     """Generalised Kullback-Leibler divergence sum (V log(V / P) - V + P), P = max(W . H, eps), of device tensors as a 0-d float64
-    device tensor (maua_nmf_kl_div_f32: P in fp32 as the updates compute it, the terms and the sums in double).  Does not synchronise."""
-    F, T = V.shape
+    device tensor (maua_nmf_kl_div_f32: P in fp32 as the updates compute it, the terms and the sums in double).  ``V`` [F, T], ``W`` [F, K]
+    and ``H`` [K, T] are numpy arrays or tensors on any device; float32 contiguous tensors on the current device are used as they are,
+    and then nothing synchronises.  ValueError: shapes that do not agree, K outside 1 .. 32."""
+    shapes = tuple(tuple(x.shape) for x in (V, W, H))
+    if any(len(s) != 2 for s in shapes) or 0 in shapes[0]:
+        raise ValueError(f"nmf_divergence: V, W and H must be matrices [F, T], [F, K] and [K, T], V not empty (got {shapes})")
+    (F, T), K = shapes[0], shapes[1][1]
+    if shapes[1] != (F, K) or shapes[2] != (K, T):
+        raise ValueError(f"nmf_divergence: V {shapes[0]} needs W [{F}, K] and H [K, {T}] with one K (got {shapes[1]} and {shapes[2]})")
+    if not 1 <= K <= NMF_MAX_COMPONENTS:
+        raise ValueError(f"nmf_divergence: {K} components, need 1 .. {NMF_MAX_COMPONENTS}")
+    if F * T >= 2 ** 31:
+        raise ValueError(f"nmf_divergence: V has {F * T} elements, the device kernels index fewer than 2^31")
+    V, W, H = _signal._to_dev(V), _signal._to_dev(W), _signal._to_dev(H)
     cols = th.empty(T, dtype=th.float64, device=V.device)
     _lib.call("maua_nmf_kl_div_f32", V, W, H, F, T, W.shape[1], float(eps), cols)
     return cols.sum()

@@ -114,11 +114,11 @@ def sosfilt(sos, x, zi=None, chunk=None, dtype=th.float32, device=None):
     want64 = _out_dtype(dtype)
     zi_d = None
     if zi is not None:
+        if tuple(zi.shape) not in ((ns, 2), (F, ns, 2)):
+            raise ValueError(f"sosfilt: zi must be [{ns}, 2] or [{F}, {ns}, 2] (got {list(zi.shape)})")
         zi_d = _sig._to_dev(zi, th.float64)
         if zi_d.dim() == 2:
             zi_d = zi_d[None].expand(F, ns, 2).contiguous()
-        if tuple(zi_d.shape) != (F, ns, 2):
-            raise ValueError(f"sosfilt: zi must be [{ns}, 2] or [{F}, {ns}, 2] (got {list(zi_d.shape)})")
     y64, y32, zf = _run(sos, x, zi_d, chunk, want64, not want64, zi is not None)
     y = y64 if want64 else y32
     if squeeze:

@@ -364,9 +364,11 @@ def perlin_noise(shape, res, tileable=(True, False, False), interpolant=None, gr
         raise NotImplementedError("the HIP Perlin kernel implements the default quintic interpolant")
     if any(s % r for s, r in zip(shape, res)):
         raise ValueError("shape must be a multiple of res")
-    dev = th.device("cuda", th.cuda.current_device())
-    g = perlin_gradients(res, tileable) if gradients is None else np.asarray(gradients, dtype=np.float32)
-    gd = th.from_numpy(np.ascontiguousarray(g)).to(dev)
-    out = th.empty(tuple(shape), dtype=th.float32, device=dev)
+    g = perlin_gradients(res, tileable) if gradients is None else gradients if isinstance(gradients, th.Tensor) else np.asarray(gradients)
+    lattice = (res[0] + 1, res[1] + 1, res[2] + 1, 3)
+    if tuple(g.shape) != lattice:
+        raise ValueError(f"perlin_noise: res {tuple(res)} needs gradients of shape {lattice} (got {tuple(g.shape)})")
+    gd = _to_dev(g)
+    out = th.empty(tuple(shape), dtype=th.float32, device=gd.device)
     _lib.call("maua_perlin3d_f32", gd, out, shape[0], shape[1], shape[2], res[0], res[1], res[2])
     return out

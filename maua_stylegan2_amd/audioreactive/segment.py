@@ -175,8 +175,9 @@ def onset_envelope(audio, sr, n_mels=128):
 
 
 def tempogram(env, win):
-    """Mean autocorrelation tempogram tg[win] of a device onset envelope (maua_tempogram_f32)."""
-    env = env.float().contiguous()
+    """Mean autocorrelation tempogram tg[win] on the device of an onset envelope, a numpy array or a tensor on any device
+    (maua_tempogram_f32)."""
+    env = _sig._to_dev(env).reshape(-1)
     n = env.numel()
     ws = th.empty(_lib.load().maua_tempogram_ws_doubles(n, win), dtype=th.float64, device=env.device)
     tg = th.empty(win, dtype=th.float32, device=env.device)
@@ -185,8 +186,9 @@ def tempogram(env, win):
 
 
 def beat_dp(onset_norm, period):
-    """(localscore, cumscore, backlink) device tensors of the beat search over a normalised fp64 envelope (maua_beat_track_f64)."""
-    x = onset_norm.double().contiguous()
+    """(localscore, cumscore, backlink) device tensors of the beat search over a normalised envelope, a numpy array or a tensor on
+    any device, computed in float64 (maua_beat_track_f64)."""
+    x = _sig._to_dev(onset_norm, th.float64).reshape(-1)
     n = x.numel()
     ls, cs = th.empty_like(x), th.empty_like(x)
     bl = th.empty(n, dtype=th.int32, device=x.device)
@@ -215,18 +217,28 @@ def beat_track(env, sr, hop=HOP):
 
 
 def beat_sync(x, bounds, median):
-    """[rows, len(bounds) - 1] np.median (``median``) or mean of x[rows, n_frames] over the spans (maua_beat_sync_f32)."""
-    x = x.float().contiguous()
+    """[rows, len(bounds) - 1] np.median (``median``) or mean of x[rows, n_frames] over the spans (maua_beat_sync_f32), on the device.
+    ``x`` and ``bounds`` are numpy arrays or tensors on any device (``bounds`` a list too).  ValueError: an ``x`` that is not a matrix,
+    fewer than two bounds, a bound outside 0 .. n_frames."""
+    if len(x.shape) != 2:
+        raise ValueError(f"beat_sync: x must be [rows, n_frames] (got {tuple(x.shape)})")
     rows, n = x.shape
-    b = th.as_tensor(np.asarray(bounds, dtype=np.int32)).to(x.device)
+    edges = np.asarray(bounds.detach().cpu() if isinstance(bounds, th.Tensor) else bounds).reshape(-1)
+    if len(edges) < 2 or int(edges.min()) < 0 or int(edges.max()) > n:
+        raise ValueError(f"beat_sync: need at least two bounds inside 0 .. {n}, the frame count (got {edges.tolist()})")
+    x = _sig._to_dev(x)
+    b = _sig._to_dev(edges, th.int32)
     out = th.empty((rows, b.numel() - 1), dtype=th.float32, device=x.device)
     _lib.call("maua_beat_sync_f32", x, rows, n, b, b.numel() - 1, int(bool(median)), out)
     return out
 
 
 def knn_links(x, k, width=WIDTH):
-    """[S, S] links of the columns of x[D, S]: the distance where row i links column j, -1 elsewhere (maua_knn_links_f32)."""
-    x = x.float().contiguous()
+    """[S, S] links of the columns of x[D, S] (a numpy array or a tensor on any device): the distance where row i links column j, -1
+    elsewhere (maua_knn_links_f32)."""
+    if len(x.shape) != 2:
+        raise ValueError(f"knn_links: x must be [D, S] (got {tuple(x.shape)})")
+    x = _sig._to_dev(x)
     d, s = x.shape
     out = th.empty((s, s), dtype=th.float32, device=x.device)
     _lib.call("maua_knn_links_f32", x, d, s, int(k), int(width), out)
@@ -244,8 +256,11 @@ def link_bandwidth(links):
 
 
 def rec_affinity(links, bandwidth):
-    """(R, Rf): mutual-link affinity exp(-d / bandwidth) and its time-lag median filter (maua_rec_affinity_f32)."""
-    links = links.float().contiguous()
+    """(R, Rf): mutual-link affinity exp(-d / bandwidth) and its time-lag median filter (maua_rec_affinity_f32) of the [S, S] links
+    of :func:`knn_links`, a numpy array or a tensor on any device."""
+    if len(links.shape) != 2 or links.shape[0] != links.shape[1]:
+        raise ValueError(f"rec_affinity: links must be a square matrix [S, S] (got {tuple(links.shape)})")
+    links = _sig._to_dev(links)
     s = links.shape[0]
     rec, filt = th.empty_like(links), th.empty_like(links)
     _lib.call("maua_rec_affinity_f32", links, s, float(bandwidth), rec, filt)

@@ -139,8 +139,14 @@ def stft_power(audio, n_fft=2048, hop=512):
 
 
 def project(fb, p, to_db=False, amin=1e-10):
-    """fb [M,K] (numpy or tensor) @ p [K,N] on device, optional 10*log10(max(amin, .))."""
+    """fb [M,K] @ p [K,N] (each a numpy array or a tensor, any device) as float32 on the device, optional 10*log10(max(amin, .)).
+    ValueError: an operand that is not a matrix, a ``p`` whose rows are not the columns of ``fb``."""
+    if len(fb.shape) != 2 or len(p.shape) != 2:
+        raise ValueError(f"project: fb and p must be matrices [M, K] and [K, N] (got {tuple(fb.shape)} and {tuple(p.shape)})")
+    if fb.shape[1] != p.shape[0]:
+        raise ValueError(f"project: fb {tuple(fb.shape)} has {fb.shape[1]} columns, p {tuple(p.shape)} has {p.shape[0]} rows")
     fbt = _const_dev(fb, np.float32) if isinstance(fb, np.ndarray) else _to_dev(fb)
+    p = _to_dev(p)
     m, k = fbt.shape
     n = p.shape[1]
     out = th.empty((m, n), dtype=th.float32, device=p.device)
