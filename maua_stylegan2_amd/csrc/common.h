@@ -44,7 +44,7 @@ static inline bool fits_raw_descriptor(int64_t bytes) { return bytes <= 0x7fffff
 // Name of the kernel template instance that the last convolution launch of this process ran, as rocprofv3 prints it
 // (maua_modconv_last_instance): bench.py, tools/microbench.py and the tables under profiles/ join on it.  A launch that is followed by
 // helper kernels (edge lines, seam pass, reducers) keeps its main kernel's name.  (The generic kernel's names come from its instance
-// table, modconv.hip kConvInstances, which maua_modconv_plan_instance answers from without launching.)
+// tables, modconv_m0.hip .. modconv_m4.hip kConvInstances, which maua_modconv_plan_instance answers from without launching.)
 inline char g_conv_instance[96] = "";
 
 // THE launch of a convolution kernel instance (256 threads, dynamic LDS beyond the default 64 KB allowed): attribute, name, launch,

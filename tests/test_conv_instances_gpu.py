@@ -1,4 +1,4 @@
-"""GPU: every instance of modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP> (csrc/modconv.hip) a call can reach, launched through
+"""GPU: every instance of modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP> (csrc/modconv_kernel.h, instantiated by csrc/modconv_m0.hip .. modconv_m4.hip) a call can reach, launched through
 the C ABI at the smallest shape that reaches it, between red zones, against the fp64 direct convolution with a per-element bound.
 
 The rows come from tests/golden/conv_instances.json, which tools/conv_instance_sweep.py writes on the CPU: it walks a grid of small shapes

@@ -15,7 +15,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 SOURCES = ("modconv_w2d", "modconv_up2d")
 STREAMING = ("upfirdn2d",)  # HBM-bound kernels: no LDS-DMA, but a spill or a scratch array there is HBM traffic the roofline does not count
-GENERIC = ("modconv",)  # the generic convolution kernel: which instances the product build holds, and that the FAST ones do not spill
+# the generic convolution kernel, one unit per mode: which instances the product build holds, and that the FAST ones do not spill
+GENERIC = ("modconv_m0", "modconv_m1", "modconv_m2", "modconv_m3", "modconv_m4")
 SIDE = ("modconv_sbf16",)  # the split-bf16 side measurement: only which kernels the product build holds
 
 
@@ -87,9 +88,9 @@ def test_hot_kernels_use_no_scratch_memory(device_asm, name):
 
 
 def test_generic_conv_kernel_compiled_set_is_the_instance_table(device_asm):
-    """csrc/modconv.hip instantiates modconv_mfma_kernel from one table (MAUA_CONV_ROWS); the product build must hold exactly the 58
-    instances of tests/golden/conv_instances.json — the ones the plan can reach (tests/test_conv_instances_host.py enumerates it) and
-    the GPU test launches — so no kernel is compiled that no call runs, and none is tested that is not compiled.  The FAST instances
+    """csrc/modconv_m0.hip .. modconv_m4.hip instantiate modconv_mfma_kernel (csrc/modconv_kernel.h), each from the table of its mode
+    (MAUA_CONV_ROWS); together, and each in exactly one unit, the product build must hold exactly the 58 instances of
+    tests/golden/conv_instances.json — the ones the plan can reach (tests/test_conv_instances_host.py enumerates it) and the GPU test launches — so no kernel is compiled that no call runs, and none is tested that is not compiled.  The FAST instances
     (channel counts in whole K chunks and weight tiles: every layer of a real generator) keep everything in registers; the ragged-channel
     instances carry 12 .. 196 bytes of scratch for their masked loads and are not held to that."""
     table = json.load(open(os.path.join(REPO, "tests", "golden", "conv_instances.json")))["instances"]
@@ -99,9 +100,13 @@ def test_generic_conv_kernel_compiled_set_is_the_instance_table(device_asm):
         bm, bn, wm, mode, multi, fast, maxp = mangled.search(symbol).groups()
         return f"modconv_mfma_kernel<{bm}, {bn}, {wm}, {mode}, {('false', 'true')[int(multi)]}, {('false', 'true')[int(fast)]}, {maxp}>"
 
-    spills = _per_kernel(device_asm["modconv"], "vgpr_spill_count")
-    scratch = _per_kernel(device_asm["modconv"], "private_segment_fixed_size")
-    symbols = [k for k in spills if "modconv_mfma_kernel" in k]
+    spills, scratch, symbols = {}, {}, []
+    for unit in GENERIC:
+        unit_spills = _per_kernel(device_asm[unit], "vgpr_spill_count")
+        symbols += [k for k in unit_spills if "modconv_mfma_kernel" in k]
+        spills.update(unit_spills)
+        scratch.update(_per_kernel(device_asm[unit], "private_segment_fixed_size"))
+    assert len(set(symbols)) == len(symbols), "an instance is compiled in two units"
     assert sorted(demangled(k) for k in symbols) == sorted(r["name"] for r in table) and len(symbols) == 58
     fast = [k for k in symbols if mangled.search(k).group(6) == "1"]
     assert len(fast) == 29

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Which instances of modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP> (csrc/modconv.hip) can a call reach, and by which
+"""Which instances of modconv_mfma_kernel<BM, BN, WM, MODE, MULTI, FAST, MAXP> (csrc/modconv_kernel.h, instantiated by csrc/modconv_m0.hip .. modconv_m4.hip) can a call reach, and by which
 smallest shape?  -> tests/golden/conv_instances.json, the table tests/test_conv_instances_gpu.py and tests/test_conv_instances_host.py
 are parametrised over.
 

@@ -2,8 +2,8 @@
 """Static per-source-line issue-cycle profile of one kernel instantiation (no GPU needed).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -gline-tables-only -S --cuda-device-only -Iinclude \\
-          maua_stylegan2_amd/csrc/modconv.hip -o /tmp/modconv_g.s
-    python tools/isa_lines.py /tmp/modconv_g.s maua_stylegan2_amd/csrc/modconv.hip 'ILi32ELi128ELi1ELi3ELb0ELb1ELi3E' [top]
+          maua_stylegan2_amd/csrc/modconv_m3.hip -o /tmp/modconv_g.s     # the unit of the instance's mode
+    python tools/isa_lines.py /tmp/modconv_g.s maua_stylegan2_amd/csrc/modconv_kernel.h 'ILi32ELi128ELi1ELi3ELb0ELb1ELi3E' [top]
 
 Every VALU instruction of the kernel counts 4 issue cycles, every SALU 1 (the issue model of profiles/r01_pmc_modconv.md),
 attributed to the source line of its .loc; MFMAs are listed separately (64 cycles each).  Instructions are split by PROGRAM

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Static instruction mix of the hottest loop of every modconv_mfma_kernel instantiation, from the device assembly:
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -Iinclude maua_stylegan2_amd/csrc/modconv.hip -o /tmp/modconv.s
+    for m in 0 1 2 3 4; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -Iinclude \
+        maua_stylegan2_amd/csrc/modconv_m$m.hip -o /tmp/modconv_m$m.s; done     # one unit per kernel mode
+    cat /tmp/modconv_m?.s > /tmp/modconv.s                                        # (or pass one mode's file)
     python tools/isa_mix.py /tmp/modconv.s [--all] > profiles/rNN_isa_modconv.md
 
 For each kernel: VGPR count / spills from the metadata, and for the loop (backward branch range) that contains the most
