@@ -459,6 +459,35 @@ int maua_jpeg_encode_u8(const uint8_t* rgb, int batch, int h, int w, int quality
  * 16-byte boundary takes the 16-byte vector path, everything else goes byte by byte.  (Additive: the ABI version is unchanged.) */
 int maua_temporal_fold_u8(const uint8_t* in, uint8_t* out, int groups, int subframes, int64_t frame_bytes, const uint8_t* weights,
                           const uint16_t* decode, const uint16_t* encode_threshold, void* stream);
+/* Deep frame delivery (csrc/deep_frames.hip): 16-bit packed RGB and 10-bit planar YUV from the fp32 image.  (Additive: the ABI version
+ * is unchanged.)
+ *   maua_frames_to_u16  [B,3,H,W] fp32 -> [B,H,W,3] uint16 (ffmpeg's rgb48le), the 8-bit quantiser with the scale changed: bit for bit the
+ *                       fp32 statement ((clip(x, -1, 1) + 1) * 32767.5).astype(uint16), a truncating cast; the add and the multiply are
+ *                       never contracted.  NaN gives 0, -inf 0, +inf 65535, 1 gives 65535.  Arguments as maua_frames_to_u8 (batch <= 0 is
+ *                       MAUA_EINVAL); plane % 4 == 0 with img 16-byte and out 8-byte aligned takes the vector path.
+ *   maua_crop_resize_u16  maua_crop_resize_u8 on uint16 frames: the same taps, clamping and coefficients rounded to 22 fractional bits,
+ *                       64-bit products, the horizontal pass rounded half up to 16 bits, then the vertical pass on that, clamped to
+ *                       0 .. 65535.  MAUA_ENOSYS for a down-scale; MAUA_EINVAL as the 8-bit entry.
+ *   maua_rgb48_to_yuv_p10  rgb[B,h,w,3] uint16 -> planar out[B, frame] uint16 with a 10-bit value in the low bits: per frame the Y plane
+ *                       [h, w], then U, then V, each [h/2, w/2] for subsampling 420, [h, w/2] for 422, [h, w] for 444 (ffmpeg's
+ *                       yuv420p10le / yuv422p10le / yuv444p10le).  ITU-R BT.709 limited range, the exact rational value for Kr = 0.2126,
+ *                       Kg = 0.7152, Kb = 0.0722 rounded half up, in 64-bit integers (`/` is floor).  For a block of n pixels whose codes
+ *                       sum to Sr, Sg, Sb (n = 1 for Y; chroma from the box sum of the 2 x 2, 2 x 1 or 1 x 1 block: centre siting):
+ *                         L  = 2126 Sr + 7152 Sg + 722 Sb
+ *                         Y  = 64 + (2 * 876 * L + D) / (2 D)                       D  = 10000 * 65535
+ *                         Cb = (2 * (512 Eb + 896 * (10000 Sb - L)) + Eb) / (2 Eb)  Eb = 2 * 9278 * 65535 * n
+ *                         Cr = (2 * (512 Er + 896 * (10000 Sr - L)) + Er) / (2 Er)  Er = 2 * 7874 * 65535 * n
+ *                       MAUA_EINVAL for another subsampling, non-positive h or w, batch < 0, odd w (420, 422) or odd h (420), a NULL
+ *                       buffer; batch == 0 is a successful no-op; more than 65535 frames a launch are MAUA_ENOSYS.  Any legal width and
+ *                       alignment is served; w % 8 == 0 with 16-byte aligned buffers takes the vector path.
+ *   maua_frames_to_yuv_p10_f32  img[B,3,h,w] fp32 -> the same planar frame in one launch: maua_rgb48_to_yuv_p10 applied to
+ *                       maua_frames_to_u16, bit for bit, the 16-bit codes kept in registers.  Arguments and refusals as
+ *                       maua_rgb48_to_yuv_p10; w % 4 == 0 with img 16-byte and out 8-byte aligned takes the vector path. */
+int maua_frames_to_u16(const float* img, uint16_t* out, int batch, int h, int w, void* stream);
+int maua_crop_resize_u16(const uint16_t* in, uint16_t* out, int batch, int in_h, int in_w, int x0, int y0, int crop_w, int crop_h,
+                         int out_w, int out_h, void* stream);
+int maua_rgb48_to_yuv_p10(const uint16_t* rgb, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
+int maua_frames_to_yuv_p10_f32(const float* img, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ audio / temporal
  * Circular Gaussian FIR along time (audioreactive/signal.py:319-368): x [T, F] -> y [T, F], taps[2*radius+1]

@@ -132,6 +132,10 @@ _SIGNATURES = {
     "maua_jpeg_ws_bytes": (c_int64, [c_int] * 4),
     "maua_jpeg_encode_u8": (c_int, [_P] + [c_int] * 5 + [_P, c_int, _P, c_int64, _P, _P]),
     "maua_temporal_fold_u8": (c_int, [_P, _P, c_int, c_int, c_int64, _P, _P, _P, _P]),
+    "maua_frames_to_u16": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "maua_crop_resize_u16": (c_int, [_P, _P] + [c_int] * 9 + [_P]),
+    "maua_rgb48_to_yuv_p10": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "maua_frames_to_yuv_p10_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "maua_sg1_epilogue_f32": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "maua_temporal_fir_f32": (c_int, [_P, _P, _P, c_int, c_int64, c_int, _P]),
     "maua_stft_power_f32": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P]),

@@ -64,7 +64,8 @@ CLI_FLAGS = (
     ("--output_file", dict(type=str, default=None)),
     # (not one of the reference's: what travels to the encoder — planar 4:2:0 is made on the device, render.frames_to_yuv420p)
     # ... or one baseline JPEG per frame, render.frames_to_mjpeg, at --mjpeg_quality 1 .. 95)
-    ("--pipe_pix_fmt", dict(type=str, default="rgb24", choices=render.PIPE_PIX_FMTS)),
+    # ... or a deep format, render.frames_to_deep: 16-bit RGB / 10-bit BT.709 YUV from the fp32 image, encoded as HEVC Main10)
+    ("--pipe_pix_fmt", dict(type=str, default="rgb24", choices=render.PIPE_PIX_FMTS + render.DEEP_PIX_FMTS)),
     ("--mjpeg_quality", dict(type=int, default=render.MJPEG_DEFAULT_QUALITY)),
     # (temporal supersampling, render.TemporalFold: --fps F --subframes N is --fps F * N up to and including synthesis; the frames are then
     # folded N:1 on the device and written at F)

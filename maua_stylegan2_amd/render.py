@@ -23,6 +23,9 @@ Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to plan
 they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
 Opt-in pipe format ``mjpeg`` (``mjpeg:<quality>``): every frame is encoded as one baseline JPEG on the device (frames_to_mjpeg) and travels
 in a fixed-size slot; the sink writes the streams alone, to ``ffmpeg -f mjpeg`` or, without a binary, to a playable Motion-JPEG .avi (avi.py).
+Opt-in deep pipe formats (DEEP_PIX_FMTS: ``rgb48le``, ``yuv420p10le``, ``yuv422p10le``, ``yuv444p10le``): the lanes keep the fp32 image and
+frames_to_deep turns it into 16-bit packed RGB or 10-bit planar BT.709 YUV on the device, so no 8-bit quantiser sits between the generator
+and the encoder (libx265, 10 bits); the frames travel as flat bytes like the yuv420p ones.  Not combinable with a temporal fold.
 Opt-in temporal supersampling (TemporalFold, ``render_folded``; $MAUA_SUBFRAMES for the pinned entries): N rendered sub-frames per delivered
 frame, averaged on the device by fold_frames before any of the above; the sink and the transports then count delivered frames.
 """
@@ -68,6 +71,16 @@ PIPE_PIX_FMTS = ("rgb24", "yuv420p", "mjpeg")
 MJPEG_DEFAULT_QUALITY = 90
 # how a yuv420p pipe is tagged: the matrix / range csrc/yuv420.hip converts with (BT.601 limited range), so that players decode with it
 YUV420P_TAGS = ["-colorspace", "smpte170m", "-color_primaries", "smpte170m", "-color_trc", "smpte170m", "-color_range", "tv"]
+# the deep pipe formats: the fp32 image leaves the device at 16 bits per sample (packed RGB) or as planar 10-bit YUV (csrc/deep_frames.hip),
+# never through the 8-bit quantiser; encoded as HEVC Main10.  The YUV ones carry the matrix / range of that conversion (BT.709 limited range)
+DEEP_PIX_FMTS = ("rgb48le", "yuv420p10le", "yuv422p10le", "yuv444p10le")
+DEEP_SUBSAMPLING = {"yuv420p10le": 420, "yuv422p10le": 422, "yuv444p10le": 444}
+YUV_P10_TAGS = ["-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc", "bt709", "-color_range", "tv"]
+
+
+def deep_frame_bytes(pix_fmt, width, height):
+    """Bytes of one ``width`` x ``height`` frame of a deep pipe format: 6 per pixel for rgb48le and 4:4:4, 4 for 4:2:2, 3 for 4:2:0."""
+    return width * height * {"rgb48le": 6, "yuv444p10le": 6, "yuv422p10le": 4, "yuv420p10le": 3}[pix_fmt]
 
 
 def _pipe_pix_fmt(pix_fmt):
@@ -75,8 +88,8 @@ def _pipe_pix_fmt(pix_fmt):
     (_mjpeg_quality reads it): the bare name is returned."""
     pix_fmt = pix_fmt or os.environ.get("MAUA_PIPE_PIX_FMT") or "rgb24"
     name = "mjpeg" if pix_fmt.startswith("mjpeg:") else pix_fmt
-    if name not in PIPE_PIX_FMTS:
-        raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
+    if name not in PIPE_PIX_FMTS + DEEP_PIX_FMTS:
+        raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS + DEEP_PIX_FMTS)})")
     return name
 
 
@@ -104,14 +117,15 @@ class FrameSink:
     """Ordered consumer of uint8 [H, W, 3] frames (``pix_fmt="rgb24"``) or of flat planar I420 frames [H * W * 3 / 2]
     (``pix_fmt="yuv420p"``: converted, and for wide outputs resized, on the device — frames_to_yuv420p), or of flat mjpeg slots
     [mjpeg_slot_bytes] (``pix_fmt="mjpeg"``: one JPEG per frame behind a 16-byte slot header — frames_to_mjpeg; ``quality`` is only quoted
-    in the error an overflowed slot raises)."""
+    in the error an overflowed slot raises), or of flat deep frames [deep_frame_bytes] (``pix_fmt`` in DEEP_PIX_FMTS: 16-bit little-endian
+    samples as bytes — frames_to_deep; encoded with libx265 at 10 bits)."""
 
     def __init__(self, output_file, width, height, framerate, audio_file=None, offset=0, duration=None,
                  ffmpeg_preset="slow", pix_fmt="rgb24", quality=None):
-        if pix_fmt not in PIPE_PIX_FMTS:
-            raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS)})")
-        if pix_fmt == "yuv420p" and (width % 2 or height % 2):
-            raise ValueError(f"yuv420p needs even dimensions, got {width}x{height}")
+        if pix_fmt not in PIPE_PIX_FMTS + DEEP_PIX_FMTS:
+            raise ValueError(f"unknown pipe pixel format {pix_fmt!r} ({' | '.join(PIPE_PIX_FMTS + DEEP_PIX_FMTS)})")
+        if (pix_fmt == "yuv420p" or pix_fmt in DEEP_PIX_FMTS) and (width % 2 or height % 2):
+            raise ValueError(f"{pix_fmt} needs even dimensions, got {width}x{height}")
         self.w, self.h = width, height
         self.pix_fmt = pix_fmt
         self.quality = quality
@@ -137,7 +151,10 @@ class FrameSink:
                        f"{framerate}", "-s", f"{width}x{height}", "-i", "pipe:"]
             if audio_file is not None:
                 cmd += ["-ss", f"{offset}", "-t", f"{duration}", "-guess_layout_max", "0", "-i", audio_file]
-            cmd += ["-r", f"{framerate}", "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-preset", ffmpeg_preset]
+            if pix_fmt in DEEP_PIX_FMTS:
+                cmd += ["-r", f"{framerate}"] + self._deep_codec_args(pix_fmt, ffmpeg_preset)
+            else:
+                cmd += ["-r", f"{framerate}", "-vcodec", "libx264", "-pix_fmt", "yuv420p", "-preset", ffmpeg_preset]
             if pix_fmt == "yuv420p":
                 cmd += YUV420P_TAGS
             if audio_file is not None:
@@ -150,11 +167,22 @@ class FrameSink:
             audio = f" -ss {offset} -t {duration} -guess_layout_max 0 -i {audio_file}" if audio_file is not None else ""
             mux = " -b:a 320K -ac 2" if audio_file is not None else ""
             tags = " " + " ".join(YUV420P_TAGS) if pix_fmt == "yuv420p" else ""
+            codec = f"-vcodec libx264 -pix_fmt yuv420p -preset {ffmpeg_preset}"
+            if pix_fmt in DEEP_PIX_FMTS:
+                codec = " ".join(self._deep_codec_args(pix_fmt, ffmpeg_preset))
             target = output_file[:-len(ext)] if output_file.endswith(ext) else output_file
             print(f"ffmpeg binary not found: writing raw {pix_fmt} frames ({width}x{height}) to {path}\n"
                   f"  encode later with: ffmpeg -f rawvideo -pix_fmt {pix_fmt} -framerate {framerate} -s {width}x{height} -i {path}{audio} "
-                  f"-r {framerate} -vcodec libx264 -pix_fmt yuv420p -preset {ffmpeg_preset}{tags}{mux} {target}")
+                  f"-r {framerate} {codec}{tags}{mux} {target}")
             self.file = open(path, "wb")
+
+    @staticmethod
+    def _deep_codec_args(pix_fmt, ffmpeg_preset):
+        """Output side of a deep pipe: HEVC at 10 bits (rgb48le is converted to 4:2:0 by ffmpeg itself and stays untagged, as rgb24 does: a
+        tag would claim a matrix this side does not control; the YUV formats carry the matrix the device converted with)."""
+        out_fmt = "yuv420p10le" if pix_fmt == "rgb48le" else pix_fmt
+        args = ["-vcodec", "libx265", "-pix_fmt", out_fmt, "-tag:v", "hvc1", "-preset", ffmpeg_preset]
+        return args + (YUV_P10_TAGS if pix_fmt != "rgb48le" else [])
 
     def write(self, frame):
         """frame: numpy uint8 [H, W, 3]; wide 2048-px outputs are cropped + resized as render.py:98-105.  A yuv420p sink takes the flat
@@ -172,6 +200,15 @@ class FrameSink:
                                  f"(quality {self.quality if self.quality is not None else 'unknown'}: lower it)")
             if self.proc is not None or self.file is not None:
                 (self.proc.stdin if self.proc is not None else self.file).write(memoryview(frame[16: 16 + n]).cast("B"))
+            self.count += 1
+            return
+        if self.pix_fmt in DEEP_PIX_FMTS:
+            n_bytes = deep_frame_bytes(self.pix_fmt, self.w, self.h)
+            if frame.ndim != 1 or frame.shape[0] != n_bytes or frame.dtype != np.uint8:
+                raise ValueError(f"a {self.pix_fmt} frame of {self.w}x{self.h} is a flat uint8 array of {n_bytes} bytes, got {frame.dtype} "
+                                 f"{tuple(frame.shape)}")
+            if self.proc is not None or self.file is not None:
+                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(np.ascontiguousarray(frame)).cast("B"))
             self.count += 1
             return
         if self.pix_fmt == "yuv420p":
@@ -360,6 +397,62 @@ def frames_to_mjpeg(u8, scratch, quality):
         _lib.check(lib.maua_jpeg_encode_u8(u8.data_ptr(), b, h, w, quality, restart_mcus, header.data_ptr(), header.numel(), out.data_ptr(),
                                            slot_bytes, ws.data_ptr(), _lib.stream_ptr(u8.device)), "maua_jpeg_encode_u8")
     return out
+
+
+def _deep_scratch(scratch, key, shape, dev):
+    """The reusable int16 buffer (uint16 bits) of one deep stage, keyed by the stage's input buffer: the protocol of crop_resize_for_delivery."""
+    out = scratch.get(key)
+    if out is None:
+        out = scratch[key] = th.empty(shape, dtype=th.int16, device=dev)
+    return out
+
+
+def frames_to_deep(images, out_size, pix_fmt, scratch):
+    """fp32 [b, 3, H, W] device images (the generator's output, before any quantiser) -> the frames of a deep pipe format (DEEP_PIX_FMTS) as
+    flat bytes, uint8 [b, deep_frame_bytes], on the current (= producing) stream (csrc/deep_frames.hip states the arithmetic):
+      no resize, a YUV format   maua_frames_to_yuv_p10_f32: one launch, the 16-bit codes never leave the registers
+      no resize, rgb48le        maua_frames_to_u16
+      2048-px wide outputs      maua_frames_to_u16, maua_crop_resize_u16 to 1920x1080 / 1080x1920 (the crop of crop_resize_for_delivery), then
+                                maua_rgb48_to_yuv_p10 for a YUV format
+    ``scratch``: dict holding the reusable buffers, keyed by the input buffer (the lanes' batches are in flight concurrently)."""
+    if pix_fmt not in DEEP_PIX_FMTS:
+        raise ValueError(f"{pix_fmt!r} is not a deep pipe format ({' | '.join(DEEP_PIX_FMTS)})")
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda:
+        raise RuntimeError(f"frames_to_deep takes fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    b, _, h, w = images.shape
+    if h % 2 or w % 2:
+        raise ValueError(f"{pix_fmt} needs even frame dimensions, got {w}x{h}")
+    images = images.contiguous()
+    lib, dev, sub = _lib.load(), images.device, DEEP_SUBSAMPLING.get(pix_fmt)
+    box = None
+    if out_size == 1920 and w == 2048:
+        box = (112, 0, w - 224, h, 1920, 1080)
+    elif out_size == 1080 and h == 2048:
+        box = (0, 112, w, h - 224, 1080, 1920)
+    if box is not None and (box[4] < box[2] or box[5] < box[3]):
+        raise ValueError(f"{pix_fmt}: a {w}x{h} frame cannot be delivered at --out_size {out_size}: the device resize only up-scales")
+    ptr = images.data_ptr()
+    with th.cuda.device(dev):
+        st = _lib.stream_ptr(dev)
+        if b == 0:
+            oh, ow = (box[5], box[4]) if box is not None else (h, w)
+            return th.empty((0, deep_frame_bytes(pix_fmt, ow, oh)), dtype=th.uint8, device=dev)
+        if box is None and sub is not None:
+            out = _deep_scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), dev)
+            _lib.check(lib.maua_frames_to_yuv_p10_f32(ptr, out.data_ptr(), b, h, w, sub, st), "maua_frames_to_yuv_p10_f32")
+            return out.view(th.uint8)
+        master = _deep_scratch(scratch, ("deep-u16", ptr, b, h, w), (b, h, w, 3), dev)
+        _lib.check(lib.maua_frames_to_u16(ptr, master.data_ptr(), b, h, w, st), "maua_frames_to_u16")
+        if box is not None:
+            x0, y0, cw, ch, ow, oh = box
+            resized = _deep_scratch(scratch, ("deep-resize", ptr, b, oh, ow), (b, oh, ow, 3), dev)
+            _lib.check(lib.maua_crop_resize_u16(master.data_ptr(), resized.data_ptr(), b, h, w, x0, y0, cw, ch, ow, oh, st), "maua_crop_resize_u16")
+            master, h, w = resized, oh, ow
+        if sub is None:
+            return master.view(b, h * w * 3).view(th.uint8)
+        out = _deep_scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), dev)
+        _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, h, w, sub, st), "maua_rgb48_to_yuv_p10")
+        return out.view(th.uint8)
 
 
 MAX_SUBFRAMES = 16
@@ -568,8 +661,9 @@ def _lane_is_stale(lane, weights_key, slots, seed, offset, synth_slots, synth_of
     return bool(synth_slots) and lane.synth_frame_offset != synth_offset
 
 
-def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=None):
-    """``n_lanes`` captured forwards (GraphLane) of ``batch_size`` frames with uint8 frame output, each on its own stream.
+def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=None, frames="u8"):
+    """``n_lanes`` captured forwards (GraphLane) of ``batch_size`` frames with uint8 frame output (``frames="f32"``: with the fp32 image
+    [b, 3, H, W] as the output, no quantiser in the graph; cached next to the uint8 lanes), each on its own stream.
     Without bends they are cached on the generator and reused by every later render (a captured forward reads its inputs
     through a frame source, so nothing about a particular render is baked in); a changed weight drops the cache.  With bends the
     transforms' static operands are part of the graph: captured per call.  ``random`` = (slots, seed, frame offset): lanes that generate
@@ -592,14 +686,18 @@ def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=Non
     cache = generator.__dict__.setdefault("_graph_lanes", {})
     lanes = []
     tap = bool(getattr(generator, "tap_float_image", False))  # (parity tests: such lanes also write the fp32 image — other kernels arguments)
+    if frames not in ("u8", "f32"):
+        raise ValueError(f"unknown frame kind {frames!r} (u8 | f32)")
     for k in range(n_lanes):
         stream = _lane_stream(dev, k)
         cache_key = (batch_size, k, tap) + ((slots,) if slots else ()) + ((("synth",) + synth_slots,) if synth_slots else ())
+        if frames != "u8":  # (the uint8 lanes keep the key they always had)
+            cache_key += (("frames", frames),)
         lane = None if bends else cache.get(cache_key)
         if lane is None or _lane_is_stale(lane, key, slots, seed, offset, synth_slots, synth_offset):
             stream.wait_stream(th.cuda.current_stream(dev))
             with th.cuda.stream(stream):
-                lane = generator.capture_graph(batch_size, lane=k, frames_u8=True, bends=bends, **extra)
+                lane = generator.capture_graph(batch_size, lane=k, frames_u8=frames == "u8", bends=bends, **extra)
             stream.synchronize()
             if not bends:
                 cache[cache_key] = lane
@@ -723,9 +821,10 @@ def _set_parameter(generator, dotted_name, tensor):
     setattr(module, leaf, th.nn.Parameter(tensor, requires_grad=False))
 
 
-def _eager_batch(generator, plan, n, m, stream, lane_streams, out):
+def _eager_batch(generator, plan, n, m, stream, lane_streams, out, frames="u8"):
     """Frames [n, m) by one eager forward on ``stream`` (the current one): every batch of a render that is not capturable, the ragged tail
-    batch of one that is.  ``lane_streams``: the captured lanes' streams, drained first.  Returns the uint8 frames, in ``out`` when it fits."""
+    batch of one that is.  ``lane_streams``: the captured lanes' streams, drained first.  Returns the uint8 frames, in ``out`` when it fits;
+    ``frames="f32"``: the generator's fp32 image [b, 3, H, W] as it is."""
     b = m - n
     noise_batch = [None if nz is None or isinstance(nz, NoiseSynth) else (nz if nz.shape[0] == 1 else nz[n:m]) for nz in plan.noise]  # [1, ...] = one map for every frame
     for i, recipe in plan.recipes.items():  # the launch a graph lane makes for these frames, without a frame source
@@ -746,26 +845,32 @@ def _eager_batch(generator, plan, n, m, stream, lane_streams, out):
     images, _ = generator(styles=plan.latents[n:m], noise=noise_batch,
                           truncation=plan.truncation if plan.trunc_t is None else plan.trunc_t[n:m],
                           transform_dict_list=bend_batch, randomize_noise=plan.randomize_noise, input_is_latent=True)
+    if frames == "f32":
+        return images
     if out is None or out.shape[0] != b or out.shape[1:3] != images.shape[2:]:
         out = th.empty((b, images.shape[2], images.shape[3], 3), dtype=th.uint8, device=plan.dev)
     return frames_to_uint8(images, out)
 
 
 def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), rewrites=None, randomize_noise=False,
-               use_graph=True, frame_range=None, lanes=3):
+               use_graph=True, frame_range=None, lanes=3, frames="u8"):
     """Generator -> uint8 frames for ``frame_range`` (default: all) of the sequence.  Yields (first_frame_index,
     uint8 device tensor [b, H, W, 3]) per batch, in order, with the producing stream current; the tensor stays valid
-    until ``lanes`` further batches have been requested.
+    until ``lanes`` further batches have been requested.  ``frames="f32"``: the fp32 image [b, 3, H, W] (values nominally in [-1, 1], not
+    clamped) instead of the quantised frames — what the deep pipe formats are made from (frames_to_deep).
 
     hipGraph path: ``lanes`` graphs of ``batch_size`` frames (same weights, private activations) are replayed round-robin
     on their own streams, so consecutive batches overlap on the device — the small, latency-bound 4^2..32^2 layers and
     the last partial wave of every big launch of one batch run underneath the other batch's MFMA-bound layers.  The
     sequences (latents, noise maps, truncation, bend modulations) stay resident in HBM; a replay moves one frame index."""
+    if frames not in ("u8", "f32"):
+        raise ValueError(f"unknown frame kind {frames!r} (u8 | f32)")
     plan = _plan_render(generator, latents, noise, truncation, bends, rewrites, randomize_noise, use_graph, frame_range)
     caller_stream = th.cuda.current_stream(plan.dev)
     full_batches = (plan.hi - plan.lo) // batch_size
     if plan.capturable and full_batches >= 1:
-        lane_state = graph_lanes(generator, batch_size, min(max(1, int(lanes)), full_batches), plan.seq_bends, plan.random, plan.synth)
+        lane_state = graph_lanes(generator, batch_size, min(max(1, int(lanes)), full_batches), plan.seq_bends, plan.random, plan.synth,
+                                 **({} if frames == "u8" else {"frames": frames}))
         for stream, lane in lane_state:
             lane.bind(plan.latents, plan.noise, plan.trunc_t)  # once per render: the pointers of the HBM-resident sequences
             stream.wait_stream(caller_stream)
@@ -781,10 +886,13 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
             with th.cuda.stream(stream):
                 if lane is not None and m - n == batch_size:
                     lane.replay(n)
-                    yield n, lane.u8  # the frame epilogue is part of the captured forward (fused into the last ToRGB)
-                else:
+                    # (u8: the frame epilogue is part of the captured forward, fused into the last ToRGB)
+                    yield n, lane.u8 if frames == "u8" else lane.image
+                elif frames == "u8":
                     eager_u8 = _eager_batch(generator, plan, n, m, stream, captured_streams, eager_u8)
                     yield n, eager_u8
+                else:
+                    yield n, _eager_batch(generator, plan, n, m, stream, captured_streams, None, frames)
     finally:  # also when the consumer stops early (sink error, generator closed)
         for name, weight in plan.original_weights.items():  # leave the generator as it was found
             _set_parameter(generator, name, weight)
@@ -942,7 +1050,8 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
     """``render`` with an optional ``_shard = (lo, hi, n_frames)``: set by generate() after sharding.scatter_frames, it says
     that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames.
-    ``pipe_pix_fmt``: "rgb24", "yuv420p", "mjpeg" or "mjpeg:<quality>" (PIPE_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24) — what
+    ``pipe_pix_fmt``: "rgb24", "yuv420p", "mjpeg" or "mjpeg:<quality>" (PIPE_PIX_FMTS) or a deep format (DEEP_PIX_FMTS: 16-bit RGB / 10-bit
+    YUV made from the fp32 image; refused together with a temporal fold, which is 8-bit only); default $MAUA_PIPE_PIX_FMT, else rgb24 — what
     crosses to the host, to rank 0 and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the
     environment variable.  This parameter list is pinned as well: a temporal fold comes from $MAUA_SUBFRAMES, $MAUA_SHUTTER and
     $MAUA_SHUTTER_LIGHT (_fold_from_env; unset: none) — ``render_folded`` takes it as an argument."""
@@ -977,6 +1086,12 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                          f"(e.g. --batch {subframes * max(1, round(batch_size / subframes))})")
     quality = _mjpeg_quality(pipe_pix_fmt) if _pipe_pix_fmt(pipe_pix_fmt) == "mjpeg" else None
     pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
+    deep = pipe_pix_fmt in DEEP_PIX_FMTS
+    if deep and subframes > 1:
+        raise ValueError(f"--pipe_pix_fmt {pipe_pix_fmt} cannot be combined with --subframes {subframes}: the temporal fold is 8-bit only "
+                         f"(it averages the uint8 frames); render at --subframes 1 or with an 8-bit pipe format")
+    if deep and (width % 2 or height % 2):
+        raise ValueError(f"{pipe_pix_fmt} needs even dimensions, got {width}x{height}")
     rank, world = sharding.rank_world()
     # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM) or "host" (per-rank D2H into shared memory)
     transport = transport or os.environ.get("MAUA_FRAME_TRANSPORT", "gather")
@@ -1019,9 +1134,13 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
             with contextlib.closing(delivery):
                 scratch = {}  # the reusable output buffers of the device-side crop / resize / conversion
                 # (lanes: synthesize's default, 3, on every path)
+                # (a deep format asks for the fp32 image; the keyword is passed on that path only)
                 for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
-                                        frame_range=frame_range):
-                    delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold))  # 2048-px frames leave the device as 1920x1080 already
+                                        frame_range=frame_range, **({"frames": "f32"} if deep else {})):
+                    if deep:
+                        delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch))
+                    else:
+                        delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold))  # 2048-px frames leave the device as 1920x1080 already
                 delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt))
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
@@ -1031,7 +1150,7 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
 def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
     """[H, W, 3] of the frames the generator produces for ``out_size`` (1920 / 1080 render 2048-px-wide / -high frames
     that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p", [mjpeg_slot_bytes] for
-    "mjpeg"."""
+    "mjpeg", [deep_frame_bytes] for the deep formats."""
     side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
     if out_size == 1920:
         shape = (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
@@ -1041,4 +1160,6 @@ def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
         shape = (side, side, 3)
     if pix_fmt == "mjpeg":
         return (mjpeg_slot_bytes(shape[1], shape[0]),)
+    if pix_fmt in DEEP_PIX_FMTS:
+        return (deep_frame_bytes(pix_fmt, shape[1], shape[0]),)
     return (shape[0] * shape[1] * 3 // 2,) if pix_fmt == "yuv420p" else shape
