@@ -488,6 +488,55 @@ int maua_crop_resize_u16(const uint16_t* in, uint16_t* out, int batch, int in_h,
                          int out_w, int out_h, void* stream);
 int maua_rgb48_to_yuv_p10(const uint16_t* rgb, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
 int maua_frames_to_yuv_p10_f32(const float* img, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
+/* Frame delivery at any size (csrc/resample.hip): a separable resampler on packed 3-channel frames, Pillow's Image.resize(size, resample,
+ * box) for 8-bit images restated in integers and extended to 16 bits.  (Additive: the ABI version is unchanged.)
+ * Per axis, for a source length n, a source interval [in0, in1), an output length m and a filter f of support s (box 0.5, bilinear 1,
+ * hamming 1, bicubic 2 with a = -0.5, lanczos 3), in double:
+ *   scale = (in1 - in0) / m, fs = max(scale, 1), support = s * fs, ksize = 2 * ceil(support) + 1
+ *   output j: center = in0 + (j + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)), xmax = min(n, (int)(center + support + 0.5)) - xmin
+ *   w_x = f((x + xmin - center + 0.5) / fs) for x < xmax, each divided by their sequential sum when that is non-zero
+ *   k_x = (int)(w_x * 2^22 +- 0.5) (the sign of w_x), 0 from xmax to ksize;  bounds_j = (xmin, xmax)
+ *   a pass: out_j = clamp((2^21 + sum_x in[xmin + x] * k_x) >> 22, 0, top), an arithmetic shift; top = 255 or 65535
+ * The horizontal pass runs first and is rounded to the sample type, the vertical pass runs on its result; 8-bit sums are 32 bits wide,
+ * 16-bit sums 64.
+ *   maua_resample_coeffs  host only, no HIP call: writes k[out_size, ksize] to h_k (`cap` int32 entries) and bounds[out_size, 2] to
+ *                       h_bounds for `filter` (MAUA_RESAMPLE_BOX .. MAUA_RESAMPLE_LANCZOS) and returns ksize.  MAUA_EINVAL for a size below
+ *                       1, an interval outside 0 <= in0 < in1 <= in_size, an unknown filter, a NULL table or cap < out_size * ksize;
+ *                       MAUA_ENOSYS for ksize > MAUA_RESAMPLE_MAX_TAPS (a Lanczos down-scale beyond about 10 : 1).
+ *   maua_resample_u8 / maua_resample_u16  in[B,in_h,in_w,3] -> the window [dst_y0, dst_y0 + dst_h) x [dst_x0, dst_x0 + dst_w) of every frame
+ *                       of out[B,out_h,out_w,3]; no byte outside the window is written (a letterbox border is the caller's, zeroed once).
+ *                       kx[dst_w, ksize_x], bx[dst_w, 2], ky[dst_h, ksize_y], by[dst_h, 2]: DEVICE copies of the tables; both tables of an
+ *                       axis NULL = the axis is copied (dst_w == in_w / dst_h == in_h required, its ksize ignored).  Bounds are clamped
+ *                       to the frame and to ksize on the device, so no table makes the kernels read outside `in`.  One launch (fused) or
+ *                       two (through `ws`, maua_resample_ws_bytes bytes, may be NULL where that is 0) on `stream`; no allocation, no
+ *                       synchronisation, capturable; no atomics, identical bits from run to run.  Any alignment (of the sample type) and
+ *                       any width is served; the 4-byte store path needs out, its row pitch and the window's first column on 4-byte
+ *                       boundaries.  batch == 0 is a successful no-op.  MAUA_EINVAL, before any HIP call, for a NULL buffer, one table
+ *                       of an axis without the other, a size below 1, a window outside the frame, taps outside 1 .. 64, a copied axis of
+ *                       unequal lengths, out (or a needed ws) overlapping in, a needed ws that is NULL; MAUA_ENOSYS above 65535 frames.
+ *   maua_resample_ws_bytes  bytes of `ws` for these arguments (ksize 0 = copied axis): 0 where the fused kernel runs or the arguments are
+ *                       refused, else B * in_h * dst_w * 3 samples.  A pure function of its arguments.
+ *   maua_resample_plan  the entries' own dispatch without the launch (sample_bytes 1 / 2; ksize 0 = copied axis; out_misalign = the
+ *                       output address modulo 4): writes "fused.u8.vec 64x64 tiles=510 trips=1 rows=49 lds=12288" (instance, tile — 64
+ *                       columns by 64, 32 or 16 rows, the tallest whose LDS stays within 20 KB —, tiles per frame, trips of a workgroup's
+ *                       tile loop, LDS rows of the intermediate, dynamic LDS bytes; .vec / .scalar = the store path) or "twopass.u16 trips=8,2 ws=123" (grid-stride trips of the horizontal and vertical launch, workspace
+ *                       bytes) and returns 0; the entries' refusals, or MAUA_EINVAL for a short buf.  No HIP call. */
+#define MAUA_RESAMPLE_MAX_TAPS 64
+#define MAUA_RESAMPLE_BOX 0
+#define MAUA_RESAMPLE_BILINEAR 1
+#define MAUA_RESAMPLE_HAMMING 2
+#define MAUA_RESAMPLE_BICUBIC 3
+#define MAUA_RESAMPLE_LANCZOS 4
+int maua_resample_coeffs(int in_size, int in0, int in1, int out_size, int filter, int32_t* h_k, int32_t* h_bounds, int cap);
+int maua_resample_u8(const uint8_t* in, uint8_t* out, int batch, int in_h, int in_w, int out_h, int out_w, int dst_x0, int dst_y0, int dst_w,
+                     int dst_h, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, void* ws,
+                     void* stream);
+int maua_resample_u16(const uint16_t* in, uint16_t* out, int batch, int in_h, int in_w, int out_h, int out_w, int dst_x0, int dst_y0,
+                      int dst_w, int dst_h, const int32_t* kx, const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by,
+                      int ksize_y, void* ws, void* stream);
+int64_t maua_resample_ws_bytes(int sample_bytes, int batch, int in_h, int in_w, int dst_w, int dst_h, int ksize_x, int ksize_y);
+int maua_resample_plan(int sample_bytes, int batch, int in_h, int in_w, int out_h, int out_w, int dst_x0, int dst_y0, int dst_w, int dst_h,
+                       int ksize_x, int ksize_y, int out_misalign, char* buf, int buf_len);
 
 /* ------------------------------------------------------------------------------------------------ audio / temporal
  * Circular Gaussian FIR along time (audioreactive/signal.py:319-368): x [T, F] -> y [T, F], taps[2*radius+1]

@@ -136,7 +136,12 @@ _SIGNATURES = {
     "maua_crop_resize_u16": (c_int, [_P, _P] + [c_int] * 9 + [_P]),
     "maua_rgb48_to_yuv_p10": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "maua_frames_to_yuv_p10_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
-    "maua_sg1_epilogue_f32": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "maua_resample_coeffs": (c_int, [c_int] * 5 + [_P, _P, c_int]),
+    "maua_resample_u8": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, c_int, _P, _P, c_int, _P, _P]),
+    "maua_resample_u16": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, c_int, _P, _P, c_int, _P, _P]),
+    "maua_resample_ws_bytes": (c_int64, [c_int] * 8),
+    "maua_resample_plan": (c_int, [c_int] * 13 + [c_char_p, c_int]),
+    "maua_sg1_epilogue_f32":(c_int, [_P, _P, _P, c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "maua_temporal_fir_f32": (c_int, [_P, _P, _P, c_int, c_int64, c_int, _P]),
     "maua_stft_power_f32": (c_int, [_P, c_int64, _P, c_int, c_int, _P, c_int, _P]),
     "maua_stft_complex_f32": (c_int, [_P, c_int64, _P, c_int, c_int, _P, _P, c_int, _P]),
@@ -346,6 +351,38 @@ def planned_sosfilt(n_filters, n_sections, n, chunk=0):
     out = (ctypes.c_int32 * 8)()
     rc = load().maua_sosfilt_plan(n_filters, n_sections, n, chunk, out)
     return rc, (dict(zip(SOSFILT_PLAN_FIELDS, out)) if rc == 0 else None)
+
+
+RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "hamming": 2, "bicubic": 3, "lanczos": 4}  # MAUA_RESAMPLE_* (include/maua_hip.h)
+RESAMPLE_MAX_TAPS = 64
+
+
+def resample_coeffs(in_size, in0, in1, out_size, filter):
+    """(rc, k, bounds): maua_resample_coeffs' tables of one axis as int32 numpy arrays [out_size, ksize] and [out_size, 2] (rc = ksize), or
+    its refusal (rc < 0, tables None).  Host only: works without a GPU."""
+    filter_id = RESAMPLE_FILTERS.get(filter, -1) if isinstance(filter, str) else int(filter)
+    n = max(int(out_size), 1)
+    k = np.empty(n * RESAMPLE_MAX_TAPS, np.int32)
+    bounds = np.empty((n, 2), np.int32)
+    rc = load().maua_resample_coeffs(in_size, in0, in1, out_size, filter_id, k.ctypes.data, bounds.ctypes.data, k.size)
+    if rc <= 0:
+        return rc, None, None
+    return rc, k[: n * rc].reshape(n, rc).copy(), bounds
+
+
+def planned_resample(sample_bytes, batch, in_h, in_w, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h, ksize_x, ksize_y, out_misalign=0):
+    """(rc, instance, fields): what maua_resample_u8 / _u16 would launch — "fused.u8.vec", "fused.u16.scalar", "twopass.u8", ... and the
+    plan's key=value fields as a dict of strings (the fused tile, "64x64", "64x32" or "64x16", under "tile") — or the refusal (instance None).  ksize 0 = a copied axis
+    (NULL tables).  Arguments only, no launch: works without a GPU."""
+    buf = ctypes.create_string_buffer(128)
+    rc = load().maua_resample_plan(sample_bytes, batch, in_h, in_w, out_h, out_w, dst_x0, dst_y0, dst_w, dst_h, ksize_x, ksize_y,
+                                   out_misalign, buf, 128)
+    if rc != 0:
+        return rc, None, {}
+    name, *rest = buf.value.decode().split(" ")
+    fields = dict(part.split("=") for part in rest if "=" in part)
+    fields.update({"tile": part for part in rest if "=" not in part})
+    return rc, name, fields
 
 
 class HipEvent:

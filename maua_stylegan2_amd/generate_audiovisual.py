@@ -73,6 +73,13 @@ CLI_FLAGS = (
     ("--shutter", dict(type=str, default="box", help="box, tent or N comma-separated integer weights, e.g. 1,1,0,0")),
     ("--shutter_light", dict(type=str, default="encoded", choices=render.SHUTTER_LIGHTS)),
 )
+# (delivery at any size, render.FrameResize: every frame is resampled on the device before the colour conversion; without --deliver_size
+# the render makes exactly the calls it makes without these flags.  A table of its own: the order of CLI_FLAGS is pinned by tests)
+DELIVERY_FLAGS = (
+    ("--deliver_size", dict(type=str, default=None, help="WIDTHxHEIGHT of the written video, e.g. 1920x1080 (default: the generator's)")),
+    ("--deliver_filter", dict(type=str, default="lanczos", choices=render.RESIZE_FILTERS)),
+    ("--deliver_fit", dict(type=str, default="crop", choices=render.RESIZE_FITS)),
+)
 
 
 def _install_aliases():
@@ -391,9 +398,17 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     try:
         # generate() keeps the reference's parameter list: the pipe format arrives in the namespace (--pipe_pix_fmt, a plugin's OVERRIDE,
         # a caller's own ``args``) or through $MAUA_PIPE_PIX_FMT
-        written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
-                          output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
-                          getattr(args, "mjpeg_quality", None), *((fold,) if subframes > 1 else ()))
+        # ... and so does a delivery size (--deliver_size / --deliver_filter / --deliver_fit); without one, the calls are those of a job
+        # that has never heard of it
+        resize = _resize_of(args)
+        if resize is not None:
+            written = _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
+                                        output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
+                                        getattr(args, "mjpeg_quality", None), fold if subframes > 1 else None, resize)
+        else:
+            written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
+                              output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
+                              getattr(args, "mjpeg_quality", None), *((fold,) if subframes > 1 else ()))
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -410,6 +425,24 @@ def _fold_of(args):
     if subframes is None or subframes == 1:
         return None
     return render.TemporalFold(subframes, getattr(args, "shutter", None) or "box", getattr(args, "shutter_light", None) or "encoded")
+
+
+def _resize_of(args):
+    """The delivery size a namespace asks for (``deliver_size``, ``deliver_filter``, ``deliver_fit``: the CLI flags, a plugin's OVERRIDE or
+    a caller's own ``args``): a render.FrameResize, or None without a ``deliver_size`` — whatever the other two say."""
+    size = getattr(args, "deliver_size", None)
+    if not size:
+        return None
+    return render.FrameResize(size, getattr(args, "deliver_filter", None) or "lanczos", getattr(args, "deliver_fit", None) or "crop")
+
+
+def _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
+                      randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt, mjpeg_quality, fold, resize):
+    """``_render`` for a job with a delivery size (its own parameter list is pinned): render.render_delivered, on one GPU or a shard."""
+    if pipe_pix_fmt == "mjpeg" and mjpeg_quality is not None:
+        pipe_pix_fmt = f"mjpeg:{mjpeg_quality}"
+    return render.render_delivered(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation, bends,
+                                   rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt, fold=fold, resize=resize)
 
 
 def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
@@ -452,7 +485,7 @@ def load_plugin(audioreactive_file):
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    for flag, kwargs in CLI_FLAGS:
+    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS:
         parser.add_argument(flag, **kwargs)
     return parser
 
@@ -484,7 +517,7 @@ def main(argv=None):
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     settings.pop("mjpeg_quality", None)
-    for key in ("subframes", "shutter", "shutter_light"):
+    for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit"):
         settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)

@@ -28,6 +28,9 @@ frames_to_deep turns it into 16-bit packed RGB or 10-bit planar BT.709 YUV on th
 and the encoder (libx265, 10 bits); the frames travel as flat bytes like the yuv420p ones.  Not combinable with a temporal fold.
 Opt-in temporal supersampling (TemporalFold, ``render_folded``; $MAUA_SUBFRAMES for the pinned entries): N rendered sub-frames per delivered
 frame, averaged on the device by fold_frames before any of the above; the sink and the transports then count delivered frames.
+Opt-in delivery size (FrameResize, ``render_delivered``; $MAUA_DELIVER_SIZE / _FILTER / _FIT for the pinned entries): every delivered frame
+is resampled on the device (resize_frames: Lanczos, bicubic, Hamming, bilinear or box; crop, pad or stretch) after the fold and before the
+colour conversion, at 16 bits on the deep formats; the sink and the transports see the delivery size.
 """
 import collections
 import contextlib
@@ -63,6 +66,7 @@ def _output_dims(out_size):
         return 1920, 1080
     if out_size == 1080:
         return 1080, 1920
+    # (the generator's sizes, as in the reference; the VIDEO can have any size: --deliver_size, FrameResize)
     raise Exception("The only output sizes currently supported are: 512, 1024, 1080, or 1920")
 
 
@@ -219,7 +223,8 @@ class FrameSink:
                 (self.proc.stdin if self.proc is not None else self.file).write(memoryview(np.ascontiguousarray(frame)).cast("B"))
             self.count += 1
             return
-        if frame.shape[1] == 2048 or frame.shape[0] == 2048:
+        # (a frame that already has the sink's size is written as it is: a delivery size of 2048 px is not the reference's wide output)
+        if (frame.shape[1] == 2048 or frame.shape[0] == 2048) and (frame.shape[0], frame.shape[1]) != (self.h, self.w):
             import PIL.Image
 
             if frame.shape[1] == 2048:
@@ -407,19 +412,38 @@ def _deep_scratch(scratch, key, shape, dev):
     return out
 
 
-def frames_to_deep(images, out_size, pix_fmt, scratch):
+def frames_to_deep(images, out_size, pix_fmt, scratch, resize=None):
     """fp32 [b, 3, H, W] device images (the generator's output, before any quantiser) -> the frames of a deep pipe format (DEEP_PIX_FMTS) as
     flat bytes, uint8 [b, deep_frame_bytes], on the current (= producing) stream (csrc/deep_frames.hip states the arithmetic):
       no resize, a YUV format   maua_frames_to_yuv_p10_f32: one launch, the 16-bit codes never leave the registers
       no resize, rgb48le        maua_frames_to_u16
       2048-px wide outputs      maua_frames_to_u16, maua_crop_resize_u16 to 1920x1080 / 1080x1920 (the crop of crop_resize_for_delivery), then
                                 maua_rgb48_to_yuv_p10 for a YUV format
+      with ``resize``           maua_frames_to_u16 on the whole generated frame, maua_resample_u16 (resize_frames) to the delivery size, then
+                                maua_rgb48_to_yuv_p10 for a YUV format: the resampler works on the 16-bit codes, nothing is re-quantised
     ``scratch``: dict holding the reusable buffers, keyed by the input buffer (the lanes' batches are in flight concurrently)."""
     if pix_fmt not in DEEP_PIX_FMTS:
         raise ValueError(f"{pix_fmt!r} is not a deep pipe format ({' | '.join(DEEP_PIX_FMTS)})")
     if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda:
         raise RuntimeError(f"frames_to_deep takes fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
     b, _, h, w = images.shape
+    if resize is not None:
+        check_deliver_size(resize, pix_fmt)
+        images = images.contiguous()
+        lib, dev, sub, ptr = _lib.load(), images.device, DEEP_SUBSAMPLING.get(pix_fmt), images.data_ptr()
+        ow, oh = resize.size
+        if b == 0:
+            return th.empty((0, deep_frame_bytes(pix_fmt, ow, oh)), dtype=th.uint8, device=dev)
+        with th.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            master = _deep_scratch(scratch, ("deep-u16", ptr, b, h, w), (b, h, w, 3), dev)
+            _lib.check(lib.maua_frames_to_u16(ptr, master.data_ptr(), b, h, w, st), "maua_frames_to_u16")
+            master = resize_frames(master, resize, scratch)
+            if sub is None:
+                return master.view(b, oh * ow * 3).view(th.uint8)
+            out = _deep_scratch(scratch, ("deep-yuv", ptr, b, oh, ow, sub), (b, deep_frame_bytes(pix_fmt, ow, oh) // 2), dev)
+            _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, oh, ow, sub, st), "maua_rgb48_to_yuv_p10")
+            return out.view(th.uint8)
     if h % 2 or w % 2:
         raise ValueError(f"{pix_fmt} needs even frame dimensions, got {w}x{h}")
     images = images.contiguous()
@@ -579,12 +603,158 @@ def fold_frames(u8, fold, scratch):
     return out
 
 
-def _deliverable(u8, out_size, pix_fmt, scratch, quality=None, fold=None):
+RESIZE_FILTERS = ("lanczos", "bicubic", "hamming", "bilinear", "box")
+RESIZE_FITS = ("crop", "pad", "stretch")
+
+
+def parse_deliver_size(text):
+    """``"WxH"`` (the --deliver_size flag, $MAUA_DELIVER_SIZE) or a (w, h) pair -> (w, h), both at least 1."""
+    if isinstance(text, str):
+        parts = text.lower().split("x")
+        try:
+            size = tuple(int(p) for p in parts)
+        except ValueError:
+            size = ()
+        if len(size) != 2:
+            raise ValueError(f"--deliver_size {text!r} is not WIDTHxHEIGHT (e.g. 1920x1080)")
+    else:
+        size = tuple(int(v) for v in text)
+        if len(size) != 2:
+            raise ValueError(f"a delivery size is (width, height), got {text!r}")
+    if size[0] < 1 or size[1] < 1:
+        raise ValueError(f"--deliver_size {size[0]}x{size[1]}: both sides must be at least 1")
+    return size
+
+
+class FrameResize:
+    """Delivery at a size of the user's choice: every frame is resampled on the device (resize_frames; csrc/resample.hip = Pillow's
+    ``Image.resize`` in integers) to ``size`` = (w, h) or "WxH" with ``filter`` (RESIZE_FILTERS) before the colour conversion.  ``fit`` says
+    how a W x H source meets another aspect ratio, in integers (``geometry``):
+      stretch  the whole source maps to the whole target
+      crop     the centred box of the target's aspect ratio: W h > H w -> cw = clamp((H w + h // 2) // h, 1, W), ch = H; else
+               ch = clamp((W h + w // 2) // w, 1, H), cw = W; x0 = (W - cw) // 2, y0 = (H - ch) // 2
+      pad      the whole source into a centred window dw x dh of the target, one side the target's, the other (H w + W // 2) // W or
+               (W h + H // 2) // H, both rounded down to even (at least 2), at the even offsets ((w - dw) // 2) & ~1, ((h - dh) // 2) & ~1;
+               the border is RGB 0
+    With a resize set the built-in 112-px crop of the 1920 / 1080 outputs is skipped: the source is the whole generated frame."""
+
+    def __init__(self, size, filter="lanczos", fit="crop"):
+        self.size = parse_deliver_size(size)
+        if filter not in RESIZE_FILTERS:
+            raise ValueError(f"unknown --deliver_filter {filter!r} ({' | '.join(RESIZE_FILTERS)})")
+        if fit not in RESIZE_FITS:
+            raise ValueError(f"unknown --deliver_fit {fit!r} ({' | '.join(RESIZE_FITS)})")
+        self.filter, self.fit = filter, fit
+
+    def __repr__(self):
+        return f"FrameResize({self.size[0]}x{self.size[1]}, filter={self.filter!r}, fit={self.fit!r})"
+
+    def key(self):
+        return self.size + (self.filter, self.fit)
+
+    def geometry(self, W, H):
+        """(box, window) for a W x H source: the source box (x0, y0, x1, y1) and the target window (x, y, w, h) it is resampled into."""
+        w, h = self.size
+        if W < 1 or H < 1:
+            raise ValueError(f"a {W}x{H} frame cannot be resized")
+        if self.fit == "stretch":
+            return (0, 0, W, H), (0, 0, w, h)
+        if self.fit == "crop":
+            if W * h > H * w:
+                cw, ch = min(max((H * w + h // 2) // h, 1), W), H
+            else:
+                cw, ch = W, min(max((W * h + w // 2) // w, 1), H)
+            x0, y0 = (W - cw) // 2, (H - ch) // 2
+            return (x0, y0, x0 + cw, y0 + ch), (0, 0, w, h)
+        if w < 2 or h < 2:
+            raise ValueError(f"--deliver_fit pad needs a target of at least 2x2, got --deliver_size {w}x{h}")
+        if W * h > H * w:
+            dw, dh = w, (H * w + W // 2) // W
+        else:
+            dw, dh = (W * h + H // 2) // H, h
+        dw, dh = max(min(dw, w) & ~1, 2), max(min(dh, h) & ~1, 2)
+        return (0, 0, W, H), (((w - dw) // 2) & ~1, ((h - dh) // 2) & ~1, dw, dh)
+
+
+def check_deliver_size(resize, pix_fmt):
+    """yuv420p and the deep formats need even sides: refused with the flag's name, before anything is rendered."""
+    if resize is not None and (pix_fmt == "yuv420p" or pix_fmt in DEEP_PIX_FMTS) and (resize.size[0] % 2 or resize.size[1] % 2):
+        raise ValueError(f"--deliver_size {resize.size[0]}x{resize.size[1]}: --pipe_pix_fmt {pix_fmt} needs even sides")
+
+
+def _resize_from_env():
+    """The resize of a render whose parameter list is pinned (render, render_shard, render_folded): $MAUA_DELIVER_SIZE (WxH),
+    $MAUA_DELIVER_FILTER (lanczos), $MAUA_DELIVER_FIT (crop).  $MAUA_DELIVER_SIZE unset or empty: none, and the other two are not read."""
+    text = os.environ.get("MAUA_DELIVER_SIZE")
+    if not text:
+        return None
+    return FrameResize(text, os.environ.get("MAUA_DELIVER_FILTER") or "lanczos", os.environ.get("MAUA_DELIVER_FIT") or "crop")
+
+
+_RESIZE_TABLES = {}  # (device index, W, H) + FrameResize.key() -> (box, window, (kx, bx, ksize_x), (ky, by, ksize_y)) with device tables
+
+
+def _resize_tables(dev, W, H, resize):
+    index = dev.index if dev.index is not None else th.cuda.current_device()
+    key = (index, W, H) + resize.key()
+    entry = _RESIZE_TABLES.get(key)
+    if entry is None:
+        box, window = resize.geometry(W, H)
+        axes = []
+        for n, in0, in1, m, name in ((W, box[0], box[2], window[2], "width"), (H, box[1], box[3], window[3], "height")):
+            if m == n and in0 == 0 and in1 == n:
+                axes.append((None, None, 0))  # the definition copies the axis
+                continue
+            rc, k, bounds = _lib.resample_coeffs(n, in0, in1, m, resize.filter)
+            if rc == -38:
+                raise ValueError(f"--deliver_size {resize.size[0]}x{resize.size[1]}: the {name} {in1 - in0} -> {m} needs more than "
+                                 f"{_lib.RESAMPLE_MAX_TAPS} {resize.filter} taps; choose a larger size or a shorter filter (bilinear, box)")
+            if rc <= 0:
+                _lib.check(rc, "maua_resample_coeffs")
+            axes.append((th.from_numpy(k).to(dev), th.from_numpy(bounds).to(dev), rc))
+        entry = _RESIZE_TABLES[key] = (box, window, axes[0], axes[1])
+    return entry
+
+
+def resize_frames(frames, resize, scratch):
+    """uint8 — or int16-viewed uint16 — [b, H, W, 3] device frames -> [b, h, w, 3] of the same type at ``resize.size`` on the current
+    (= producing) stream, by maua_resample_u8 / maua_resample_u16 with ``resize``'s filter and fit.  The device tables are cached per
+    (device, source size, setting).  ``scratch``: dict holding the reusable output buffers and workspaces, keyed by the input buffer (the
+    protocol of crop_resize_for_delivery); a padded frame's border is zeroed when the buffer is allocated and never written again."""
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype not in (th.uint8, th.int16) or not frames.is_cuda:
+        raise RuntimeError(f"resize_frames takes uint8 or int16 [b, H, W, 3] device frames, got {frames.dtype} {tuple(frames.shape)} on "
+                           f"{frames.device}")
+    frames = frames.contiguous()
+    b, H, W, _ = frames.shape
+    dev = frames.device
+    sz = 1 if frames.dtype == th.uint8 else 2
+    box, (x, y, w, h), (kx, bx, ksx), (ky, by, ksy) = _resize_tables(dev, W, H, resize)
+    ow, oh = resize.size
+    key = ("resize", frames.data_ptr(), b, H, W, sz) + resize.key()
+    buffers = scratch.get(key)
+    lib = _lib.load()
+    if buffers is None:
+        out = th.zeros((b, oh, ow, 3), dtype=frames.dtype, device=dev)
+        n_ws = int(lib.maua_resample_ws_bytes(sz, b, H, W, w, h, ksx, ksy))
+        buffers = scratch[key] = (out, th.empty(n_ws, dtype=th.uint8, device=dev) if n_ws else None)
+    out, ws = buffers
+    if b == 0:
+        return out
+    fn = lib.maua_resample_u8 if sz == 1 else lib.maua_resample_u16
+    with th.cuda.device(dev):
+        _lib.check(fn(frames.data_ptr(), out.data_ptr(), b, H, W, oh, ow, x, y, w, h, _lib.ptr(kx), _lib.ptr(bx), ksx, _lib.ptr(ky), _lib.ptr(by),
+                      ksy, _lib.ptr(ws), _lib.stream_ptr(dev)), "maua_resample_u8" if sz == 1 else "maua_resample_u16")
+    return out
+
+
+def _deliverable(u8, out_size, pix_fmt, scratch, quality=None, fold=None, resize=None):
     """A batch as it leaves the device: the sub-frames of a temporal fold averaged (on the generator's own frames, so that every later
-    stage sees delivered frames only), wide frames cropped + resized, then — yuv420p — converted to planar 4:2:0 or — mjpeg — encoded."""
+    stage sees delivered frames only), wide frames cropped + resized — or, with ``resize`` (FrameResize), every frame resampled to the
+    delivery size —, then — yuv420p — converted to planar 4:2:0 or — mjpeg — encoded."""
     if _subframes(fold) > 1:
         u8 = fold_frames(u8, fold, scratch)
-    u8 = crop_resize_for_delivery(u8, out_size, scratch)
+    # (a resize of the user's replaces the built-in crop: its source is the whole generated frame)
+    u8 = crop_resize_for_delivery(u8, out_size, scratch) if resize is None else resize_frames(u8, resize, scratch)
     if pix_fmt == "mjpeg":
         return frames_to_mjpeg(u8, scratch, MJPEG_DEFAULT_QUALITY if quality is None else quality)
     return frames_to_yuv420p(u8, scratch) if pix_fmt == "yuv420p" else u8
@@ -1054,9 +1224,12 @@ def render_shard(generator, latents, noise, offset, duration, batch_size, out_si
     YUV made from the fp32 image; refused together with a temporal fold, which is 8-bit only); default $MAUA_PIPE_PIX_FMT, else rgb24 — what
     crosses to the host, to rank 0 and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the
     environment variable.  This parameter list is pinned as well: a temporal fold comes from $MAUA_SUBFRAMES, $MAUA_SHUTTER and
-    $MAUA_SHUTTER_LIGHT (_fold_from_env; unset: none) — ``render_folded`` takes it as an argument."""
+    $MAUA_SHUTTER_LIGHT (_fold_from_env; unset: none) — ``render_folded`` takes it as an argument —, a delivery size from
+    $MAUA_DELIVER_SIZE, $MAUA_DELIVER_FILTER and $MAUA_DELIVER_FIT (_resize_from_env; unset: none) — ``render_delivered`` takes both."""
+    resize = _resize_from_env()
     return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, _fold_from_env())
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, _fold_from_env(),
+                         *(() if resize is None else (resize,)))
 
 
 def render_folded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
@@ -1064,9 +1237,21 @@ def render_folded(generator, latents, noise, offset, duration, batch_size, out_s
     """``render_shard`` with an explicit ``fold`` (TemporalFold or None; the environment is not read): ``latents`` and every per-frame input
     hold ``fold.subframes`` rows per delivered frame, each batch is folded N:1 on the device before anything else happens to it, the sink
     runs at delivered frames / duration and the return value counts delivered frames.  ``batch_size`` and the frame count (of the job and
-    of every rank's block: ``_shard`` stays in rendered frames) must be multiples of N."""
+    of every rank's block: ``_shard`` stays in rendered frames) must be multiples of N.  (A delivery size: $MAUA_DELIVER_SIZE, as
+    render_shard.)"""
+    resize = _resize_from_env()
     return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold)
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *(() if resize is None else (resize,)))
+
+
+def render_delivered(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                     bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None):
+    """``render_folded`` with an explicit ``resize`` (FrameResize or None; the environment is not read for either): every delivered frame
+    is resampled on the device to ``resize.size`` on the rank that rendered it — after the fold, before the colour conversion / the JPEG
+    encoder; at 16 bits on the deep formats —, and the sink, the stream's frame shape and both multi-rank transports see that size.  The
+    built-in 112-px crop of the 1920 / 1080 outputs is skipped: the source is the whole generated frame (2048 x 1024 for out_size 1920)."""
+    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *(() if resize is None else (resize,)))
 
 
 def fold_shard_bounds(n_frames, subframes, rank, world):
@@ -1077,9 +1262,13 @@ def fold_shard_bounds(n_frames, subframes, rank, world):
 
 
 def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold):
-    """The body of render_shard / render_folded.  ``fold`` None or of one sub-frame: the plain render, call for call."""
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None):
+    """The body of render_shard / render_folded / render_delivered.  ``fold`` None or of one sub-frame and ``resize`` None: the plain
+    render, call for call."""
     width, height = _output_dims(out_size)
+    if resize is not None:
+        check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
+        width, height = resize.size  # what the sink, the stream's frame shape and the transports see
     subframes = _subframes(fold)
     if batch_size % subframes:
         raise ValueError(f"--batch {batch_size} is not a multiple of --subframes {subframes}: a batch must hold whole groups of sub-frames "
@@ -1137,22 +1326,27 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                 # (a deep format asks for the fp32 image; the keyword is passed on that path only)
                 for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
                                         frame_range=frame_range, **({"frames": "f32"} if deep else {})):
-                    if deep:
+                    if resize is not None:  # (the keyword is passed on this path only: the plain render makes the calls it always made)
+                        delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch, resize=resize) if deep else
+                                      _deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold, resize=resize))
+                    elif deep:
                         delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch))
                     else:
                         delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold))  # 2048-px frames leave the device as 1920x1080 already
-                delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt))
+                delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt, *(() if resize is None else (resize,))))
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
     return sink.count if sink is not None else 0
 
 
-def _stream_frame_shape(generator, out_size, pix_fmt="rgb24"):
+def _stream_frame_shape(generator, out_size, pix_fmt="rgb24", resize=None):
     """[H, W, 3] of the frames the generator produces for ``out_size`` (1920 / 1080 render 2048-px-wide / -high frames
     that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p", [mjpeg_slot_bytes] for
-    "mjpeg", [deep_frame_bytes] for the deep formats."""
+    "mjpeg", [deep_frame_bytes] for the deep formats.  With ``resize`` (FrameResize) the frames travel at its size, whatever the generator's."""
     side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
-    if out_size == 1920:
+    if resize is not None:
+        shape = (resize.size[1], resize.size[0], 3)
+    elif out_size == 1920:
         shape = (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
     elif out_size == 1080:
         shape = (1920, 1080, 3) if side == 1024 else (2 * side, side, 3)
