@@ -1064,11 +1064,12 @@ class Generator(nn.Module):
         current_size = 4
         image = None
         posted = False  # whether `out` carries the next convolution's styles already
+        u8_written = False  # whether the last layer's epilogue wrote ``frames_u8``
 
         def plain_layer(conv, tag, slot, layer_id, x, e, to_rgb, e_rgb, rgb_name, is_last=False, post_off=None):
             """conv1 (``x`` None: on the constant input) or the plain layer of a resolution, its bends, and the resolution's ToRGB onto
             ``image``: offered to the layer's own launches, else a pass of its own.  Returns the layer's map."""
-            nonlocal image, posted
+            nonlocal image, posted, u8_written
             h, w = (4, 4) if x is None else x.shape[2:]
             rgb_buf = bufs(rgb_name, (batch, 3, h, w))
             wants_rgb = self.min_rgb_size <= current_size
@@ -1088,8 +1089,10 @@ class Generator(nn.Module):
             acts.append(out)
             if fuse is not None and fuse.get("done"):
                 image = rgb_buf
-                if is_last and frames_u8 is not None and fuse.get("u8_done", True) and not self.tap_float_image:
-                    image = None  # left the device path as uint8 frames
+                if is_last and frames_u8 is not None and fuse.get("u8_done", True):
+                    u8_written = True  # left the device path as uint8 frames
+                    if not self.tap_float_image:
+                        image = None
             elif wants_rgb:
                 assert not posted  # (a separate ToRGB pass reads the un-scaled map: plain.run only posts from the ToRGB-fused paths)
                 image = to_rgb.run(out, s, e_rgb["s_off"], image, rgb_buf)
@@ -1113,7 +1116,9 @@ class Generator(nn.Module):
             post_off = None if is_last else post_for(2 * n + 3, self.convs[2 * n + 2], h, w, e_next)
             out = plain_layer(plain, f"convs.{2 * n + 1}", 2 * n + 2, 2 * n + 3, out, e_plain, self.to_rgbs[n], e_rgb, f"rgbs.{n}",
                               is_last, post_off)
-        if frames_u8 is not None and image is not None:  # last layer not fusable (bend on it, > 64 channels, ...)
+        # last layer not fusable (bend on it, > 64 channels, ...).  (Not behind an epilogue that wrote the frames: with tap_float_image the
+        # fp32 image exists as well, and converting it here would replace the frames the parity tests mean to look at.)
+        if frames_u8 is not None and image is not None and not u8_written:
             _lib.check(lib.maua_frames_to_u8(image.data_ptr(), frames_u8.data_ptr(), batch, image.shape[2], image.shape[3], st),
                        "maua_frames_to_u8")
         lat_out = None

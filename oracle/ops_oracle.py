@@ -25,13 +25,16 @@ def upfirdn2d(x, kernel, up=1, down=1, pad=(0, 0)):
 def upfirdn2d_xy(x, kernel, up_x, up_y, down_x, down_y, px0, px1, py0, py1):
     n, c, h, w = x.shape
     kh, kw = kernel.shape
-    planes = x.reshape(n * c, 1, h, w).to(torch.float32)
+    # (computed in float32 as the reference's dispatcher does, except for float64 inputs: the fp64 whole-forward reference of
+    # tests/forward_ref.py runs this file on a state dict cast to double and must not be rounded to float32 half way)
+    dtype = torch.float64 if x.dtype == torch.float64 else torch.float32
+    planes = x.reshape(n * c, 1, h, w).to(dtype)
     # zero-stuffed canvas: sample (y, x) lands on (y*up_y, x*up_x); up-1 trailing zeros after the last one
     stuffed = planes.new_zeros(n * c, 1, h * up_y, w * up_x)
     stuffed[:, :, ::up_y, ::up_x] = planes
     # pad >= 0 adds zeros, pad < 0 crops (op/upfirdn2d.py:171-181)
     stuffed = F.pad(stuffed, [px0, px1, py0, py1])
-    taps = torch.flip(kernel.to(torch.float32), [0, 1]).reshape(1, 1, kh, kw)
+    taps = torch.flip(kernel.to(dtype), [0, 1]).reshape(1, 1, kh, kw)
     full = F.conv2d(stuffed, taps)
     out = full[:, :, ::down_y, ::down_x]
     oh = upfirdn2d_out_size(h, up_y, down_y, py0, py1, kh)

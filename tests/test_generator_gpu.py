@@ -35,6 +35,19 @@ def test_generator_matches_reference_golden(gpu, golden, size):
     err = np.abs(got - gold["image"]).max()
     assert err < TOL, f"{size}: max abs err {err}"
     np.testing.assert_allclose([a.abs().mean().item() for a in acts], gold["act_mean_abs"], rtol=1e-3)
+    if size <= 256:
+        # ... and every element of every activation map (and of the image) against the fp64 forward of the same inputs, inside the bounds
+        # 4 G max |fp32 - fp64| of tests/forward_ref.py (the CPU forwards of a 1024^2 generator take too long for this suite)
+        import forward_ref as fr
+
+        sd = seeding.seeded_state_dict(size, seed=s_sd)
+        args = (sd, lat.cpu(), [n.cpu() for n in noise], torch.full((batch,), float(gold["truncation"])), g.truncation_latent.cpu())
+        ref, rnd = fr.walk_as(torch.float64, *args), fr.walk_as(torch.float32, *args)
+        bnd = fr.bounds_of(ref, rnd)
+        checks = [fr.check(f"{size}: activation map {i}", a, ref["acts"][i], bnd["acts"][i]) for i, a in enumerate(acts)]
+        checks.append(fr.check(f"{size}: image", img, ref["image"], bnd["image"]))
+        print(f"[golden {size}] worst: {max(checks)[1]}")
+        assert all(frac <= 1.0 for frac, _ in checks), [msg for frac, msg in checks if frac > 1.0]
     np.testing.assert_allclose(np.array([img.mean().item(), img.std().item()]), gold["image_mean_std"], atol=1e-3)
     # checkpoint noise buffers + truncation 1 (identity)
     g.truncation_latent = None
