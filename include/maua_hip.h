@@ -488,6 +488,41 @@ int maua_crop_resize_u16(const uint16_t* in, uint16_t* out, int batch, int in_h,
                          int out_w, int out_h, void* stream);
 int maua_rgb48_to_yuv_p10(const uint16_t* rgb, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
 int maua_frames_to_yuv_p10_f32(const float* img, uint16_t* out, int batch, int h, int w, int subsampling, void* stream);
+/* Colour grading of the fp32 image (csrc/grade.hip): ASC CDL, a 3 x 3 matrix and a 3-D LUT in front of the quantisers.  (Additive: the ABI
+ * version is unchanged.)
+ *   maua_grade_f32    img[B,3,h,w] fp32 -> out[B,3,h,w] fp32; out == img (in place) is legal
+ *   maua_grade_to_u8  img[B,3,h,w] fp32 -> out[B,h,w,3] uint8: maua_frames_to_u8 applied to maua_grade_f32's result, bit for bit, the
+ *                     graded value kept in registers
+ * Frame b reads the 24 floats at rows + b * row_stride (row_stride >= 24): slope[3] at 0, offset[3] at 3, power[3] at 6, the matrix M[3][3]
+ * row-major at 9, bias[3] at 18, lut_mix at 21, two reserved zeros.  Per pixel, in fp32, every operation rounded on its own (no multiply-add
+ * is contracted), with clamp01(a) = fminf(fmaxf(a, 0), 1), which takes a NaN to 0 as the quantiser's clamp does:
+ *   v_c = clamp01(x_c * 0.5f + 0.5f)
+ *   t_c = clamp01(v_c * slope_c + offset_c);  t_c = power_c == 1 ? t_c : powf(t_c, power_c)       (0 stays 0)
+ *   m_c = clamp01(((M[c][0] * t_0 + M[c][1] * t_1) + M[c][2] * t_2) + bias_c)
+ *   lut != NULL and lut_mix != 0:  l = tetra(lut, m);  m_c = clamp01(m_c + lut_mix * (l_c - m_c))
+ *   y_c = m_c * 2.0f - 1.0f
+ * lut: a table of lut_n^3 entries (2 <= lut_n <= 65) over the domain [0, 1], red index fastest (.cube order), every entry PADDED to four
+ * floats (r, g, b, unused) and the table 16-byte aligned: entry (ir, ig, ib) is at float offset 4 * ((ib * lut_n + ig) * lut_n + ir).
+ * tetra, per axis a: p = m_a * (lut_n - 1), i_a = min((int)p, lut_n - 2), f_a = p - i_a.  The fractions are ordered hi >= mid >= lo by
+ * this chain, which also resolves ties:
+ *   f_r >= f_g:  f_g >= f_b ? (r, g, b) : f_r >= f_b ? (r, b, g) : (b, r, g)
+ *   otherwise:   f_b >= f_g ? (b, g, r) : f_b >= f_r ? (g, b, r) : (g, r, b)
+ * The vertices are v0 = c(i), v1 = v0 stepped along hi's axis, v2 = v1 stepped along mid's axis, v3 = c(i + 1), and
+ *   l_c = (((1 - hi) * v0_c + (hi - mid) * v1_c) + (mid - lo) * v2_c) + lo * v3_c
+ * m is clamped before it indexes the table: no index leaves it, whatever the rows and the image hold.
+ * Identity: a frame whose row has slope 1, offset 0, power 1, M = I, bias 0 and (lut == NULL or lut_mix == 0) is passed through untouched —
+ * out = img bit for bit, NaN payloads included; the uint8 output is maua_frames_to_u8's — because 2 * fl(0.5 x + 0.5) - 1 is not x in fp32.
+ * The device does NOT check the rows (finite values, power > 0): audioreactive/grade.py's Grade does; the output is defined (clamped)
+ * for any row.  One launch on `stream`, no allocation, no synchronisation: capturable.
+ * Refused before any HIP call: MAUA_EINVAL for non-positive h or w, batch < 0, row_stride < 24, a lut with lut_n outside 2 .. 65 or not
+ * 16-byte aligned, a NULL img, out or rows (batch > 0), an out that overlaps img other than out == img for the fp32 entry; batch == 0 is a
+ * successful no-op; more than 65535 frames or more than 2^31 - 256 pixels per frame a launch are MAUA_ENOSYS.
+ * Vector path (a lane takes 4 consecutive pixels: 16-byte loads, 16-byte stores or three dwords of uint8): h * w % 4 == 0, img 16-byte
+ * aligned, out 16-byte (fp32) or 4-byte (uint8) aligned; anything else takes the scalar path, which serves any size and alignment. */
+int maua_grade_f32(const float* img, float* out, int batch, int h, int w, const float* rows, int row_stride, const float* lut, int lut_n,
+                   void* stream);
+int maua_grade_to_u8(const float* img, uint8_t* out, int batch, int h, int w, const float* rows, int row_stride, const float* lut, int lut_n,
+                     void* stream);
 /* Frame delivery at any size (csrc/resample.hip): a separable resampler on packed 3-channel frames, Pillow's Image.resize(size, resample,
  * box) for 8-bit images restated in integers and extended to 16 bits.  (Additive: the ABI version is unchanged.)
  * Per axis, for a source length n, a source interval [in0, in1), an output length m and a filter f of support s (box 0.5, bilinear 1,

@@ -15,6 +15,10 @@ hipGraph-replayed, frames leave as uint8, and under ``torchrun`` every GPU rende
 Temporal supersampling (not in the reference): ``--fps F --subframes N`` is ``--fps F * N`` up to and including synthesis; the frames are
 then folded N:1 on the device (``--shutter``, ``--shutter_light``; render.TemporalFold) and written at F.  ``--batch`` must be a multiple
 of N.
+
+Colour grading (not in the reference): a plugin's ``initialize`` (or its ``OVERRIDE``, or the caller's ``args``) leaves an ``ar.Grade`` — or a
+callable ``grade(args)`` — in ``args.grade``; ``--grade`` / ``--grade_lut`` / ``--grade_lut_mix`` build a static one.  Every rendered frame is
+then graded on the device in front of the quantiser (render.render_graded).
 """
 import argparse
 import gc
@@ -79,6 +83,14 @@ DELIVERY_FLAGS = (
     ("--deliver_size", dict(type=str, default=None, help="WIDTHxHEIGHT of the written video, e.g. 1920x1080 (default: the generator's)")),
     ("--deliver_filter", dict(type=str, default="lanczos", choices=render.RESIZE_FILTERS)),
     ("--deliver_fit", dict(type=str, default="crop", choices=render.RESIZE_FITS)),
+)
+# (colour grading, audioreactive/grade.py + csrc/grade.hip: static flags that build a one-row ar.Grade; a modulated grade comes from the
+# plugin as ``args.grade``.  Without any of them the render makes exactly the calls it makes without these flags.  A table of its own again)
+GRADE_FLAGS = (
+    ("--grade_lut", dict(type=str, default=None, help="a 3-D .cube file applied to every frame after the CDL and the matrix")),
+    ("--grade_lut_mix", dict(type=float, default=1.0, help="weight of --grade_lut, 0 .. 1")),
+    ("--grade", dict(type=str, default=None, dest="grade_spec",
+                     help='a static grade, e.g. "exposure=0.3,saturation=1.2,gamma=0.9,hue=15" (keys: ' + ", ".join(ar.grade.SPEC_KEYS) + ")")),
 )
 
 
@@ -325,6 +337,9 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     if front_end:
         if initialize is not None:
             args = initialize(args)
+    # (generate() keeps the reference's parameter list: a colour grade arrives in the namespace — ``args.grade`` set by the plugin's
+    # initialize, by its OVERRIDE or by the caller, and the --grade / --grade_lut flags —; resolved on rank 0, after initialize)
+    grade = _grade_of(args) if rank == 0 else None
 
     if rank == 0:
         print("\ngenerating latents...")
@@ -368,6 +383,8 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
             latents, noise, truncation = _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames)
         lo, hi = render.fold_shard_bounds(n_frames, subframes, rank, world)
         shard = (lo, hi, n_frames)
+        if sharding.broadcast_object(grade is not None if rank == 0 else None):  # (a job without a grade adds this one object, nothing else)
+            grade = _broadcast_grade(grade, lo, hi)
 
     # (reference :191-192.)  The job's one collection — 45-70 ms on this heap.  Full on purpose where it runs: young-generation collections
     # (tried in round 5) leave the preprocessing's cyclic garbage, device tensors among it, alive, and a render that has to LOAD its generator
@@ -401,7 +418,14 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # ... and so does a delivery size (--deliver_size / --deliver_filter / --deliver_fit); without one, the calls are those of a job
         # that has never heard of it
         resize = _resize_of(args)
-        if resize is not None:
+        if grade is not None:
+            pix_fmt = getattr(args, "pipe_pix_fmt", None)
+            if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
+                pix_fmt = f"mjpeg:{args.mjpeg_quality}"
+            written = render.render_graded(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
+                                           bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt,
+                                           fold=fold if subframes > 1 else None, resize=resize, grade=grade)
+        elif resize is not None:
             written = _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
                                         output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
                                         getattr(args, "mjpeg_quality", None), fold if subframes > 1 else None, resize)
@@ -434,6 +458,49 @@ def _resize_of(args):
     if not size:
         return None
     return render.FrameResize(size, getattr(args, "deliver_filter", None) or "lanczos", getattr(args, "deliver_fit", None) or "crop")
+
+
+def _grade_of(args):
+    """The colour grade a namespace asks for, or None.  ``args.grade``: an ar.Grade, a callable ``grade(args) -> ar.Grade`` (evaluated here:
+    after initialize, so it may use what initialize computed), or a --grade string; ``grade_spec`` / ``grade_lut`` / ``grade_lut_mix``: the
+    CLI flags.  Without a plugin grade the flags build a one-row grade; with one, --grade_lut is attached to it when it has no LUT of its
+    own, and anything that would need two grades composed (a --grade string next to a plugin grade, two LUTs) is refused."""
+    grade = getattr(args, "grade", None)
+    spec, lut, mix = getattr(args, "grade_spec", None), getattr(args, "grade_lut", None), getattr(args, "grade_lut_mix", None)
+    mix = 1.0 if mix is None else mix
+    if isinstance(grade, str):
+        grade = ar.Grade(**ar.grade.parse_spec(grade))
+    elif grade is not None and not isinstance(grade, ar.Grade):
+        if not callable(grade):
+            raise TypeError(f"args.grade must be an ar.Grade or a callable grade(args) -> ar.Grade, got {type(grade).__name__}")
+        grade = grade(args)
+        if grade is not None and not isinstance(grade, ar.Grade):
+            raise TypeError(f"args.grade(args) must return an ar.Grade, got {type(grade).__name__}")
+    if grade is None:
+        if not spec and not lut:
+            return None
+        return ar.Grade(**(ar.grade.parse_spec(spec) if spec else {}), lut=lut, lut_mix=mix)
+    if spec:
+        raise ValueError("--grade cannot be combined with the plugin's grade (two grades do not compose into one row): set it in the plugin")
+    if lut:
+        if grade.lut is not None:
+            raise ValueError("--grade_lut cannot be combined with a plugin grade that has a LUT of its own")
+        grade = grade.with_lut(lut, mix)
+    return grade
+
+
+def _broadcast_grade(grade, lo, hi):
+    """One process per GPU: rank 0's grade reaches every rank — the row table is broadcast and cut to this rank's frames [lo, hi) (a one-row
+    table is kept as it is), the LUT is broadcast whole.  (A helper of its own: _scatter_from_rank0's parameter list is pinned.)"""
+    rank, _ = sharding.rank_world()
+    table, lut = sharding.broadcast_object((grade.table, grade.lut) if rank == 0 else None)
+    if table.shape[0] != 1:
+        if hi > table.shape[0]:
+            raise RuntimeError(f"the grade's table has {table.shape[0]} rows, this rank renders the frames {lo} .. {hi}")
+        if hi == lo:
+            return ar.Grade.from_table(table[:1], lut)  # (a rank without frames: never applied)
+        table = table[lo:hi]
+    return ar.Grade.from_table(table, lut)
 
 
 def _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
@@ -485,7 +552,7 @@ def load_plugin(audioreactive_file):
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS:
+    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS:
         parser.add_argument(flag, **kwargs)
     return parser
 
@@ -517,7 +584,8 @@ def main(argv=None):
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     settings.pop("mjpeg_quality", None)
-    for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit"):
+    for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit", "grade", "grade_spec", "grade_lut",
+                "grade_lut_mix"):
         settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)

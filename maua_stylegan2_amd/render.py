@@ -31,6 +31,9 @@ frame, averaged on the device by fold_frames before any of the above; the sink a
 Opt-in delivery size (FrameResize, ``render_delivered``; $MAUA_DELIVER_SIZE / _FILTER / _FIT for the pinned entries): every delivered frame
 is resampled on the device (resize_frames: Lanczos, bicubic, Hamming, bilinear or box; crop, pad or stretch) after the fold and before the
 colour conversion, at 16 bits on the deep formats; the sink and the transports see the delivery size.
+Opt-in colour grade (audioreactive/grade.py's Grade, ``render_graded``): the lanes keep the fp32 image and every rendered frame is graded on
+the device by its row of the grade's table (grade_frames: ASC CDL, a 3 x 3 matrix, a 3-D LUT) before any of the above — the 8-bit formats
+continue with the frames the quantiser gives for the graded image, the deep formats with the image graded in place.
 """
 import collections
 import contextlib
@@ -477,6 +480,51 @@ def frames_to_deep(images, out_size, pix_fmt, scratch, resize=None):
         out = _deep_scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), dev)
         _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, h, w, sub, st), "maua_rgb48_to_yuv_p10")
         return out.view(th.uint8)
+
+
+def grade_frames(images, grade_rows, lut, scratch, out="u8"):
+    """fp32 [b, 3, H, W] device images (the generator's output) graded on the current (= producing) stream by csrc/grade.hip: ASC CDL slope /
+    offset / power, a 3 x 3 matrix with bias and a 3-D LUT (include/maua_hip.h states the arithmetic; audioreactive/grade.py's Grade builds
+    the operands).  ``grade_rows``: float32 device rows [b, >= 24], one per frame of the batch (a view into a longer table is fine: the row
+    stride is passed on); ``lut``: Grade.lut_table's padded table [N^3, 4] or None.
+      out="u8"   -> uint8 [b, H, W, 3] by maua_grade_to_u8 (= frames_to_uint8 of the graded image), in a reusable buffer of ``scratch`` keyed
+                    by the input buffer (the protocol of crop_resize_for_delivery)
+      out="f32"  -> ``images`` itself, graded in place by maua_grade_f32
+    Frames whose row is the identity come out as they went in (as frames_to_uint8's for "u8")."""
+    if out not in ("u8", "f32"):
+        raise ValueError(f"unknown grade output {out!r} (u8 | f32)")
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"grade_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    b, _, h, w = images.shape
+    dev = images.device
+    if (grade_rows.dim() != 2 or grade_rows.shape[0] != b or grade_rows.shape[1] < 24 or grade_rows.dtype != th.float32 or grade_rows.device != dev
+            or (b > 0 and grade_rows.stride(1) != 1) or (b > 1 and grade_rows.stride(0) < 24)):
+        raise RuntimeError(f"grade_frames takes float32 rows [{b}, >= 24] on {dev}, got {grade_rows.dtype} {tuple(grade_rows.shape)} "
+                           f"(strides {grade_rows.stride()}) on {grade_rows.device}")
+    lut_n = 0
+    if lut is not None:
+        if lut.dim() != 2 or lut.shape[1] != 4 or lut.dtype != th.float32 or lut.device != dev or not lut.is_contiguous():
+            raise RuntimeError(f"grade_frames takes the padded LUT [N^3, 4] float32 on {dev}, got {lut.dtype} {tuple(lut.shape)} on {lut.device}")
+        lut_n = round(lut.shape[0] ** (1 / 3))
+        if lut_n ** 3 != lut.shape[0]:
+            raise RuntimeError(f"grade_frames: a LUT of {lut.shape[0]} entries is not a cube")
+    stride = grade_rows.stride(0) if b > 1 else 24
+    lib = _lib.load()
+    if out == "f32":
+        if b:
+            with th.cuda.device(dev):
+                _lib.check(lib.maua_grade_f32(images.data_ptr(), images.data_ptr(), b, h, w, grade_rows.data_ptr(), stride, _lib.ptr(lut), lut_n,
+                                              _lib.stream_ptr(dev)), "maua_grade_f32")
+        return images
+    key = ("grade-u8", images.data_ptr(), b, h, w)
+    u8 = scratch.get(key)
+    if u8 is None:
+        u8 = scratch[key] = th.empty((b, h, w, 3), dtype=th.uint8, device=dev)
+    if b:
+        with th.cuda.device(dev):
+            _lib.check(lib.maua_grade_to_u8(images.data_ptr(), u8.data_ptr(), b, h, w, grade_rows.data_ptr(), stride, _lib.ptr(lut), lut_n,
+                                            _lib.stream_ptr(dev)), "maua_grade_to_u8")
+    return u8
 
 
 MAX_SUBFRAMES = 16
@@ -1254,6 +1302,33 @@ def render_delivered(generator, latents, noise, offset, duration, batch_size, ou
                          rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *(() if resize is None else (resize,)))
 
 
+def render_graded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None):
+    """``render_delivered`` with a colour ``grade`` (audioreactive/grade.py's Grade, or None: render_delivered, call for call): the lanes keep
+    the fp32 image, every rendered frame is graded on the device by its row of the grade's table (grade_frames) — per sub-frame and before
+    the fold with a temporal fold, before the resampler with a delivery size —, then the 8-bit formats go on as maua_grade_to_u8's frames
+    through crop / fold / resize / yuv420p / mjpeg and the deep formats as the image graded in place through frames_to_deep.  The table
+    holds one row, or one row per entry of ``latents`` (with ``_shard``: this rank's block, Grade.slice); anything else is refused before
+    the first batch."""
+    extra = () if resize is None and grade is None else (resize,) if grade is None else (resize, grade)
+    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *extra)
+
+
+def _grade_operands(grade, n_rendered, batch_size, dev):
+    """(rows, lut, per_frame) of a render's grade on ``dev``: the device row table — a one-row table repeated to a batch, so that every
+    launch finds a row per frame — and the padded LUT.  Refuses a table that has neither one row nor ``n_rendered``."""
+    if not (hasattr(grade, "rows") and hasattr(grade, "lut_table") and hasattr(grade, "n_rows")):
+        raise TypeError(f"grade must be an audioreactive Grade, got {type(grade).__name__}")
+    if grade.n_rows not in (1, n_rendered):
+        raise ValueError(f"the grade's table has {grade.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
+    rows = grade.rows(dev)
+    per_frame = grade.n_rows != 1 or n_rendered == 1
+    if not per_frame:
+        rows = rows.expand(max(batch_size, 1), rows.shape[1]).contiguous()
+    return rows, grade.lut_table(dev), per_frame
+
+
 def fold_shard_bounds(n_frames, subframes, rank, world):
     """[lo, hi) of a rank's block in RENDERED frames when every delivered frame is folded from ``subframes`` of them: the job is sharded in
     units of delivered frames (sharding.shard_bounds of n_frames / N), so that no group straddles two ranks."""
@@ -1262,9 +1337,9 @@ def fold_shard_bounds(n_frames, subframes, rank, world):
 
 
 def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None):
-    """The body of render_shard / render_folded / render_delivered.  ``fold`` None or of one sub-frame and ``resize`` None: the plain
-    render, call for call."""
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None):
+    """The body of render_shard / render_folded / render_delivered / render_graded.  ``fold`` None or of one sub-frame, ``resize`` None and
+    ``grade`` None: the plain render, call for call."""
     width, height = _output_dims(out_size)
     if resize is not None:
         check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
@@ -1298,6 +1373,8 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
     # what the sink and the transports count: delivered frames — n_frames and batch_size themselves without a fold
     n_out, batch_out = n_frames // subframes, batch_size // subframes
     dev = device_of(generator)
+    if grade is not None:  # (refused here, before the sink is opened and the first batch is rendered)
+        grade_rows, grade_lut, grade_per_frame = _grade_operands(grade, len(latents), batch_size, dev)
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
@@ -1324,8 +1401,13 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                 scratch = {}  # the reusable output buffers of the device-side crop / resize / conversion
                 # (lanes: synthesize's default, 3, on every path)
                 # (a deep format asks for the fp32 image; the keyword is passed on that path only)
-                for _, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
-                                        frame_range=frame_range, **({"frames": "f32"} if deep else {})):
+                # (a grade asks for it as well: it works on the fp32 image, and hands the 8-bit chain the frames the quantiser would have)
+                for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
+                                            frame_range=frame_range, **({"frames": "f32"} if deep or grade is not None else {})):
+                    if grade is not None:
+                        count = u8.shape[0]
+                        rows = grade_rows[first: first + count] if grade_per_frame else grade_rows[:count]
+                        u8 = grade_frames(u8.contiguous(), rows, grade_lut, scratch, out="f32" if deep else "u8")
                     if resize is not None:  # (the keyword is passed on this path only: the plain render makes the calls it always made)
                         delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch, resize=resize) if deep else
                                       _deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold, resize=resize))
