@@ -523,6 +523,59 @@ int maua_grade_f32(const float* img, float* out, int batch, int h, int w, const 
                    void* stream);
 int maua_grade_to_u8(const float* img, uint8_t* out, int batch, int h, int w, const float* rows, int row_stride, const float* lut, int lut_n,
                      void* stream);
+/* Lens effects on the fp32 image (csrc/lens.hip): bloom, sharpen / soften and vignette, in front of the grade and the quantisers.
+ * (Additive: the ABI version is unchanged.)  Images are the generator's fp32 [B,3,h,w], raw range [-1, 1]; clamp01(a) = fminf(fmaxf(a, 0), 1)
+ * takes a NaN to 0.  Frame b reads the 16 floats at rows + b * row_stride (row_stride >= 16): threshold at 0, knee at 1, bloom_rgb[3] at 2
+ * (gain x tint, folded by the host), sharpen at 5 (negative softens), vignette at 6, vig_inner at 7, vig_outer at 8, seven reserved zeros.
+ *
+ * maua_lens_extract_f32  img[B,3,h,w] -> out[B,3,ceil(h/d),ceil(w/d)], d in {1, 2, 4, 8}.  Per pixel, in fp32, every operation rounded on
+ * its own (nothing contracted):
+ *   v_c = clamp01(x_c * 0.5f + 0.5f);  m = fmaxf(fmaxf(v_r, v_g), v_b);  o = m - threshold
+ *   s = fminf(fmaxf(o + knee, 0), 2.0f * knee);  s = (s * s) / (4.0f * knee + 1e-5f)
+ *   q = fmaxf(s, o) / fmaxf(m, 1e-5f)            (the soft-knee curve; s >= 0, so q >= 0)
+ *   hl_c = v_c * q
+ * An output cell is the sum of hl_c over the pixels of its d x d block that exist — accumulated from 0.0f row by row, within a row from
+ * left to right — divided by their count as a float: edge blocks divide by their own count.
+ *
+ * maua_lens_blur_f32  src[B,planes,h,w] -> dst[B,planes,h,w], dst must not overlap src.  0 <= radius <= 64, tap_stride >= radius + 1;
+ * frame b reads its half-kernel w[0 .. radius] at taps + b * tap_stride, w[0] the centre:
+ *   y[i] = w[0] x[i] + sum_{k = 1 .. radius} w[k] (x[clamp(i - k)] + x[clamp(i + k)])       clamp: to 0 .. n - 1 (edges replicated)
+ * along rows, then along columns of the result.  The order of the summation is NOT fixed and multiply-adds may be fused: the result is
+ * within 2 (radius + 4) 2^-23 max|x| of the exact one for weights that sum to 1, and exact wherever every partial sum is representable
+ * (dyadic taps on integers).  radius == 0 with w[0] == 1 copies.  The taps are not checked: the host builds them.
+ * maua_lens_blur_plan reports, without launching, what the entry does for (h, w, radius, src): plan[0] the instance (1: w % 4 == 0
+ * and src 16-byte aligned, the halo is staged with 16-byte loads; 0: scalar loads, any size and alignment), plan[1] x plan[2] the output
+ * tile of a workgroup (64 x 64), plan[3] the workgroups per plane, plan[4] a workgroup's LDS in bytes (<= 65536 at every radius), plan[5] the
+ * number of launches (1: there is no two-launch path).
+ *
+ * maua_lens_apply_f32  img[B,3,h,w] -> out[B,3,h,w]; out == img (in place) is legal.  bloom ([B,3,bh,bw], the blurred map of reduction d)
+ * and soft ([B,3,h,w], a short-radius blur of img) may be NULL: then that term is absent.  Per pixel (px, py), in fp32, every operation
+ * rounded on its own, in this order:
+ *   y_c = x_c
+ *   soft:   y_c = y_c + sharpen * (x_c - soft_c)
+ *   bloom:  u = fminf(fmaxf((px + 0.5f) / d - 0.5f, 0), bw - 1), x0 = (int)u, x1 = min(x0 + 1, bw - 1), fx = u - x0; v, y0, y1, fy likewise
+ *           with py and bh;  w00 = (1 - fx) * (1 - fy), w01 = fx * (1 - fy), w10 = (1 - fx) * fy, w11 = fx * fy;
+ *           g_c = ((w00 * b[y0][x0] + w01 * b[y0][x1]) + w10 * b[y1][x0]) + w11 * b[y1][x1]
+ *           y_c = y_c + (2.0f * bloom_rgb_c) * g_c                                  (2: the map lives in display range 0 .. 1)
+ *   vignette != 0:  dx = ((px + 0.5f) - w * 0.5f) / (w * 0.5f), dy likewise;  r = sqrtf(dx * dx + dy * dy) * 0.70710678f   (corner: 1)
+ *           t = clamp01((r - vig_inner) / (vig_outer - vig_inner));  f = 1.0f - vignette * ((t * t) * (3.0f - 2.0f * t))
+ *           y_c = (y_c + 1.0f) * f - 1.0f
+ * Identity: a frame whose row has bloom_rgb == 0, sharpen == 0 and vignette == 0 is passed through untouched — out = img bit for bit, NaN
+ * payloads included, whatever bloom and soft hold.  The test is uniform over the frame.
+ *
+ * Every entry is one launch on `stream`, no allocation, no synchronisation: capturable.  The rows are not checked (audioreactive/lens.py's
+ * Lens does).  Refused before any HIP call: MAUA_EINVAL for non-positive sizes, batch < 0, d outside {1, 2, 4, 8} (apply: with a bloom
+ * only), radius outside 0 .. 64, tap_stride < radius + 1, row_stride < 16, a NULL img / src / out / dst / rows / taps (batch > 0), an output
+ * that overlaps an input other than out == img in apply; batch == 0 is a successful no-op; more than 65535 frames (blur: or planes) or more
+ * than 2^31 - 256 pixels per plane (blur: or more than 2^24 - 1 tiles of 64 x 64 per plane, which only a plane a few pixels wide or high
+ * reaches) are MAUA_ENOSYS.  Vector paths (16-byte accesses, 4 consecutive pixels of a row per lane): w % 4 == 0 and
+ * the image pointers 16-byte aligned (extract: img; blur: src; apply: img, out and soft); anything else takes the scalar paths. */
+int maua_lens_extract_f32(const float* img, float* out, int batch, int h, int w, int d, const float* rows, int row_stride, void* stream);
+int maua_lens_blur_f32(const float* src, float* dst, int batch, int planes, int h, int w, int radius, const float* taps, int tap_stride,
+                       void* stream);
+int maua_lens_blur_plan(int h, int w, int radius, const float* src, int* plan);
+int maua_lens_apply_f32(const float* img, float* out, int batch, int h, int w, const float* rows, int row_stride, const float* bloom, int bh,
+                        int bw, int d, const float* soft, void* stream);
 /* Frame delivery at any size (csrc/resample.hip): a separable resampler on packed 3-channel frames, Pillow's Image.resize(size, resample,
  * box) for 8-bit images restated in integers and extended to 16 bits.  (Additive: the ABI version is unchanged.)
  * Per axis, for a source length n, a source interval [in0, in1), an output length m and a filter f of support s (box 0.5, bilinear 1,

@@ -9,6 +9,7 @@ from .filters import *  # noqa: F401,F403  (sosfilt, sosfiltfilt, bandpass, enve
 from .grade import *  # noqa: F401,F403  (Grade, load_cube, save_cube, lut_from_function: colour grading of the fp32 image, no counterpart in the reference)
 from .harmony import *  # noqa: F401,F403  (viterbi, hmm_posterior, chord_vocabulary, raw_chords, chords, key: chords and key, no counterpart in the reference)
 from .latent import *  # noqa: F401,F403
+from .lens import *  # noqa: F401,F403  (Lens: bloom, sharpen and vignette on the fp32 image, no counterpart in the reference)
 from .noise import *  # noqa: F401,F403  (NoiseSynth, noise_term: synthesised noise slots, no counterpart in the reference)
 from .signal import *  # noqa: F401,F403
 from .signal import set_SMF  # noqa: F401

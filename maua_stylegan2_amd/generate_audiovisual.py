@@ -19,6 +19,9 @@ of N.
 Colour grading (not in the reference): a plugin's ``initialize`` (or its ``OVERRIDE``, or the caller's ``args``) leaves an ``ar.Grade`` — or a
 callable ``grade(args)`` — in ``args.grade``; ``--grade`` / ``--grade_lut`` / ``--grade_lut_mix`` build a static one.  Every rendered frame is
 then graded on the device in front of the quantiser (render.render_graded).
+
+Lens effects (not in the reference): likewise an ``ar.Lens`` — or a callable ``lens(args)`` — in ``args.lens``, or a static ``--lens``: bloom,
+sharpen and vignette on every rendered frame's fp32 image, in front of the grade (render.render_lensed).
 """
 import argparse
 import gc
@@ -91,6 +94,14 @@ GRADE_FLAGS = (
     ("--grade_lut_mix", dict(type=float, default=1.0, help="weight of --grade_lut, 0 .. 1")),
     ("--grade", dict(type=str, default=None, dest="grade_spec",
                      help='a static grade, e.g. "exposure=0.3,saturation=1.2,gamma=0.9,hue=15" (keys: ' + ", ".join(ar.grade.SPEC_KEYS) + ")")),
+)
+
+# (lens effects, audioreactive/lens.py + csrc/lens.hip: one static flag that builds a one-row ar.Lens; a modulated lens comes from the plugin
+# as ``args.lens``.  Without either the render makes exactly the calls it makes without this flag)
+LENS_FLAGS = (
+    ("--lens", dict(type=str, default=None, dest="lens_spec",
+                    help='static lens effects, e.g. "bloom=0.8,bloom_size=0.03,bloom_threshold=0.6,sharpen=0.4,vignette=0.3" (keys: '
+                         + ", ".join(ar.lens.SPEC_KEYS) + ")")),
 )
 
 
@@ -340,6 +351,7 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     # (generate() keeps the reference's parameter list: a colour grade arrives in the namespace — ``args.grade`` set by the plugin's
     # initialize, by its OVERRIDE or by the caller, and the --grade / --grade_lut flags —; resolved on rank 0, after initialize)
     grade = _grade_of(args) if rank == 0 else None
+    lens = _lens_of(args) if rank == 0 else None  # (``args.lens`` / --lens, the same way)
 
     if rank == 0:
         print("\ngenerating latents...")
@@ -385,6 +397,8 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         shard = (lo, hi, n_frames)
         if sharding.broadcast_object(grade is not None if rank == 0 else None):  # (a job without a grade adds this one object, nothing else)
             grade = _broadcast_grade(grade, lo, hi)
+        if sharding.broadcast_object(lens is not None if rank == 0 else None):  # (likewise: a job without a lens adds this one object)
+            lens = _broadcast_lens(lens, lo, hi)
 
     # (reference :191-192.)  The job's one collection — 45-70 ms on this heap.  Full on purpose where it runs: young-generation collections
     # (tried in round 5) leave the preprocessing's cyclic garbage, device tensors among it, alive, and a render that has to LOAD its generator
@@ -418,13 +432,13 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # ... and so does a delivery size (--deliver_size / --deliver_filter / --deliver_fit); without one, the calls are those of a job
         # that has never heard of it
         resize = _resize_of(args)
-        if grade is not None:
+        if grade is not None or lens is not None:  # (render_lensed without a lens is render_graded, call for call)
             pix_fmt = getattr(args, "pipe_pix_fmt", None)
             if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
                 pix_fmt = f"mjpeg:{args.mjpeg_quality}"
-            written = render.render_graded(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
+            written = render.render_lensed(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
                                            bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt,
-                                           fold=fold if subframes > 1 else None, resize=resize, grade=grade)
+                                           fold=fold if subframes > 1 else None, resize=resize, grade=grade, lens=lens)
         elif resize is not None:
             written = _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
                                         output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
@@ -503,6 +517,43 @@ def _broadcast_grade(grade, lo, hi):
     return ar.Grade.from_table(table, lut)
 
 
+def _lens_of(args):
+    """The lens a namespace asks for, or None.  ``args.lens``: an ar.Lens, a callable ``lens(args) -> ar.Lens`` (evaluated here: after
+    initialize), or a --lens string; ``lens_spec``: the CLI flag, which builds a one-row lens.  A --lens string next to a plugin's lens is
+    refused: two lenses do not compose into one row."""
+    lens = getattr(args, "lens", None)
+    spec = getattr(args, "lens_spec", None)
+    if isinstance(lens, str):
+        lens = ar.Lens(**ar.lens.parse_spec(lens))
+    elif lens is not None and not isinstance(lens, ar.Lens):
+        if not callable(lens):
+            raise TypeError(f"args.lens must be an ar.Lens or a callable lens(args) -> ar.Lens, got {type(lens).__name__}")
+        lens = lens(args)
+        if lens is not None and not isinstance(lens, ar.Lens):
+            raise TypeError(f"args.lens(args) must return an ar.Lens, got {type(lens).__name__}")
+    if lens is None:
+        return ar.Lens(**ar.lens.parse_spec(spec)) if spec else None
+    if spec:
+        raise ValueError("--lens cannot be combined with the plugin's lens (two lenses do not compose into one row): set it in the plugin")
+    return lens
+
+
+def _broadcast_lens(lens, lo, hi):
+    """One process per GPU: rank 0's lens reaches every rank — the row table and the per-row sizes are broadcast and cut to this rank's
+    frames [lo, hi) (a one-row table is kept as it is), together with the whole table's ``plan_max``: every rank derives the reduction,
+    the radii and the taps of a frame that the one-rank job derives, also when bloom_size or sharpen_radius is modulated.  (A helper of
+    its own, like _broadcast_grade.)"""
+    rank, _ = sharding.rank_world()
+    table, size, sigma, plan_max = sharding.broadcast_object((lens.table, lens.bloom_size, lens.sharpen_sigma, lens.plan_max) if rank == 0 else None)
+    if table.shape[0] != 1:
+        if hi > table.shape[0]:
+            raise RuntimeError(f"the lens's table has {table.shape[0]} rows, this rank renders the frames {lo} .. {hi}")
+        if hi == lo:
+            return ar.Lens.from_tables(table[:1], size[:1], sigma[:1], plan_max)  # (a rank without frames: never applied)
+        table, size, sigma = table[lo:hi], size[lo:hi], sigma[lo:hi]
+    return ar.Lens.from_tables(table, size, sigma, plan_max)
+
+
 def _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
                       randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt, mjpeg_quality, fold, resize):
     """``_render`` for a job with a delivery size (its own parameter list is pinned): render.render_delivered, on one GPU or a shard."""
@@ -552,7 +603,7 @@ def load_plugin(audioreactive_file):
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS:
+    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS + LENS_FLAGS:
         parser.add_argument(flag, **kwargs)
     return parser
 
@@ -585,7 +636,7 @@ def main(argv=None):
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     settings.pop("mjpeg_quality", None)
     for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit", "grade", "grade_spec", "grade_lut",
-                "grade_lut_mix"):
+                "grade_lut_mix", "lens", "lens_spec"):
         settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)

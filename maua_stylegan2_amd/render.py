@@ -34,6 +34,8 @@ colour conversion, at 16 bits on the deep formats; the sink and the transports s
 Opt-in colour grade (audioreactive/grade.py's Grade, ``render_graded``): the lanes keep the fp32 image and every rendered frame is graded on
 the device by its row of the grade's table (grade_frames: ASC CDL, a 3 x 3 matrix, a 3-D LUT) before any of the above — the 8-bit formats
 continue with the frames the quantiser gives for the graded image, the deep formats with the image graded in place.
+Opt-in lens effects (audioreactive/lens.py's Lens, ``render_lensed``): bloom, sharpen and vignette on the same fp32 image, per rendered
+frame by its row of the lens's table (lens_frames), in front of the grade.
 """
 import collections
 import contextlib
@@ -525,6 +527,75 @@ def grade_frames(images, grade_rows, lut, scratch, out="u8"):
             _lib.check(lib.maua_grade_to_u8(images.data_ptr(), u8.data_ptr(), b, h, w, grade_rows.data_ptr(), stride, _lib.ptr(lut), lut_n,
                                             _lib.stream_ptr(dev)), "maua_grade_to_u8")
     return u8
+
+
+class LensOperands:
+    """A render's lens on one device (_lens_operands): the Lens, whether its table holds a row per rendered frame, and — per frame
+    size, the plan rule needs the height; _render_shard resolves the generated size before it opens the sink — the device tables, a one-row table repeated to a batch so that every
+    launch finds a row and a half-kernel per frame."""
+
+    def __init__(self, lens, per_frame, batch_size, dev):
+        self.lens, self.per_frame, self.batch_size, self.dev = lens, per_frame, max(batch_size, 1), dev
+        self._sized = {}
+
+    def sized(self, h, w):
+        """(rows, d, bloom radius, bloom taps, sharpen radius, sharpen taps) for frames of h x w."""
+        if (h, w) not in self._sized:
+            rows, d, rb, bt, rs, st = self.lens.operands(self.dev, h, w)
+            if not self.per_frame:
+                rows, bt, st = (t.expand(self.batch_size, t.shape[1]).contiguous() for t in (rows, bt, st))
+            self._sized[(h, w)] = (rows, d, rb, bt, rs, st)
+        return self._sized[(h, w)]
+
+
+def lens_frames(images, lens_ops, first, count, scratch):
+    """fp32 [b, 3, H, W] device images (the generator's output; b == count) through the lens of csrc/lens.hip, IN PLACE, on the current
+    (= producing) stream: bloom (highlights extracted and averaged over d x d blocks, that map blurred by the frame's Gaussian, added back
+    bilinearly), sharpen / soften (against a short Gaussian of the image) and vignette; include/maua_hip.h states the arithmetic,
+    audioreactive/lens.py's Lens builds the operands.  ``lens_ops``: LensOperands; ``first``: the batch's first rendered frame (its rows
+    are [first, first + count) of a per-frame table).  The bloom chain (extract, blur) is launched only when some row of the JOB has a
+    bloom, the sharpen's blur only when some row has a sharpen, nothing at all for a lens that is the identity throughout; frames whose
+    row is the identity come out as they went in, bit for bit.  The reduced maps and the soft image live in ``scratch``, keyed by the
+    input buffer (the protocol of crop_resize_for_delivery)."""
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"lens_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    b, _, h, w = images.shape
+    if b != count:
+        raise RuntimeError(f"lens_frames: {b} images for {count} frames")
+    lens = lens_ops.lens
+    if b == 0 or lens.is_identity:
+        return images
+    dev = images.device
+    rows, d, rb, btaps, rs, staps = lens_ops.sized(h, w)
+    lo = first if lens_ops.per_frame else 0
+    if lo < 0 or lo + b > rows.shape[0]:
+        raise RuntimeError(f"lens_frames: the frames {lo} .. {lo + b} are not inside the {rows.shape[0]} rows of the lens")
+    rows, btaps, staps = rows[lo: lo + b], btaps[lo: lo + b], staps[lo: lo + b]
+    lib = _lib.load()
+    st = _lib.stream_ptr(dev)
+    bloom = soft = None
+    bh, bw = -(-h // d), -(-w // d)
+    with th.cuda.device(dev):
+        if lens.has_bloom:
+            key = ("lens-bloom", images.data_ptr(), b, bh, bw)
+            maps = scratch.get(key)
+            if maps is None:
+                maps = scratch[key] = th.empty((2, b, 3, bh, bw), dtype=th.float32, device=dev)
+            _lib.check(lib.maua_lens_extract_f32(images.data_ptr(), maps[0].data_ptr(), b, h, w, d, rows.data_ptr(), rows.stride(0), st),
+                       "maua_lens_extract_f32")
+            _lib.check(lib.maua_lens_blur_f32(maps[0].data_ptr(), maps[1].data_ptr(), b, 3, bh, bw, rb, btaps.data_ptr(), btaps.stride(0), st),
+                       "maua_lens_blur_f32")
+            bloom = maps[1]
+        if lens.has_sharpen:
+            key = ("lens-soft", images.data_ptr(), b, h, w)
+            soft = scratch.get(key)
+            if soft is None:
+                soft = scratch[key] = th.empty((b, 3, h, w), dtype=th.float32, device=dev)
+            _lib.check(lib.maua_lens_blur_f32(images.data_ptr(), soft.data_ptr(), b, 3, h, w, rs, staps.data_ptr(), staps.stride(0), st),
+                       "maua_lens_blur_f32")
+        _lib.check(lib.maua_lens_apply_f32(images.data_ptr(), images.data_ptr(), b, h, w, rows.data_ptr(), rows.stride(0), _lib.ptr(bloom), bh, bw, d,
+                                           _lib.ptr(soft), st), "maua_lens_apply_f32")
+    return images
 
 
 MAX_SUBFRAMES = 16
@@ -1329,6 +1400,41 @@ def _grade_operands(grade, n_rendered, batch_size, dev):
     return rows, grade.lut_table(dev), per_frame
 
 
+def render_lensed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
+                  lens=None):
+    """``render_graded`` with a ``lens`` (audioreactive/lens.py's Lens, or None: render_graded, call for call): the lanes keep the fp32
+    image and every rendered frame passes through lens_frames (bloom, sharpen, vignette; in place) — the whole generated frame (2048 x 1024
+    for out_size 1920), per sub-frame and before the fold, before the resampler —, then through the grade if there is one, then down the
+    existing chain: without a grade the 8-bit formats continue with frames_to_uint8 of the lensed image, the deep formats with the image
+    itself.  The table holds one row, or one row per entry of ``latents`` (with ``_shard``: this rank's block, Lens.slice); anything else
+    is refused before the first batch."""
+    if lens is None:
+        return render_graded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                             rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade)
+    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
+
+
+def _lens_operands(lens, n_rendered, batch_size, dev):
+    """The LensOperands of a render's lens on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
+    if not (hasattr(lens, "operands") and hasattr(lens, "n_rows") and hasattr(lens, "has_bloom")):
+        raise TypeError(f"lens must be an audioreactive Lens, got {type(lens).__name__}")
+    if lens.n_rows not in (1, n_rendered):
+        raise ValueError(f"the lens's table has {lens.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
+    return LensOperands(lens, lens.n_rows != 1 or n_rendered == 1, batch_size, dev)
+
+
+def _lensed_u8(images, scratch):
+    """frames_to_uint8 of a lensed batch into a reusable buffer of ``scratch`` keyed by the input buffer."""
+    b, _, h, w = images.shape
+    key = ("lens-u8", images.data_ptr(), b, h, w)
+    u8 = scratch.get(key)
+    if u8 is None:
+        u8 = scratch[key] = th.empty((b, h, w, 3), dtype=th.uint8, device=images.device)
+    return frames_to_uint8(images, out=u8)
+
+
 def fold_shard_bounds(n_frames, subframes, rank, world):
     """[lo, hi) of a rank's block in RENDERED frames when every delivered frame is folded from ``subframes`` of them: the job is sharded in
     units of delivered frames (sharding.shard_bounds of n_frames / N), so that no group straddles two ranks."""
@@ -1337,9 +1443,9 @@ def fold_shard_bounds(n_frames, subframes, rank, world):
 
 
 def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None):
-    """The body of render_shard / render_folded / render_delivered / render_graded.  ``fold`` None or of one sub-frame, ``resize`` None and
-    ``grade`` None: the plain render, call for call."""
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None, lens=None):
+    """The body of render_shard / render_folded / render_delivered / render_graded / render_lensed.  ``fold`` None or of one sub-frame,
+    ``resize`` None, ``grade`` None and ``lens`` None: the plain render, call for call."""
     width, height = _output_dims(out_size)
     if resize is not None:
         check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
@@ -1375,6 +1481,9 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
     dev = device_of(generator)
     if grade is not None:  # (refused here, before the sink is opened and the first batch is rendered)
         grade_rows, grade_lut, grade_per_frame = _grade_operands(grade, len(latents), batch_size, dev)
+    if lens is not None:  # (likewise)
+        lens_ops = _lens_operands(lens, len(latents), batch_size, dev)
+        lens_ops.sized(*_generated_hw(generator, out_size))  # (a bloom too wide for this frame height is refused here, not inside the first batch)
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
@@ -1403,7 +1512,12 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                 # (a deep format asks for the fp32 image; the keyword is passed on that path only)
                 # (a grade asks for it as well: it works on the fp32 image, and hands the 8-bit chain the frames the quantiser would have)
                 for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
-                                            frame_range=frame_range, **({"frames": "f32"} if deep or grade is not None else {})):
+                                            frame_range=frame_range,
+                                            **({"frames": "f32"} if deep or grade is not None or lens is not None else {})):
+                    if lens is not None:  # (first the lens, then the grade: the glow is graded with the picture it belongs to)
+                        u8 = lens_frames(u8.contiguous(), lens_ops, first, u8.shape[0], scratch)
+                        if grade is None and not deep:
+                            u8 = _lensed_u8(u8, scratch)  # (the quantiser every 8-bit render ends its forward with)
                     if grade is not None:
                         count = u8.shape[0]
                         rows = grade_rows[first: first + count] if grade_per_frame else grade_rows[:count]
@@ -1419,6 +1533,12 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
     return sink.count if sink is not None else 0
+
+
+def _generated_hw(generator, out_size):
+    """(H, W) of the frames the generator produces for ``out_size``: 1920 / 1080 render 2048-px-wide / -high frames."""
+    side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
+    return (side, 2 * side) if out_size == 1920 else (2 * side, side) if out_size == 1080 else (side, side)
 
 
 def _stream_frame_shape(generator, out_size, pix_fmt="rgb24", resize=None):
