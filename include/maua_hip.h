@@ -576,6 +576,45 @@ int maua_lens_blur_f32(const float* src, float* dst, int batch, int planes, int 
 int maua_lens_blur_plan(int h, int w, int radius, const float* src, int* plan);
 int maua_lens_apply_f32(const float* img, float* out, int batch, int h, int w, const float* rows, int row_stride, const float* bloom, int bh,
                         int bw, int d, const float* soft, void* stream);
+/* Frame feedback on the fp32 image (csrc/feedback.hip): the previous OUTPUT frame, warped, scaled and combined under the new one, in front
+ * of the lens, the grade and the quantisers.  (Additive: the ABI version is unchanged.)  Images are the generator's fp32 [B,3,h,w], raw
+ * range [-1, 1], black = -1.  A recurrence: frame i of the call reads out[i - 1]; frame 0 reads `state` ([3,h,w]; state_valid == 0: a
+ * black frame, `state` is not read); the last frame's result is also stored to `state`.
+ *
+ * `rows` is HOST memory, read during the call and never after it: frame i's 16 floats at rows + i * row_stride (row_stride >= 16) travel
+ * to its launch by value, so a captured call keeps the values it was captured with.  A row: the INVERSE matrix in pixels a, b, tx at 0..2
+ * and c, d, ty at 3..5, gain at 6, tint_rgb at 7..9, dry at 10, limit at 11, a "still" flag at 12, three reserved zeros.
+ * Per output pixel (x, y), in fp32, every operation rounded on its own, in this order (nothing is fused):
+ *   cx = (w - 1) * 0.5f, cy = (h - 1) * 0.5f;  dx = x - cx, dy = y - cy
+ *   sx = ((a * dx + b * dy) + tx) + cx,  sy = ((c * dx + d * dy) + ty) + cy;  each clamped to +-2^30 by fminf(fmaxf(s, -2^30), 2^30)
+ *   ix = (int)floorf(sx), fx = sx - floorf(sx);  iy, fy likewise;  the taps are columns ix, ix + 1 and rows iy, iy + 1, each INDEX taken
+ *   through the border rule (border 0 zero: an index outside 0 .. n - 1 is a black tap, -1.0f;  1 replicate: clamped;  2 mirror: reflected
+ *   about the first and last element, period 2 (n - 1), n == 1: index 0;  3 wrap: modulo n) — the same as folding the coordinate, since
+ *   every rule is continuous in it
+ *   top = v00 + fx * (v01 - v00), bottom = v10 + fx * (v11 - v10), p_c = top + fy * (bottom - top)
+ *   u_prev = 0.5f * p_c + 0.5f;  u_cur = 0.5f * cur_c + 0.5f;  g_c = gain * tint_c (rounded once);  A = dry * u_cur, B = g_c * u_prev
+ *   mode 0 add: u = A + B;  1 max: u = fmaxf(A, B);  2 screen: u = 1.0f - (1.0f - clamp01(A)) * (1.0f - clamp01(B)),
+ *   clamp01(a) = fminf(fmaxf(a, 0), 1);   u = fminf(u, limit);   out_c = 2.0f * u - 1.0f
+ * Neutral: a row with gain == 0 and dry == 1 passes its frame through — out = cur bit for bit, NaN payloads included; the frame is the
+ * state of the next one like any other.  Still: a row whose flag is non-zero AND whose matrix is exactly 1, 0, 0, 0, 1, 0.
+ *
+ * Launches, in order, all on `stream`: a run of consecutive still rows (at most 64 frames, a longer run is split) is ONE launch that keeps
+ * a lane's pixels in registers across the run's frames; every other frame is one launch.  The two kinds agree bit for bit on finite
+ * images.  The launch of the last frame stores `out` and `state`; only a call of ONE moving, non-neutral frame with state_valid != 0 —
+ * which gathers from the state it replaces — stores `out` and is followed by one device-to-device copy on `stream`.  No allocation, no
+ * synchronisation: capturable.  out == img (in place) is legal.  Vector instances (16-byte accesses, 4 consecutive pixels of a row per
+ * lane): w % 4 == 0 and img, out and state 16-byte aligned; anything else takes the scalar instances.
+ * maua_feedback_plan reports without launching (host_rows NULL: every row counts as moving): plan[0] launches, plan[1] how many of them are
+ * still runs, plan[2] 1 when w and img allow the vector instances, plan[3], plan[4] bit k set when launch k (of the first 64) is a still
+ * run, plan[5] 1 when the call may be followed by the copy above, plan[6] workgroups per launch, plan[7] the longest still run of a launch.
+ * Refused before any HIP call, outputs untouched: MAUA_EINVAL for a NULL img / out / state / rows (plan: img / plan), batch < 1,
+ * non-positive sizes, mode outside 0 .. 2, border outside 0 .. 3, row_stride < 16, out overlapping img other than out == img, state
+ * overlapping img or out; MAUA_ENOSYS for more than 2^31 - 256 pixels per plane.  The rows are not checked (audioreactive/feedback.py's
+ * Feedback does).  maua_feedback_test_grid_cap (tests only) caps the workgroups of a launch (0: the default) and returns the old cap. */
+int maua_feedback_f32(const float* img, float* out, float* state, int state_valid, int batch, int h, int w, const float* rows, int row_stride,
+                      int mode, int border, void* stream);
+int maua_feedback_plan(int batch, int h, int w, const float* host_rows, int row_stride, const float* img, int* plan);
+int maua_feedback_test_grid_cap(int cap);
 /* Frame delivery at any size (csrc/resample.hip): a separable resampler on packed 3-channel frames, Pillow's Image.resize(size, resample,
  * box) for 8-bit images restated in integers and extended to 16 bits.  (Additive: the ABI version is unchanged.)
  * Per axis, for a source length n, a source interval [in0, in1), an output length m and a filter f of support s (box 0.5, bilinear 1,

@@ -142,6 +142,9 @@ _SIGNATURES = {
     "maua_lens_blur_f32": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "maua_lens_blur_plan": (c_int, [c_int, c_int, c_int, _P, _P]),
     "maua_lens_apply_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, _P]),
+    "maua_feedback_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P]),
+    "maua_feedback_plan": (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P]),
+    "maua_feedback_test_grid_cap": (c_int, [c_int]),
     "maua_resample_coeffs": (c_int, [c_int] * 5 + [_P, _P, c_int]),
     "maua_resample_u8": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, c_int, _P, _P, c_int, _P, _P]),
     "maua_resample_u16": (c_int, [_P, _P] + [c_int] * 9 + [_P, _P, c_int, _P, _P, c_int, _P, _P]),

@@ -5,6 +5,7 @@ from .bars import *  # noqa: F401,F403  (bar_model, bar_viterbi, raw_bars, downb
 from .beat import *  # noqa: F401,F403  (raw_plp, tempogram, pulse, tempo, beats, beat_phase: the predominant local pulse, no counterpart in the reference)
 from .bend import *  # noqa: F401,F403
 from .decompose import *  # noqa: F401,F403  (nmf, decompose, components: spectrogram factorisation, no counterpart in the reference)
+from .feedback import *  # noqa: F401,F403  (Feedback: frame feedback — trails, echo tunnels — on the fp32 image, no counterpart in the reference)
 from .filters import *  # noqa: F401,F403  (sosfilt, sosfiltfilt, bandpass, envelope, bands: recursive filters on the device, no counterpart in the reference)
 from .grade import *  # noqa: F401,F403  (Grade, load_cube, save_cube, lut_from_function: colour grading of the fp32 image, no counterpart in the reference)
 from .harmony import *  # noqa: F401,F403  (viterbi, hmm_posterior, chord_vocabulary, raw_chords, chords, key: chords and key, no counterpart in the reference)

@@ -22,6 +22,10 @@ then graded on the device in front of the quantiser (render.render_graded).
 
 Lens effects (not in the reference): likewise an ``ar.Lens`` — or a callable ``lens(args)`` — in ``args.lens``, or a static ``--lens``: bloom,
 sharpen and vignette on every rendered frame's fp32 image, in front of the grade (render.render_lensed).
+
+Frame feedback (not in the reference): likewise an ``ar.Feedback`` — or a callable ``feedback(args)`` — in ``args.feedback``, or a static
+``--feedback``: every rendered frame is combined with the warped, dimmed previous output, in front of the lens (render.render_fed).  A
+recurrence over the frames: one rank only.  With --subframes N it runs per rendered sub-frame, so ``gain`` compounds N times per written frame.
 """
 import argparse
 import gc
@@ -102,6 +106,14 @@ LENS_FLAGS = (
     ("--lens", dict(type=str, default=None, dest="lens_spec",
                     help='static lens effects, e.g. "bloom=0.8,bloom_size=0.03,bloom_threshold=0.6,sharpen=0.4,vignette=0.3" (keys: '
                          + ", ".join(ar.lens.SPEC_KEYS) + ")")),
+)
+
+# (frame feedback, audioreactive/feedback.py + csrc/feedback.hip: one static flag that builds a one-row ar.Feedback; a modulated one comes
+# from the plugin as ``args.feedback``.  Without either the render makes exactly the calls it makes without this flag)
+FEEDBACK_FLAGS = (
+    ("--feedback", dict(type=str, default=None, dest="feedback_spec",
+                        help='static frame feedback (trails), e.g. "gain=0.92,zoom=1.015,rotate=0.3,mode=max,border=mirror" (keys: '
+                             + ", ".join(ar.feedback.SPEC_KEYS) + "); one rank only")),
 )
 
 
@@ -352,6 +364,10 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     # initialize, by its OVERRIDE or by the caller, and the --grade / --grade_lut flags —; resolved on rank 0, after initialize)
     grade = _grade_of(args) if rank == 0 else None
     lens = _lens_of(args) if rank == 0 else None  # (``args.lens`` / --lens, the same way)
+    feedback = _feedback_of(args) if rank == 0 else None  # (``args.feedback`` / --feedback, the same way)
+    if grouped and world > 1 and sharding.broadcast_object(feedback is not None if rank == 0 else None):
+        # (every rank raises, before the scatter: a shard's first frame needs its predecessor's state — render.render_fed)
+        raise ValueError(render.FEEDBACK_ONE_RANK.format(where=f"this is a {world}-rank job"))
 
     if rank == 0:
         print("\ngenerating latents...")
@@ -432,7 +448,14 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # ... and so does a delivery size (--deliver_size / --deliver_filter / --deliver_fit); without one, the calls are those of a job
         # that has never heard of it
         resize = _resize_of(args)
-        if grade is not None or lens is not None:  # (render_lensed without a lens is render_graded, call for call)
+        if feedback is not None:  # (a job without a feedback makes the calls below, as it always did)
+            pix_fmt = getattr(args, "pipe_pix_fmt", None)
+            if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
+                pix_fmt = f"mjpeg:{args.mjpeg_quality}"
+            written = render.render_fed(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
+                                        bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt,
+                                        fold=fold if subframes > 1 else None, resize=resize, grade=grade, lens=lens, feedback=feedback)
+        elif grade is not None or lens is not None:  # (render_lensed without a lens is render_graded, call for call)
             pix_fmt = getattr(args, "pipe_pix_fmt", None)
             if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
                 pix_fmt = f"mjpeg:{args.mjpeg_quality}"
@@ -538,6 +561,28 @@ def _lens_of(args):
     return lens
 
 
+def _feedback_of(args):
+    """The frame feedback a namespace asks for, or None.  ``args.feedback``: an ar.Feedback, a callable ``feedback(args) -> ar.Feedback``
+    (evaluated here: after initialize), or a --feedback string; ``feedback_spec``: the CLI flag, which builds a one-row feedback.  A
+    --feedback string next to a plugin's feedback is refused: two recurrences do not compose into one row."""
+    feedback = getattr(args, "feedback", None)
+    spec = getattr(args, "feedback_spec", None)
+    if isinstance(feedback, str):
+        feedback = ar.Feedback(**ar.feedback.parse_spec(feedback))
+    elif feedback is not None and not isinstance(feedback, ar.Feedback):
+        if not callable(feedback):
+            raise TypeError(f"args.feedback must be an ar.Feedback or a callable feedback(args) -> ar.Feedback, got {type(feedback).__name__}")
+        feedback = feedback(args)
+        if feedback is not None and not isinstance(feedback, ar.Feedback):
+            raise TypeError(f"args.feedback(args) must return an ar.Feedback, got {type(feedback).__name__}")
+    if feedback is None:
+        return ar.Feedback(**ar.feedback.parse_spec(spec)) if spec else None
+    if spec:
+        raise ValueError("--feedback cannot be combined with the plugin's feedback (two recurrences do not compose into one row): set it "
+                         "in the plugin")
+    return feedback
+
+
 def _broadcast_lens(lens, lo, hi):
     """One process per GPU: rank 0's lens reaches every rank — the row table and the per-row sizes are broadcast and cut to this rank's
     frames [lo, hi) (a one-row table is kept as it is), together with the whole table's ``plan_max``: every rank derives the reduction,
@@ -603,7 +648,7 @@ def load_plugin(audioreactive_file):
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS + LENS_FLAGS:
+    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS + LENS_FLAGS + FEEDBACK_FLAGS:
         parser.add_argument(flag, **kwargs)
     return parser
 
@@ -636,7 +681,7 @@ def main(argv=None):
     settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
     settings.pop("mjpeg_quality", None)
     for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit", "grade", "grade_spec", "grade_lut",
-                "grade_lut_mix", "lens", "lens_spec"):
+                "grade_lut_mix", "lens", "lens_spec", "feedback", "feedback_spec"):
         settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)

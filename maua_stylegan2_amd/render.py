@@ -36,6 +36,8 @@ the device by its row of the grade's table (grade_frames: ASC CDL, a 3 x 3 matri
 continue with the frames the quantiser gives for the graded image, the deep formats with the image graded in place.
 Opt-in lens effects (audioreactive/lens.py's Lens, ``render_lensed``): bloom, sharpen and vignette on the same fp32 image, per rendered
 frame by its row of the lens's table (lens_frames), in front of the grade.
+Opt-in frame feedback (audioreactive/feedback.py's Feedback, ``render_fed``): the previous output frame fed back under every rendered frame
+(feedback_frames: a recurrence over the frames, chained across the lanes' streams by events), in front of the lens.  One rank only.
 """
 import collections
 import contextlib
@@ -595,6 +597,79 @@ def lens_frames(images, lens_ops, first, count, scratch):
                        "maua_lens_blur_f32")
         _lib.check(lib.maua_lens_apply_f32(images.data_ptr(), images.data_ptr(), b, h, w, rows.data_ptr(), rows.stride(0), _lib.ptr(bloom), bh, bw, d,
                                            _lib.ptr(soft), st), "maua_lens_apply_f32")
+    return images
+
+
+class FeedbackOperands:
+    """A render's feedback on one device (_feedback_operands): the Feedback, whether its table holds a row per rendered frame, and what
+    outlives a batch — the persistent ``state`` [3, H, W] (the last output frame; allocated by the render before the lanes start, NOT a lane buffer:
+    a lane's image is overwritten by that lane's next replay while the following batch, on another lane, still has to read it), whether it
+    holds a frame yet, and the event recorded behind the last batch's feedback (feedback_frames chains the lanes' streams on it)."""
+
+    def __init__(self, feedback, per_frame, batch_size, dev):
+        self.feedback, self.per_frame, self.batch_size, self.dev = feedback, per_frame, max(batch_size, 1), dev
+        self.state = None
+        self.state_valid = False
+        self.done = None
+        self._sized = {}
+
+    def sized(self, h, w):
+        """(rows — float32 [n, 16] on the host, a one-row table repeated to a batch —, mode, border) for frames of h x w."""
+        if (h, w) not in self._sized:
+            rows, mode, border = self.feedback.operands(self.dev, h, w)
+            if not self.per_frame:
+                rows = np.ascontiguousarray(np.broadcast_to(rows, (self.batch_size, rows.shape[1])))
+            self._sized[(h, w)] = (np.ascontiguousarray(rows, np.float32), mode, border)
+        return self._sized[(h, w)]
+
+    def allocate(self, h, w):
+        """The state buffer for frames of h x w, on the current stream (the render's own, which the lanes' streams wait for when they
+        start and which waits for them when they finish: the allocator may hand the block on only after that); a new size starts
+        from black."""
+        if self.state is None or tuple(self.state.shape) != (3, h, w):
+            self.state, self.state_valid = th.empty((3, h, w), dtype=th.float32, device=self.dev), False
+        return self.state
+
+
+def feedback_frames(images, ops, first, count, scratch):
+    """fp32 [b, 3, H, W] device images (the generator's output; b == count) through the frame feedback of csrc/feedback.hip, IN PLACE, on
+    the current (= producing) stream: frame i of the batch is combined with the warped, scaled frame i - 1 of the RESULT, the batch's
+    first frame with the last result of the previous batch (``ops.state``; black before the render's first frame); include/maua_hip.h
+    states the arithmetic, audioreactive/feedback.py's Feedback builds the rows.  ``ops``: FeedbackOperands; ``first``: the batch's first
+    rendered frame (its rows are [first, first + count) of a per-frame table).  Batches must arrive in frame order.  Nothing is launched
+    for a feedback that is neutral throughout.  ``scratch`` is not used: the only buffer that outlives the call is the state.
+
+    Cross-lane ordering.  Consecutive batches run on different lane streams, and this is a recurrence: before its launches a batch's
+    stream waits for the event the previous batch recorded behind its own (``ops.done``), and records a new one behind them.  Why
+    ``state`` is safe to overwrite when this batch's last launch does so: every access to it — the read by a batch's first launch, the
+    write by its last — is one of the launches strung on that chain of events, batch after batch, and within a batch the launches are in
+    stream order; so the only launch that reads the old state after the previous batch wrote it is this batch's first, which precedes
+    this batch's last on the same stream, and the next reader waits for the event recorded after the write.  Nothing else reads it: the
+    lens, the grade and the quantisers work on the lane's image."""
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"feedback_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    del scratch
+    b, _, h, w = images.shape
+    if b != count:
+        raise RuntimeError(f"feedback_frames: {b} images for {count} frames")
+    if b == 0 or ops.feedback.is_identity:
+        return images
+    dev = images.device
+    rows, mode, border = ops.sized(h, w)
+    lo = first if ops.per_frame else 0
+    if lo < 0 or lo + b > rows.shape[0]:
+        raise RuntimeError(f"feedback_frames: the frames {lo} .. {lo + b} are not inside the {rows.shape[0]} rows of the feedback")
+    rows = rows[lo: lo + b]
+    ops.allocate(h, w)  # (the render has done so on its own stream before the lanes started)
+    lib = _lib.load()
+    with th.cuda.device(dev):
+        stream = th.cuda.current_stream(dev)
+        if ops.done is not None:
+            stream.wait_event(ops.done)
+        _lib.check(lib.maua_feedback_f32(images.data_ptr(), images.data_ptr(), ops.state.data_ptr(), int(ops.state_valid), b, h, w,
+                                         rows.ctypes.data, rows.strides[0] // 4, mode, border, _lib.stream_ptr(dev)), "maua_feedback_f32")
+        ops.state_valid = True
+        ops.done = stream.record_event()
     return images
 
 
@@ -1425,6 +1500,38 @@ def _lens_operands(lens, n_rendered, batch_size, dev):
     return LensOperands(lens, lens.n_rows != 1 or n_rendered == 1, batch_size, dev)
 
 
+def render_fed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+               bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
+               lens=None, feedback=None):
+    """``render_lensed`` with a ``feedback`` (audioreactive/feedback.py's Feedback, or None: render_lensed, call for call): the lanes keep
+    the fp32 image and every rendered frame passes through feedback_frames (the previous output fed back under it; in place) — per
+    sub-frame and before the fold —, then through the lens and the grade if there are any (the trail is glowed and graded with the picture
+    it belongs to; the state is the un-lensed image, so a bloom is not fed back into itself), then down the existing chain: without lens
+    and grade the 8-bit formats continue with frames_to_uint8 of the image, the deep formats with the image itself.  The table holds one
+    row, or one row per entry of ``latents``; anything else is refused before the first batch.
+
+    One rank only: a shard's first frame needs the state its predecessor leaves behind, so a job of more than one rank, or a ``_shard``
+    that does not start at frame 0, is refused with a ValueError before the sink is opened."""
+    if feedback is None:
+        return render_lensed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                             rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
+    return _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                          rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens, feedback=feedback)
+
+
+FEEDBACK_ONE_RANK = ("a frame feedback is a recurrence over the frames: a shard's first frame needs the state its predecessor leaves behind, "
+                     "which only a render that starts at frame 0 on its own has ({where}).  Render a feedback on one rank (one process, one GPU)")
+
+
+def _feedback_operands(feedback, n_rendered, batch_size, dev):
+    """The FeedbackOperands of a render's feedback on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
+    if not (hasattr(feedback, "operands") and hasattr(feedback, "n_rows") and hasattr(feedback, "border")):
+        raise TypeError(f"feedback must be an audioreactive Feedback, got {type(feedback).__name__}")
+    if feedback.n_rows not in (1, n_rendered):
+        raise ValueError(f"the feedback's table has {feedback.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
+    return FeedbackOperands(feedback, feedback.n_rows != 1 or n_rendered == 1, batch_size, dev)
+
+
 def _lensed_u8(images, scratch):
     """frames_to_uint8 of a lensed batch into a reusable buffer of ``scratch`` keyed by the input buffer."""
     b, _, h, w = images.shape
@@ -1444,8 +1551,17 @@ def fold_shard_bounds(n_frames, subframes, rank, world):
 
 def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
                   bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None, lens=None):
-    """The body of render_shard / render_folded / render_delivered / render_graded / render_lensed.  ``fold`` None or of one sub-frame,
-    ``resize`` None, ``grade`` None and ``lens`` None: the plain render, call for call."""
+    """What render_shard / render_folded / render_delivered / render_graded / render_lensed call: _render_frames without a feedback (this
+    parameter list is pinned; the feedback is _render_frames' last keyword)."""
+    return _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                          rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
+
+
+def _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                   bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None, lens=None,
+                   feedback=None):
+    """The body of render_shard / render_folded / render_delivered / render_graded / render_lensed / render_fed.  ``fold`` None or of one
+    sub-frame, ``resize`` None, ``grade`` None, ``lens`` None and ``feedback`` None: the plain render, call for call."""
     width, height = _output_dims(out_size)
     if resize is not None:
         check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
@@ -1478,12 +1594,19 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
         raise ValueError(f"{n_frames} rendered frames (this rank's: {lo} .. {hi}) are not whole groups of {subframes} sub-frames")
     # what the sink and the transports count: delivered frames — n_frames and batch_size themselves without a fold
     n_out, batch_out = n_frames // subframes, batch_size // subframes
+    if feedback is not None and (world > 1 or lo > 0):  # (before the sink is opened: no file is created)
+        raise ValueError(FEEDBACK_ONE_RANK.format(where=f"this shard starts at frame {lo} of a {world}-rank job"))
     dev = device_of(generator)
     if grade is not None:  # (refused here, before the sink is opened and the first batch is rendered)
         grade_rows, grade_lut, grade_per_frame = _grade_operands(grade, len(latents), batch_size, dev)
     if lens is not None:  # (likewise)
         lens_ops = _lens_operands(lens, len(latents), batch_size, dev)
         lens_ops.sized(*_generated_hw(generator, out_size))  # (a bloom too wide for this frame height is refused here, not inside the first batch)
+    if feedback is not None:
+        feedback_ops = _feedback_operands(feedback, len(latents), batch_size, dev)
+        if not feedback.is_identity:
+            feedback_ops.sized(*_generated_hw(generator, out_size))
+            feedback_ops.allocate(*_generated_hw(generator, out_size))  # (on this stream, before the lanes start)
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
@@ -1513,11 +1636,14 @@ def _render_shard(generator, latents, noise, offset, duration, batch_size, out_s
                 # (a grade asks for it as well: it works on the fp32 image, and hands the 8-bit chain the frames the quantiser would have)
                 for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
                                             frame_range=frame_range,
-                                            **({"frames": "f32"} if deep or grade is not None or lens is not None else {})):
+                                            **({"frames": "f32"} if deep or grade is not None or lens is not None or feedback is not None
+                                               else {})):
+                    if feedback is not None:  # (first of all: the state is the un-lensed image, the trail is glowed and graded with its picture)
+                        u8 = feedback_frames(u8.contiguous(), feedback_ops, first, u8.shape[0], scratch)
                     if lens is not None:  # (first the lens, then the grade: the glow is graded with the picture it belongs to)
                         u8 = lens_frames(u8.contiguous(), lens_ops, first, u8.shape[0], scratch)
-                        if grade is None and not deep:
-                            u8 = _lensed_u8(u8, scratch)  # (the quantiser every 8-bit render ends its forward with)
+                    if (lens is not None or feedback is not None) and grade is None and not deep:
+                        u8 = _lensed_u8(u8, scratch)  # (the quantiser every 8-bit render ends its forward with)
                     if grade is not None:
                         count = u8.shape[0]
                         rows = grade_rows[first: first + count] if grade_per_frame else grade_rows[:count]
