@@ -18,13 +18,13 @@ of N.
 
 Colour grading (not in the reference): a plugin's ``initialize`` (or its ``OVERRIDE``, or the caller's ``args``) leaves an ``ar.Grade`` — or a
 callable ``grade(args)`` — in ``args.grade``; ``--grade`` / ``--grade_lut`` / ``--grade_lut_mix`` build a static one.  Every rendered frame is
-then graded on the device in front of the quantiser (render.render_graded).
+then graded on the device in front of the quantiser (render.grade_frames).
 
 Lens effects (not in the reference): likewise an ``ar.Lens`` — or a callable ``lens(args)`` — in ``args.lens``, or a static ``--lens``: bloom,
-sharpen and vignette on every rendered frame's fp32 image, in front of the grade (render.render_lensed).
+sharpen and vignette on every rendered frame's fp32 image, in front of the grade (render.lens_frames).
 
 Frame feedback (not in the reference): likewise an ``ar.Feedback`` — or a callable ``feedback(args)`` — in ``args.feedback``, or a static
-``--feedback``: every rendered frame is combined with the warped, dimmed previous output, in front of the lens (render.render_fed).  A
+``--feedback``: every rendered frame is combined with the warped, dimmed previous output, in front of the lens (render.feedback_frames).  A
 recurrence over the frames: one rank only.  With --subframes N it runs per rendered sub-frame, so ``gain`` compounds N times per written frame.
 """
 import argparse
@@ -84,15 +84,15 @@ CLI_FLAGS = (
     ("--shutter", dict(type=str, default="box", help="box, tent or N comma-separated integer weights, e.g. 1,1,0,0")),
     ("--shutter_light", dict(type=str, default="encoded", choices=render.SHUTTER_LIGHTS)),
 )
-# (delivery at any size, render.FrameResize: every frame is resampled on the device before the colour conversion; without --deliver_size
-# the render makes exactly the calls it makes without these flags.  A table of its own: the order of CLI_FLAGS is pinned by tests)
+# (delivery at any size, render.FrameResize: every frame is resampled on the device before the colour conversion.
+# A table of its own: tests hold the order of CLI_FLAGS)
 DELIVERY_FLAGS = (
     ("--deliver_size", dict(type=str, default=None, help="WIDTHxHEIGHT of the written video, e.g. 1920x1080 (default: the generator's)")),
     ("--deliver_filter", dict(type=str, default="lanczos", choices=render.RESIZE_FILTERS)),
     ("--deliver_fit", dict(type=str, default="crop", choices=render.RESIZE_FITS)),
 )
 # (colour grading, audioreactive/grade.py + csrc/grade.hip: static flags that build a one-row ar.Grade; a modulated grade comes from the
-# plugin as ``args.grade``.  Without any of them the render makes exactly the calls it makes without these flags.  A table of its own again)
+# plugin as ``args.grade``.  A table of its own again)
 GRADE_FLAGS = (
     ("--grade_lut", dict(type=str, default=None, help="a 3-D .cube file applied to every frame after the CDL and the matrix")),
     ("--grade_lut_mix", dict(type=float, default=1.0, help="weight of --grade_lut, 0 .. 1")),
@@ -101,7 +101,7 @@ GRADE_FLAGS = (
 )
 
 # (lens effects, audioreactive/lens.py + csrc/lens.hip: one static flag that builds a one-row ar.Lens; a modulated lens comes from the plugin
-# as ``args.lens``.  Without either the render makes exactly the calls it makes without this flag)
+# as ``args.lens``)
 LENS_FLAGS = (
     ("--lens", dict(type=str, default=None, dest="lens_spec",
                     help='static lens effects, e.g. "bloom=0.8,bloom_size=0.03,bloom_threshold=0.6,sharpen=0.4,vignette=0.3" (keys: '
@@ -109,7 +109,7 @@ LENS_FLAGS = (
 )
 
 # (frame feedback, audioreactive/feedback.py + csrc/feedback.hip: one static flag that builds a one-row ar.Feedback; a modulated one comes
-# from the plugin as ``args.feedback``.  Without either the render makes exactly the calls it makes without this flag)
+# from the plugin as ``args.feedback``)
 FEEDBACK_FLAGS = (
     ("--feedback", dict(type=str, default=None, dest="feedback_spec",
                         help='static frame feedback (trails), e.g. "gain=0.92,zoom=1.015,rotate=0.3,mode=max,border=mirror" (keys: '
@@ -161,7 +161,7 @@ def load_generator(ckpt, is_stylegan1, G_res, out_size, noconst, latent_dim, n_m
     with th.device(th.device("cuda", th.cuda.current_device())):
         generator = Generator(G_res, latent_dim, n_mlp, channel_multiplier=channel_multiplier, constant_input=not noconst,
                               checkpoint=ckpt if rank == 0 else None, output_size=out_size, base_res_factor=base_res_factor)
-    generator = generator.cuda()  # (a no-op for what is there already; anything a constructor pinned to the CPU follows)
+    generator = generator.cuda()  # (a no-op for what is there already; anything a constructor left on the CPU follows)
     return sharding.broadcast_module(generator).eval()
 
 
@@ -366,7 +366,7 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     lens = _lens_of(args) if rank == 0 else None  # (``args.lens`` / --lens, the same way)
     feedback = _feedback_of(args) if rank == 0 else None  # (``args.feedback`` / --feedback, the same way)
     if grouped and world > 1 and sharding.broadcast_object(feedback is not None if rank == 0 else None):
-        # (every rank raises, before the scatter: a shard's first frame needs its predecessor's state — render.render_fed)
+        # (every rank raises, before the scatter: a shard's first frame needs its predecessor's state — render.render_frames)
         raise ValueError(render.FEEDBACK_ONE_RANK.format(where=f"this is a {world}-rank job"))
 
     if rank == 0:
@@ -443,33 +443,12 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
         # randomize_noise: every rank generates the maps of its frames from the job's one broadcast seed (Generator.random_noise)
         generator.noise_seed = seed + 3
     try:
-        # generate() keeps the reference's parameter list: the pipe format arrives in the namespace (--pipe_pix_fmt, a plugin's OVERRIDE,
-        # a caller's own ``args``) or through $MAUA_PIPE_PIX_FMT
-        # ... and so does a delivery size (--deliver_size / --deliver_filter / --deliver_fit); without one, the calls are those of a job
-        # that has never heard of it
-        resize = _resize_of(args)
-        if feedback is not None:  # (a job without a feedback makes the calls below, as it always did)
-            pix_fmt = getattr(args, "pipe_pix_fmt", None)
-            if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
-                pix_fmt = f"mjpeg:{args.mjpeg_quality}"
-            written = render.render_fed(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
-                                        bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt,
-                                        fold=fold if subframes > 1 else None, resize=resize, grade=grade, lens=lens, feedback=feedback)
-        elif grade is not None or lens is not None:  # (render_lensed without a lens is render_graded, call for call)
-            pix_fmt = getattr(args, "pipe_pix_fmt", None)
-            if pix_fmt == "mjpeg" and getattr(args, "mjpeg_quality", None) is not None:
-                pix_fmt = f"mjpeg:{args.mjpeg_quality}"
-            written = render.render_lensed(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
-                                           bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt,
-                                           fold=fold if subframes > 1 else None, resize=resize, grade=grade, lens=lens)
-        elif resize is not None:
-            written = _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
-                                        output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
-                                        getattr(args, "mjpeg_quality", None), fold if subframes > 1 else None, resize)
-        else:
-            written = _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size,
-                              output_file, randomize_noise, ffmpeg_preset, shard, getattr(args, "pipe_pix_fmt", None),
-                              getattr(args, "mjpeg_quality", None), *((fold,) if subframes > 1 else ()))
+        # generate() keeps the reference's parameter list: the pipe format, the fold and the delivery size arrive in the namespace
+        # (the flags, a plugin's OVERRIDE, a caller's own ``args``) or, for some jobs, through the environment (_tail_options)
+        pix_fmt, fold, resize = _tail_options(args, fold, grade, lens, feedback)
+        written = render.render_frames(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
+                                       bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt, fold=fold, resize=resize,
+                                       grade=grade, lens=lens, feedback=feedback)
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -528,7 +507,7 @@ def _grade_of(args):
 
 def _broadcast_grade(grade, lo, hi):
     """One process per GPU: rank 0's grade reaches every rank — the row table is broadcast and cut to this rank's frames [lo, hi) (a one-row
-    table is kept as it is), the LUT is broadcast whole.  (A helper of its own: _scatter_from_rank0's parameter list is pinned.)"""
+    table is kept as it is), the LUT is broadcast whole."""
     rank, _ = sharding.rank_world()
     table, lut = sharding.broadcast_object((grade.table, grade.lut) if rank == 0 else None)
     if table.shape[0] != 1:
@@ -599,34 +578,26 @@ def _broadcast_lens(lens, lo, hi):
     return ar.Lens.from_tables(table, size, sigma, plan_max)
 
 
-def _render_delivered(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
-                      randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt, mjpeg_quality, fold, resize):
-    """``_render`` for a job with a delivery size (its own parameter list is pinned): render.render_delivered, on one GPU or a shard."""
-    if pipe_pix_fmt == "mjpeg" and mjpeg_quality is not None:
-        pipe_pix_fmt = f"mjpeg:{mjpeg_quality}"
-    return render.render_delivered(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation, bends,
-                                   rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt, fold=fold, resize=resize)
+def _pipe_format_of(args):
+    """The pipe format a namespace asks for (``pipe_pix_fmt``, ``mjpeg_quality``) as render takes it: the quality of an mjpeg pipe
+    travels in the format's name, ``mjpeg:<quality>``."""
+    pix_fmt, quality = getattr(args, "pipe_pix_fmt", None), getattr(args, "mjpeg_quality", None)
+    return f"mjpeg:{quality}" if pix_fmt == "mjpeg" and quality is not None else pix_fmt
 
 
-def _render(generator, latents, noise, audio_file, offset, duration, batch, truncation, bends, rewrites, out_size, output_file,
-            randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=None, mjpeg_quality=None, fold=None):
-    if pipe_pix_fmt == "mjpeg" and mjpeg_quality is not None:
-        pipe_pix_fmt = f"mjpeg:{mjpeg_quality}"  # (render_shard's parameter list is pinned: the quality travels in the format's name)
-    if fold is not None and fold.subframes > 1:  # (latents and every per-frame input hold N rows per delivered frame)
-        written = render.render_folded(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
-                                       truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt, fold=fold)
-    elif pipe_pix_fmt not in (None, "rgb24"):
-        written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
-                                      truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pipe_pix_fmt)
-    elif shard is None:
-        written = render.render(generator=generator, latents=latents, noise=noise, audio_file=audio_file, offset=offset,
-                                duration=duration, batch_size=batch, truncation=truncation, bends=bends, rewrites=rewrites,
-                                out_size=out_size, output_file=output_file, randomize_noise=randomize_noise,
-                                ffmpeg_preset=ffmpeg_preset)
-    else:  # one process per GPU: the per-frame inputs were scattered, this rank holds frames [lo, hi) only
-        written = render.render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file,
-                                      truncation, bends, rewrites, randomize_noise, ffmpeg_preset, shard)
-    return written
+def _tail_options(args, fold, grade, lens, feedback):
+    """(pipe_pix_fmt, fold, resize) of a job's render: what the namespace says, and for some jobs what the environment says where the
+    namespace is silent ("Render tail": kept as it grew, route by route).  A job with a grade, a lens, a feedback or a
+    --deliver_size reads the namespace alone.  Any other job takes its delivery size from $MAUA_DELIVER_SIZE..., and — unless the
+    namespace sets a fold — its fold from $MAUA_SUBFRAMES... and, where the namespace says rgb24 (the flag's default), its pipe format
+    from $MAUA_PIPE_PIX_FMT.  (A namespace without a ``pipe_pix_fmt`` is $MAUA_PIPE_PIX_FMT for every job: render resolves None.)"""
+    pix_fmt, resize = _pipe_format_of(args), _resize_of(args)
+    if resize is None and grade is None and lens is None and feedback is None:
+        resize = render._resize_from_env()
+        if fold is None:
+            fold = render._fold_from_env()
+            pix_fmt = None if pix_fmt == "rgb24" else pix_fmt
+    return pix_fmt, fold, resize
 
 
 def load_plugin(audioreactive_file):

@@ -1,4 +1,4 @@
-"""Frame rendering loop — mirror of /root/reference/render.py:14-192 ``render(...)`` for MI355X.
+"""Frame rendering loop — mirror of the reference's render.py:14-192 ``render(...)`` for MI355X.
 
 Same signature and batch semantics (slice latents / noise / bend modulation / truncation on dim 0, call the generator
 with ``input_is_latent=True``), different machinery:
@@ -13,31 +13,43 @@ with ``input_is_latent=True``), different machinery:
   DataParallel replicate/scatter/gather per forward       one process per GPU, contiguous frame shards, RCCL gather of
                                                           uint8 frames to rank 0 (maua_stylegan2_amd/sharding.py)
 
-``render_shard`` runs ONE frame loop whatever carries the frames to the sink: a delivery object per transport (_LocalRing on one GPU;
-_HostStore / _GatherStream under a process group) with ``push(u8)`` — one deliverable batch, the producing stream current —,
-``finish(frame_shape)`` — end of this rank's frames, also when it had none — and ``close()`` — safe after a failure, and twice.
+``render_frames`` is the one body of every entry point: ONE frame loop, whatever happens to a batch on the device and whatever carries the
+frames to the sink.  Per batch it is ``delivery.push(tail(first, batch))``:
+  the tail (_FrameTail)   everything between the generator's output and the frames as they leave the device, resolved and refused once,
+                          before the sink is opened; the stages run on the producing stream, each only when its option is set, in the order
+                          feedback -> lens -> grade (or the plain quantiser) -> temporal fold -> crop / resize -> yuv420p / mjpeg — the deep
+                          formats end in frames_to_deep instead of the last three
+  the delivery            an object per transport (_LocalRing on one GPU; _HostStore / _GatherStream under a process group) with
+                          ``push(u8)`` — one deliverable batch, the producing stream current —, ``finish(frame_shape)`` — end of this
+                          rank's frames, also when it had none — and ``close()`` — safe after a failure, and twice.
+The entry points differ in their parameter lists and in what they read from the environment, nothing else: ``render`` (the reference's
+parameter list) and ``render_shard`` take the fold and the delivery size from the environment, ``render_folded`` the delivery size;
+``render_delivered``, ``render_graded``, ``render_lensed`` and ``render_fed`` read neither.  An unset ``pipe_pix_fmt`` is $MAUA_PIPE_PIX_FMT
+for all of them.
 
 Sinks: ffmpeg rawvideo pipe (same pixel format / codec arguments as render.py:58-91) when an ``ffmpeg`` binary exists,
 otherwise raw rgb24 bytes to ``output_file`` (+ ".rgb24"), or a null sink for benchmarking (``output_file=None``).
-Opt-in pipe format ``yuv420p`` (PIPE_PIX_FMTS): the frames are converted to planar YUV 4:2:0 on the device (frames_to_yuv420p) before
-they cross to the host / to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself.
-Opt-in pipe format ``mjpeg`` (``mjpeg:<quality>``): every frame is encoded as one baseline JPEG on the device (frames_to_mjpeg) and travels
-in a fixed-size slot; the sink writes the streams alone, to ``ffmpeg -f mjpeg`` or, without a binary, to a playable Motion-JPEG .avi (avi.py).
-Opt-in deep pipe formats (DEEP_PIX_FMTS: ``rgb48le``, ``yuv420p10le``, ``yuv422p10le``, ``yuv444p10le``): the lanes keep the fp32 image and
-frames_to_deep turns it into 16-bit packed RGB or 10-bit planar BT.709 YUV on the device, so no 8-bit quantiser sits between the generator
-and the encoder (libx265, 10 bits); the frames travel as flat bytes like the yuv420p ones.  Not combinable with a temporal fold.
-Opt-in temporal supersampling (TemporalFold, ``render_folded``; $MAUA_SUBFRAMES for the pinned entries): N rendered sub-frames per delivered
-frame, averaged on the device by fold_frames before any of the above; the sink and the transports then count delivered frames.
-Opt-in delivery size (FrameResize, ``render_delivered``; $MAUA_DELIVER_SIZE / _FILTER / _FIT for the pinned entries): every delivered frame
-is resampled on the device (resize_frames: Lanczos, bicubic, Hamming, bilinear or box; crop, pad or stretch) after the fold and before the
-colour conversion, at 16 bits on the deep formats; the sink and the transports see the delivery size.
-Opt-in colour grade (audioreactive/grade.py's Grade, ``render_graded``): the lanes keep the fp32 image and every rendered frame is graded on
-the device by its row of the grade's table (grade_frames: ASC CDL, a 3 x 3 matrix, a 3-D LUT) before any of the above — the 8-bit formats
-continue with the frames the quantiser gives for the graded image, the deep formats with the image graded in place.
-Opt-in lens effects (audioreactive/lens.py's Lens, ``render_lensed``): bloom, sharpen and vignette on the same fp32 image, per rendered
-frame by its row of the lens's table (lens_frames), in front of the grade.
-Opt-in frame feedback (audioreactive/feedback.py's Feedback, ``render_fed``): the previous output frame fed back under every rendered frame
-(feedback_frames: a recurrence over the frames, chained across the lanes' streams by events), in front of the lens.  One rank only.
+
+The options of the tail, all off by default:
+  pipe format ``yuv420p``   the frames are converted to planar YUV 4:2:0 on the device (frames_to_yuv420p) before they cross to the host /
+                            to rank 0, 1.5 bytes per pixel instead of 3, and the encoder is fed what it would otherwise convert to itself
+  ``mjpeg[:<quality>]``     every frame is encoded as one baseline JPEG on the device (frames_to_mjpeg) and travels in a fixed-size slot; the
+                            sink writes the streams alone, to ``ffmpeg -f mjpeg`` or, without a binary, to a Motion-JPEG .avi (avi.py)
+  deep formats              DEEP_PIX_FMTS: the lanes keep the fp32 image and frames_to_deep turns it into 16-bit packed RGB or 10-bit planar
+                            BT.709 YUV, so no 8-bit quantiser sits between the generator and the encoder (libx265, 10 bits); the frames
+                            travel as flat bytes like the yuv420p ones.  Not combinable with a temporal fold
+  ``fold`` (TemporalFold)   temporal supersampling ($MAUA_SUBFRAMES): N rendered sub-frames per delivered frame, averaged on the device by
+                            fold_frames before the spatial steps; the sink and the transports then count delivered frames
+  ``resize`` (FrameResize)  delivery size ($MAUA_DELIVER_SIZE / _FILTER / _FIT): every delivered frame is resampled on the device
+                            (resize_frames: Lanczos, bicubic, Hamming, bilinear or box; crop, pad or stretch) after the fold and before the
+                            colour conversion, at 16 bits on the deep formats; the sink and the transports see the delivery size
+  ``grade`` (ar.Grade)      the lanes keep the fp32 image and every rendered frame is graded by its row of the grade's table (grade_frames:
+                            ASC CDL, a 3 x 3 matrix, a 3-D LUT) — the 8-bit formats continue with the frames the quantiser gives for the
+                            graded image, the deep formats with the image graded in place
+  ``lens`` (ar.Lens)        bloom, sharpen and vignette on the same fp32 image, per rendered frame by its row of the lens's table
+                            (lens_frames), in front of the grade
+  ``feedback`` (ar.Feedback)  the previous output frame fed back under every rendered frame (feedback_frames: a recurrence over the frames,
+                            chained across the lanes' streams by events), in front of the lens.  One rank only.
 """
 import collections
 import contextlib
@@ -199,35 +211,25 @@ class FrameSink:
         """frame: numpy uint8 [H, W, 3]; wide 2048-px outputs are cropped + resized as render.py:98-105.  A yuv420p sink takes the flat
         planar frame [H * W * 3 / 2] as it is: it was resized on the device before the conversion, neither PIL nor the crop applies.  An
         mjpeg sink takes the flat slot, checks its header and writes the stream alone."""
-        if self.pix_fmt == "mjpeg":
-            slot_bytes = mjpeg_slot_bytes(self.w, self.h)
-            if frame.ndim != 1 or frame.shape[0] != slot_bytes or frame.dtype != np.uint8:
-                raise ValueError(f"an mjpeg frame of {self.w}x{self.h} is a flat uint8 slot of {slot_bytes} bytes, got {frame.dtype} "
-                                 f"{tuple(frame.shape)}")
+        if self.pix_fmt != "rgb24":  # a flat frame: its byte count and how the refusal names it (yuv420p's dtype is not looked at)
+            if self.pix_fmt == "mjpeg":
+                n_bytes, what = mjpeg_slot_bytes(self.w, self.h), "an mjpeg frame of {w}x{h} is a flat uint8 slot of {n} bytes, got {dtype} {shape}"
+            elif self.pix_fmt == "yuv420p":
+                n_bytes, what = self.w * self.h * 3 // 2, "a yuv420p frame of {w}x{h} is a flat array of {n} bytes, got shape {shape}"
+            else:
+                n_bytes = deep_frame_bytes(self.pix_fmt, self.w, self.h)
+                what = "a " + self.pix_fmt + " frame of {w}x{h} is a flat uint8 array of {n} bytes, got {dtype} {shape}"
+            if frame.ndim != 1 or frame.shape[0] != n_bytes or (self.pix_fmt != "yuv420p" and frame.dtype != np.uint8):
+                raise ValueError(what.format(w=self.w, h=self.h, n=n_bytes, dtype=frame.dtype, shape=tuple(frame.shape)))
             frame = np.ascontiguousarray(frame)
-            n, status = (int(v) for v in frame[:8].view("<u4"))
-            if status != 0 or 16 + n > slot_bytes:
-                raise ValueError(f"mjpeg frame {self.count} overflowed its slot: the stream needs {n} bytes, the slot holds {slot_bytes - 16} "
-                                 f"(quality {self.quality if self.quality is not None else 'unknown'}: lower it)")
+            if self.pix_fmt == "mjpeg":  # the slot header: the stream's length and the encoder's status
+                n, status = (int(v) for v in frame[:8].view("<u4"))
+                if status != 0 or 16 + n > n_bytes:
+                    raise ValueError(f"mjpeg frame {self.count} overflowed its slot: the stream needs {n} bytes, the slot holds {n_bytes - 16} "
+                                     f"(quality {self.quality if self.quality is not None else 'unknown'}: lower it)")
+                frame = frame[16: 16 + n]
             if self.proc is not None or self.file is not None:
-                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(frame[16: 16 + n]).cast("B"))
-            self.count += 1
-            return
-        if self.pix_fmt in DEEP_PIX_FMTS:
-            n_bytes = deep_frame_bytes(self.pix_fmt, self.w, self.h)
-            if frame.ndim != 1 or frame.shape[0] != n_bytes or frame.dtype != np.uint8:
-                raise ValueError(f"a {self.pix_fmt} frame of {self.w}x{self.h} is a flat uint8 array of {n_bytes} bytes, got {frame.dtype} "
-                                 f"{tuple(frame.shape)}")
-            if self.proc is not None or self.file is not None:
-                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(np.ascontiguousarray(frame)).cast("B"))
-            self.count += 1
-            return
-        if self.pix_fmt == "yuv420p":
-            if frame.ndim != 1 or frame.shape[0] != self.w * self.h * 3 // 2:
-                raise ValueError(f"a yuv420p frame of {self.w}x{self.h} is a flat array of {self.w * self.h * 3 // 2} bytes, got shape "
-                                 f"{tuple(frame.shape)}")
-            if self.proc is not None or self.file is not None:
-                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(np.ascontiguousarray(frame)).cast("B"))
+                (self.proc.stdin if self.proc is not None else self.file).write(memoryview(frame).cast("B"))
             self.count += 1
             return
         # (a frame that already has the sink's size is written as it is: a delivery size of 2048 px is not the reference's wide output)
@@ -332,25 +334,50 @@ def frames_to_uint8(images, out=None):
     return out
 
 
+def _cached(scratch, key, make):
+    """``scratch[key]``, made on first use.  ``scratch`` is the dict a render hands to every stage of its tail for what the stage wants to
+    find again on the next batch.  A stage keys its buffers by its INPUT buffer: the lanes' batches are in flight concurrently, so there
+    is one output buffer per input buffer."""
+    value = scratch.get(key)
+    if value is None:
+        value = scratch[key] = make()
+    return value
+
+
+def _scratch(scratch, key, shape, dtype, dev):
+    """The reusable device buffer ``scratch[key]`` (_cached), allocated — not initialised — on first use."""
+    return _cached(scratch, key, lambda: th.empty(shape, dtype=dtype, device=dev))
+
+
+def _wide_output_box(out_size, h, w):
+    """(x0, y0, cw, ch, ow, oh) of the built-in delivery of a 1920 / 1080 render's 2048-px frames — 112 px off both ends of the long side,
+    then 1920x1080 / 1080x1920 —, None for every other frame."""
+    if out_size == 1920 and w == 2048:
+        return 112, 0, w - 224, h, 1920, 1080
+    if out_size == 1080 and h == 2048:
+        return 0, 112, w, h - 224, 1080, 1920
+    return None
+
+
+def _require_fp32_images(images, who):
+    """What the stages on the fp32 image take, refused in ``who``'s name."""
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"{who} takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+
+
 def crop_resize_for_delivery(u8, out_size, scratch):
     """The wide-output delivery of reference render.py:97-104 ON THE DEVICE: 2048-px frames of a 1920 / 1080 render are cropped
     (112 px off both ends of the long side) and resized to 1920x1080 / 1080x1920 by maua_crop_resize_u8 = PIL's bilinear resize —
-    the reference (and round 2 here) does it per frame on the host with PIL, a few milliseconds each on rank 0's Python thread.
-    Other frames pass through.  ``scratch``: dict holding the reusable output buffers (one per input buffer: the lanes' frames are
-    in flight concurrently)."""
+    the reference does it per frame on the host with PIL, a few milliseconds each on rank 0's Python thread.
+    Other frames pass through.  ``scratch``: the render's reusable buffers (_cached)."""
     b, h, w, _ = u8.shape
-    if out_size == 1920 and w == 2048:
-        x0, y0, cw, ch, ow, oh = 112, 0, w - 224, h, 1920, 1080
-    elif out_size == 1080 and h == 2048:
-        x0, y0, cw, ch, ow, oh = 0, 112, w, h - 224, 1080, 1920
-    else:
+    box = _wide_output_box(out_size, h, w)
+    if box is None:
         return u8
+    x0, y0, cw, ch, ow, oh = box
     if ow < cw or oh < ch:
         return u8  # not the up-scale the device kernel reproduces: FrameSink.write falls back to PIL on the host
-    key = (u8.data_ptr(), b)
-    out = scratch.get(key)
-    if out is None:
-        out = scratch[key] = th.empty((b, oh, ow, 3), dtype=th.uint8, device=u8.device)
+    out = _scratch(scratch, (u8.data_ptr(), b), (b, oh, ow, 3), th.uint8, u8.device)
     with th.cuda.device(u8.device):
         _lib.check(_lib.load().maua_crop_resize_u8(u8.data_ptr(), out.data_ptr(), b, h, w, x0, y0, cw, ch, ow, oh,
                                                    _lib.stream_ptr(u8.device)), "maua_crop_resize_u8")
@@ -360,17 +387,14 @@ def crop_resize_for_delivery(u8, out_size, scratch):
 def frames_to_yuv420p(u8, scratch):
     """uint8 [b, H, W, 3] device frames (frames_to_uint8 / crop_resize_for_delivery) -> planar YUV 4:2:0 [b, H * W * 3 // 2] uint8 on the
     device, on the current (= producing) stream: per frame the Y plane, then U, then V (I420: ffmpeg's rawvideo yuv420p), BT.601 limited
-    range by maua_rgb_to_yuv420p_u8.  ``scratch``: dict holding the reusable output buffers, the protocol of crop_resize_for_delivery."""
+    range by maua_rgb_to_yuv420p_u8.  ``scratch``: the render's reusable buffers (_cached)."""
     if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != th.uint8 or not u8.is_cuda:
         raise RuntimeError(f"frames_to_yuv420p takes uint8 [b, H, W, 3] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
     b, h, w, _ = u8.shape
     if h % 2 or w % 2:
         raise ValueError(f"yuv420p needs even frame dimensions, got {w}x{h}")
     u8 = u8.contiguous()
-    key = ("yuv420p", u8.data_ptr(), b, h, w)
-    out = scratch.get(key)
-    if out is None:
-        out = scratch[key] = th.empty((b, h * w * 3 // 2), dtype=th.uint8, device=u8.device)
+    out = _scratch(scratch, ("yuv420p", u8.data_ptr(), b, h, w), (b, h * w * 3 // 2), th.uint8, u8.device)
     with th.cuda.device(u8.device):
         _lib.check(_lib.load().maua_rgb_to_yuv420p_u8(u8.data_ptr(), out.data_ptr(), b, h, w, _lib.stream_ptr(u8.device)),
                    "maua_rgb_to_yuv420p_u8")
@@ -380,42 +404,32 @@ def frames_to_yuv420p(u8, scratch):
 def frames_to_mjpeg(u8, scratch, quality):
     """uint8 [b, H, W, 3] device frames -> mjpeg slots [b, mjpeg_slot_bytes(W, H)] uint8 on the device, on the current (= producing) stream:
     per frame a 16-byte slot header (stream length, status) and one baseline JPEG at ``quality`` by maua_jpeg_encode_u8, one restart
-    interval per MCU row.  ``scratch``: dict holding the reusable buffers (the protocol of crop_resize_for_delivery): the slots and the
-    workspace per input buffer — the lanes' batches are encoded concurrently on their own streams, a workspace cannot be shared between
-    them — and the device copy of the JPEG header per (H, W, quality)."""
+    interval per MCU row.  ``scratch``: the render's reusable buffers (_cached): the slots and the workspace per input buffer — the lanes'
+    batches are encoded concurrently on their own streams, a workspace cannot be shared between them — and the device copy of the JPEG
+    header per (H, W, quality)."""
     if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != th.uint8 or not u8.is_cuda:
         raise RuntimeError(f"frames_to_mjpeg takes uint8 [b, H, W, 3] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
     b, h, w, _ = u8.shape
     lib = _lib.load()
     u8 = u8.contiguous()
+    dev = u8.device
     slot_bytes = mjpeg_slot_bytes(w, h)
     restart_mcus = (w + 15) // 16
-    key = ("mjpeg-header", h, w, quality)
-    header = scratch.get(key)
-    if header is None:
+
+    def device_header():
         host = np.empty(1024, np.uint8)
         n = lib.maua_jpeg_header(h, w, quality, restart_mcus, host.ctypes.data, host.size)
         if n <= 0:
             _lib.check(n, "maua_jpeg_header")
-        header = scratch[key] = th.from_numpy(host[:n].copy()).to(u8.device)
-    key = ("mjpeg", u8.data_ptr(), b, h, w, quality)
-    buffers = scratch.get(key)
-    if buffers is None:
-        out = th.empty((b, slot_bytes), dtype=th.uint8, device=u8.device)
-        ws = th.empty(max(int(lib.maua_jpeg_ws_bytes(b, h, w, restart_mcus)), 16), dtype=th.uint8, device=u8.device)
-        buffers = scratch[key] = (out, ws)
-    out, ws = buffers
+        return th.from_numpy(host[:n].copy()).to(dev)
+
+    header = _cached(scratch, ("mjpeg-header", h, w, quality), device_header)
+    out, ws = _cached(scratch, ("mjpeg", u8.data_ptr(), b, h, w, quality), lambda: (
+        th.empty((b, slot_bytes), dtype=th.uint8, device=dev),
+        th.empty(max(int(lib.maua_jpeg_ws_bytes(b, h, w, restart_mcus)), 16), dtype=th.uint8, device=dev)))
     with th.cuda.device(u8.device):
         _lib.check(lib.maua_jpeg_encode_u8(u8.data_ptr(), b, h, w, quality, restart_mcus, header.data_ptr(), header.numel(), out.data_ptr(),
                                            slot_bytes, ws.data_ptr(), _lib.stream_ptr(u8.device)), "maua_jpeg_encode_u8")
-    return out
-
-
-def _deep_scratch(scratch, key, shape, dev):
-    """The reusable int16 buffer (uint16 bits) of one deep stage, keyed by the stage's input buffer: the protocol of crop_resize_for_delivery."""
-    out = scratch.get(key)
-    if out is None:
-        out = scratch[key] = th.empty(shape, dtype=th.int16, device=dev)
     return out
 
 
@@ -428,61 +442,46 @@ def frames_to_deep(images, out_size, pix_fmt, scratch, resize=None):
                                 maua_rgb48_to_yuv_p10 for a YUV format
       with ``resize``           maua_frames_to_u16 on the whole generated frame, maua_resample_u16 (resize_frames) to the delivery size, then
                                 maua_rgb48_to_yuv_p10 for a YUV format: the resampler works on the 16-bit codes, nothing is re-quantised
-    ``scratch``: dict holding the reusable buffers, keyed by the input buffer (the lanes' batches are in flight concurrently)."""
+    One path: the 16-bit master, the spatial step if there is one, the conversion for a YUV format; the first row is its shortcut.
+    ``scratch``: the render's reusable buffers (_cached)."""
     if pix_fmt not in DEEP_PIX_FMTS:
         raise ValueError(f"{pix_fmt!r} is not a deep pipe format ({' | '.join(DEEP_PIX_FMTS)})")
     if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda:
         raise RuntimeError(f"frames_to_deep takes fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
     b, _, h, w = images.shape
+    box = None  # the spatial step: ``resize``, the built-in box of the wide outputs, or none — the frames leave at ow x oh
     if resize is not None:
         check_deliver_size(resize, pix_fmt)
-        images = images.contiguous()
-        lib, dev, sub, ptr = _lib.load(), images.device, DEEP_SUBSAMPLING.get(pix_fmt), images.data_ptr()
         ow, oh = resize.size
-        if b == 0:
-            return th.empty((0, deep_frame_bytes(pix_fmt, ow, oh)), dtype=th.uint8, device=dev)
-        with th.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            master = _deep_scratch(scratch, ("deep-u16", ptr, b, h, w), (b, h, w, 3), dev)
-            _lib.check(lib.maua_frames_to_u16(ptr, master.data_ptr(), b, h, w, st), "maua_frames_to_u16")
-            master = resize_frames(master, resize, scratch)
-            if sub is None:
-                return master.view(b, oh * ow * 3).view(th.uint8)
-            out = _deep_scratch(scratch, ("deep-yuv", ptr, b, oh, ow, sub), (b, deep_frame_bytes(pix_fmt, ow, oh) // 2), dev)
-            _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, oh, ow, sub, st), "maua_rgb48_to_yuv_p10")
-            return out.view(th.uint8)
-    if h % 2 or w % 2:
-        raise ValueError(f"{pix_fmt} needs even frame dimensions, got {w}x{h}")
+    else:
+        if h % 2 or w % 2:
+            raise ValueError(f"{pix_fmt} needs even frame dimensions, got {w}x{h}")
+        box = _wide_output_box(out_size, h, w)
+        if box is not None and (box[4] < box[2] or box[5] < box[3]):
+            raise ValueError(f"{pix_fmt}: a {w}x{h} frame cannot be delivered at --out_size {out_size}: the device resize only up-scales")
+        ow, oh = box[4:] if box is not None else (w, h)
     images = images.contiguous()
-    lib, dev, sub = _lib.load(), images.device, DEEP_SUBSAMPLING.get(pix_fmt)
-    box = None
-    if out_size == 1920 and w == 2048:
-        box = (112, 0, w - 224, h, 1920, 1080)
-    elif out_size == 1080 and h == 2048:
-        box = (0, 112, w, h - 224, 1080, 1920)
-    if box is not None and (box[4] < box[2] or box[5] < box[3]):
-        raise ValueError(f"{pix_fmt}: a {w}x{h} frame cannot be delivered at --out_size {out_size}: the device resize only up-scales")
-    ptr = images.data_ptr()
+    lib, dev, sub, ptr = _lib.load(), images.device, DEEP_SUBSAMPLING.get(pix_fmt), images.data_ptr()
+    if b == 0:
+        return th.empty((0, deep_frame_bytes(pix_fmt, ow, oh)), dtype=th.uint8, device=dev)
     with th.cuda.device(dev):
         st = _lib.stream_ptr(dev)
-        if b == 0:
-            oh, ow = (box[5], box[4]) if box is not None else (h, w)
-            return th.empty((0, deep_frame_bytes(pix_fmt, ow, oh)), dtype=th.uint8, device=dev)
-        if box is None and sub is not None:
-            out = _deep_scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), dev)
+        if resize is None and box is None and sub is not None:
+            out = _scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), th.int16, dev)
             _lib.check(lib.maua_frames_to_yuv_p10_f32(ptr, out.data_ptr(), b, h, w, sub, st), "maua_frames_to_yuv_p10_f32")
             return out.view(th.uint8)
-        master = _deep_scratch(scratch, ("deep-u16", ptr, b, h, w), (b, h, w, 3), dev)
+        master = _scratch(scratch, ("deep-u16", ptr, b, h, w), (b, h, w, 3), th.int16, dev)  # (uint16 bits in int16 tensors, here and below)
         _lib.check(lib.maua_frames_to_u16(ptr, master.data_ptr(), b, h, w, st), "maua_frames_to_u16")
-        if box is not None:
-            x0, y0, cw, ch, ow, oh = box
-            resized = _deep_scratch(scratch, ("deep-resize", ptr, b, oh, ow), (b, oh, ow, 3), dev)
-            _lib.check(lib.maua_crop_resize_u16(master.data_ptr(), resized.data_ptr(), b, h, w, x0, y0, cw, ch, ow, oh, st), "maua_crop_resize_u16")
-            master, h, w = resized, oh, ow
+        if resize is not None:
+            master = resize_frames(master, resize, scratch)
+        elif box is not None:
+            resized = _scratch(scratch, ("deep-resize", ptr, b, oh, ow), (b, oh, ow, 3), th.int16, dev)
+            _lib.check(lib.maua_crop_resize_u16(master.data_ptr(), resized.data_ptr(), b, h, w, *box, st), "maua_crop_resize_u16")
+            master = resized
         if sub is None:
-            return master.view(b, h * w * 3).view(th.uint8)
-        out = _deep_scratch(scratch, ("deep-yuv", ptr, b, h, w, sub), (b, deep_frame_bytes(pix_fmt, w, h) // 2), dev)
-        _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, h, w, sub, st), "maua_rgb48_to_yuv_p10")
+            return master.view(b, oh * ow * 3).view(th.uint8)
+        out = _scratch(scratch, ("deep-yuv", ptr, b, oh, ow, sub), (b, deep_frame_bytes(pix_fmt, ow, oh) // 2), th.int16, dev)
+        _lib.check(lib.maua_rgb48_to_yuv_p10(master.data_ptr(), out.data_ptr(), b, oh, ow, sub, st), "maua_rgb48_to_yuv_p10")
         return out.view(th.uint8)
 
 
@@ -491,14 +490,13 @@ def grade_frames(images, grade_rows, lut, scratch, out="u8"):
     offset / power, a 3 x 3 matrix with bias and a 3-D LUT (include/maua_hip.h states the arithmetic; audioreactive/grade.py's Grade builds
     the operands).  ``grade_rows``: float32 device rows [b, >= 24], one per frame of the batch (a view into a longer table is fine: the row
     stride is passed on); ``lut``: Grade.lut_table's padded table [N^3, 4] or None.
-      out="u8"   -> uint8 [b, H, W, 3] by maua_grade_to_u8 (= frames_to_uint8 of the graded image), in a reusable buffer of ``scratch`` keyed
-                    by the input buffer (the protocol of crop_resize_for_delivery)
+      out="u8"   -> uint8 [b, H, W, 3] by maua_grade_to_u8 (= frames_to_uint8 of the graded image), in a reusable buffer of ``scratch``
+                    (_cached)
       out="f32"  -> ``images`` itself, graded in place by maua_grade_f32
     Frames whose row is the identity come out as they went in (as frames_to_uint8's for "u8")."""
     if out not in ("u8", "f32"):
         raise ValueError(f"unknown grade output {out!r} (u8 | f32)")
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
-        raise RuntimeError(f"grade_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    _require_fp32_images(images, "grade_frames")
     b, _, h, w = images.shape
     dev = images.device
     if (grade_rows.dim() != 2 or grade_rows.shape[0] != b or grade_rows.shape[1] < 24 or grade_rows.dtype != th.float32 or grade_rows.device != dev
@@ -520,10 +518,7 @@ def grade_frames(images, grade_rows, lut, scratch, out="u8"):
                 _lib.check(lib.maua_grade_f32(images.data_ptr(), images.data_ptr(), b, h, w, grade_rows.data_ptr(), stride, _lib.ptr(lut), lut_n,
                                               _lib.stream_ptr(dev)), "maua_grade_f32")
         return images
-    key = ("grade-u8", images.data_ptr(), b, h, w)
-    u8 = scratch.get(key)
-    if u8 is None:
-        u8 = scratch[key] = th.empty((b, h, w, 3), dtype=th.uint8, device=dev)
+    u8 = _scratch(scratch, ("grade-u8", images.data_ptr(), b, h, w), (b, h, w, 3), th.uint8, dev)
     if b:
         with th.cuda.device(dev):
             _lib.check(lib.maua_grade_to_u8(images.data_ptr(), u8.data_ptr(), b, h, w, grade_rows.data_ptr(), stride, _lib.ptr(lut), lut_n,
@@ -531,10 +526,27 @@ def grade_frames(images, grade_rows, lut, scratch, out="u8"):
     return u8
 
 
+def _per_frame_table(what, n_rows, n_rendered):
+    """The rule of the per-frame tables of a grade, a lens and a feedback: one row for every frame, or one row per rendered frame; anything
+    else is refused.  Returns whether frame f reads row f (a one-row table: every frame reads row 0)."""
+    if n_rows not in (1, n_rendered):
+        raise ValueError(f"the {what}'s table has {n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
+    return n_rows != 1 or n_rendered == 1
+
+
+def _batch_rows(table, per_frame, batch_size):
+    """A [n, k] table (device tensor or numpy array) as the launches index it: a one-row table repeated to a batch, so that every launch
+    finds a row per frame at the table's stride; a per-frame table as it is."""
+    if per_frame:
+        return table
+    if isinstance(table, np.ndarray):
+        return np.ascontiguousarray(np.broadcast_to(table, (max(batch_size, 1), table.shape[1])))
+    return table.expand(max(batch_size, 1), table.shape[1]).contiguous()
+
+
 class LensOperands:
-    """A render's lens on one device (_lens_operands): the Lens, whether its table holds a row per rendered frame, and — per frame
-    size, the plan rule needs the height; _render_shard resolves the generated size before it opens the sink — the device tables, a one-row table repeated to a batch so that every
-    launch finds a row and a half-kernel per frame."""
+    """A render's lens on one device (_lens_operands): the Lens, whether its table holds a row per rendered frame, and — per frame size:
+    the plan rule needs the height — the device tables (_batch_rows)."""
 
     def __init__(self, lens, per_frame, batch_size, dev):
         self.lens, self.per_frame, self.batch_size, self.dev = lens, per_frame, max(batch_size, 1), dev
@@ -544,8 +556,7 @@ class LensOperands:
         """(rows, d, bloom radius, bloom taps, sharpen radius, sharpen taps) for frames of h x w."""
         if (h, w) not in self._sized:
             rows, d, rb, bt, rs, st = self.lens.operands(self.dev, h, w)
-            if not self.per_frame:
-                rows, bt, st = (t.expand(self.batch_size, t.shape[1]).contiguous() for t in (rows, bt, st))
+            rows, bt, st = (_batch_rows(t, self.per_frame, self.batch_size) for t in (rows, bt, st))
             self._sized[(h, w)] = (rows, d, rb, bt, rs, st)
         return self._sized[(h, w)]
 
@@ -557,10 +568,8 @@ def lens_frames(images, lens_ops, first, count, scratch):
     audioreactive/lens.py's Lens builds the operands.  ``lens_ops``: LensOperands; ``first``: the batch's first rendered frame (its rows
     are [first, first + count) of a per-frame table).  The bloom chain (extract, blur) is launched only when some row of the JOB has a
     bloom, the sharpen's blur only when some row has a sharpen, nothing at all for a lens that is the identity throughout; frames whose
-    row is the identity come out as they went in, bit for bit.  The reduced maps and the soft image live in ``scratch``, keyed by the
-    input buffer (the protocol of crop_resize_for_delivery)."""
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
-        raise RuntimeError(f"lens_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    row is the identity come out as they went in, bit for bit.  The reduced maps and the soft image live in ``scratch`` (_cached)."""
+    _require_fp32_images(images, "lens_frames")
     b, _, h, w = images.shape
     if b != count:
         raise RuntimeError(f"lens_frames: {b} images for {count} frames")
@@ -579,20 +588,14 @@ def lens_frames(images, lens_ops, first, count, scratch):
     bh, bw = -(-h // d), -(-w // d)
     with th.cuda.device(dev):
         if lens.has_bloom:
-            key = ("lens-bloom", images.data_ptr(), b, bh, bw)
-            maps = scratch.get(key)
-            if maps is None:
-                maps = scratch[key] = th.empty((2, b, 3, bh, bw), dtype=th.float32, device=dev)
+            maps = _scratch(scratch, ("lens-bloom", images.data_ptr(), b, bh, bw), (2, b, 3, bh, bw), th.float32, dev)
             _lib.check(lib.maua_lens_extract_f32(images.data_ptr(), maps[0].data_ptr(), b, h, w, d, rows.data_ptr(), rows.stride(0), st),
                        "maua_lens_extract_f32")
             _lib.check(lib.maua_lens_blur_f32(maps[0].data_ptr(), maps[1].data_ptr(), b, 3, bh, bw, rb, btaps.data_ptr(), btaps.stride(0), st),
                        "maua_lens_blur_f32")
             bloom = maps[1]
         if lens.has_sharpen:
-            key = ("lens-soft", images.data_ptr(), b, h, w)
-            soft = scratch.get(key)
-            if soft is None:
-                soft = scratch[key] = th.empty((b, 3, h, w), dtype=th.float32, device=dev)
+            soft = _scratch(scratch, ("lens-soft", images.data_ptr(), b, h, w), (b, 3, h, w), th.float32, dev)
             _lib.check(lib.maua_lens_blur_f32(images.data_ptr(), soft.data_ptr(), b, 3, h, w, rs, staps.data_ptr(), staps.stride(0), st),
                        "maua_lens_blur_f32")
         _lib.check(lib.maua_lens_apply_f32(images.data_ptr(), images.data_ptr(), b, h, w, rows.data_ptr(), rows.stride(0), _lib.ptr(bloom), bh, bw, d,
@@ -617,9 +620,7 @@ class FeedbackOperands:
         """(rows — float32 [n, 16] on the host, a one-row table repeated to a batch —, mode, border) for frames of h x w."""
         if (h, w) not in self._sized:
             rows, mode, border = self.feedback.operands(self.dev, h, w)
-            if not self.per_frame:
-                rows = np.ascontiguousarray(np.broadcast_to(rows, (self.batch_size, rows.shape[1])))
-            self._sized[(h, w)] = (np.ascontiguousarray(rows, np.float32), mode, border)
+            self._sized[(h, w)] = (np.ascontiguousarray(_batch_rows(rows, self.per_frame, self.batch_size), np.float32), mode, border)
         return self._sized[(h, w)]
 
     def allocate(self, h, w):
@@ -646,8 +647,7 @@ def feedback_frames(images, ops, first, count, scratch):
     stream order; so the only launch that reads the old state after the previous batch wrote it is this batch's first, which precedes
     this batch's last on the same stream, and the next reader waits for the event recorded after the write.  Nothing else reads it: the
     lens, the grade and the quantisers work on the lane's image."""
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != th.float32 or not images.is_cuda or not images.is_contiguous():
-        raise RuntimeError(f"feedback_frames takes contiguous fp32 [b, 3, H, W] device images, got {images.dtype} {tuple(images.shape)} on {images.device}")
+    _require_fp32_images(images, "feedback_frames")
     del scratch
     b, _, h, w = images.shape
     if b != count:
@@ -718,7 +718,7 @@ class TemporalFold:
 
 
 def _fold_from_env():
-    """The fold of a render whose parameter list is pinned (render, render_shard): $MAUA_SUBFRAMES, $MAUA_SHUTTER (box),
+    """The fold of the entries that have no parameter for it (render, render_shard): $MAUA_SUBFRAMES, $MAUA_SHUTTER (box),
     $MAUA_SHUTTER_LIGHT (encoded).  $MAUA_SUBFRAMES unset, empty or 1: no fold."""
     text = os.environ.get("MAUA_SUBFRAMES")
     if not text:
@@ -775,8 +775,8 @@ def _device_fold_tables(dev):
 
 def fold_frames(u8, fold, scratch):
     """uint8 [b, ...] device frames -> [b // N, ...] on the current (= producing) stream: frame g of the result is the weighted average of
-    the frames g N .. g N + N - 1 (TemporalFold; maua_temporal_fold_u8 states the arithmetic).  ``scratch``: dict holding the reusable
-    output buffers, keyed by the input buffer (the protocol of crop_resize_for_delivery: the lanes' batches are in flight concurrently)."""
+    the frames g N .. g N + N - 1 (TemporalFold; maua_temporal_fold_u8 states the arithmetic).  ``scratch``: the render's reusable buffers
+    (_cached)."""
     if u8.dim() < 2 or u8.dtype != th.uint8 or not u8.is_cuda:
         raise RuntimeError(f"fold_frames takes uint8 [b, ...] device frames, got {u8.dtype} {tuple(u8.shape)} on {u8.device}")
     n = fold.subframes
@@ -785,10 +785,7 @@ def fold_frames(u8, fold, scratch):
         raise ValueError(f"a batch of {b} frames does not hold whole groups of {n} sub-frames")
     u8 = u8.contiguous()
     frame_bytes = int(np.prod(u8.shape[1:]))
-    key = ("fold", u8.data_ptr(), b, n, tuple(u8.shape[1:]))
-    out = scratch.get(key)
-    if out is None:
-        out = scratch[key] = th.empty((b // n,) + tuple(u8.shape[1:]), dtype=th.uint8, device=u8.device)
+    out = _scratch(scratch, ("fold", u8.data_ptr(), b, n, tuple(u8.shape[1:])), (b // n,) + tuple(u8.shape[1:]), th.uint8, u8.device)
     decode, threshold = _device_fold_tables(u8.device) if fold.light == "linear" else (None, None)
     weights = (ctypes.c_uint8 * n)(*fold.weights)
     with th.cuda.device(u8.device):
@@ -877,7 +874,7 @@ def check_deliver_size(resize, pix_fmt):
 
 
 def _resize_from_env():
-    """The resize of a render whose parameter list is pinned (render, render_shard, render_folded): $MAUA_DELIVER_SIZE (WxH),
+    """The resize of the entries that have no parameter for it (render, render_shard, render_folded): $MAUA_DELIVER_SIZE (WxH),
     $MAUA_DELIVER_FILTER (lanczos), $MAUA_DELIVER_FIT (crop).  $MAUA_DELIVER_SIZE unset or empty: none, and the other two are not read."""
     text = os.environ.get("MAUA_DELIVER_SIZE")
     if not text:
@@ -913,8 +910,8 @@ def _resize_tables(dev, W, H, resize):
 def resize_frames(frames, resize, scratch):
     """uint8 — or int16-viewed uint16 — [b, H, W, 3] device frames -> [b, h, w, 3] of the same type at ``resize.size`` on the current
     (= producing) stream, by maua_resample_u8 / maua_resample_u16 with ``resize``'s filter and fit.  The device tables are cached per
-    (device, source size, setting).  ``scratch``: dict holding the reusable output buffers and workspaces, keyed by the input buffer (the
-    protocol of crop_resize_for_delivery); a padded frame's border is zeroed when the buffer is allocated and never written again."""
+    (device, source size, setting).  ``scratch``: the render's reusable buffers (_cached), here the output and the workspace; a padded
+    frame's border is zeroed when the buffer is allocated and never written again."""
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype not in (th.uint8, th.int16) or not frames.is_cuda:
         raise RuntimeError(f"resize_frames takes uint8 or int16 [b, H, W, 3] device frames, got {frames.dtype} {tuple(frames.shape)} on "
                            f"{frames.device}")
@@ -924,14 +921,13 @@ def resize_frames(frames, resize, scratch):
     sz = 1 if frames.dtype == th.uint8 else 2
     box, (x, y, w, h), (kx, bx, ksx), (ky, by, ksy) = _resize_tables(dev, W, H, resize)
     ow, oh = resize.size
-    key = ("resize", frames.data_ptr(), b, H, W, sz) + resize.key()
-    buffers = scratch.get(key)
     lib = _lib.load()
-    if buffers is None:
-        out = th.zeros((b, oh, ow, 3), dtype=frames.dtype, device=dev)
+
+    def buffers():
         n_ws = int(lib.maua_resample_ws_bytes(sz, b, H, W, w, h, ksx, ksy))
-        buffers = scratch[key] = (out, th.empty(n_ws, dtype=th.uint8, device=dev) if n_ws else None)
-    out, ws = buffers
+        return th.zeros((b, oh, ow, 3), dtype=frames.dtype, device=dev), th.empty(n_ws, dtype=th.uint8, device=dev) if n_ws else None
+
+    out, ws = _cached(scratch, ("resize", frames.data_ptr(), b, H, W, sz) + resize.key(), buffers)
     if b == 0:
         return out
     fn = lib.maua_resample_u8 if sz == 1 else lib.maua_resample_u16
@@ -1055,7 +1051,7 @@ def graph_lanes(generator, batch_size, n_lanes, bends=(), random=None, synth=Non
     for k in range(n_lanes):
         stream = _lane_stream(dev, k)
         cache_key = (batch_size, k, tap) + ((slots,) if slots else ()) + ((("synth",) + synth_slots,) if synth_slots else ())
-        if frames != "u8":  # (the uint8 lanes keep the key they always had)
+        if frames != "u8":  # (the uint8 lanes' key carries no frame kind)
             cache_key += (("frames", frames),)
         lane = None if bends else cache.get(cache_key)
         if lane is None or _lane_is_stale(lane, key, slots, seed, offset, synth_slots, synth_offset):
@@ -1233,8 +1229,7 @@ def synthesize(generator, latents, noise, batch_size, truncation=1.0, bends=(), 
     caller_stream = th.cuda.current_stream(plan.dev)
     full_batches = (plan.hi - plan.lo) // batch_size
     if plan.capturable and full_batches >= 1:
-        lane_state = graph_lanes(generator, batch_size, min(max(1, int(lanes)), full_batches), plan.seq_bends, plan.random, plan.synth,
-                                 **({} if frames == "u8" else {"frames": frames}))
+        lane_state = graph_lanes(generator, batch_size, min(max(1, int(lanes)), full_batches), plan.seq_bends, plan.random, plan.synth, frames)
         for stream, lane in lane_state:
             lane.bind(plan.latents, plan.noise, plan.trunc_t)  # once per render: the pointers of the HBM-resident sequences
             stream.wait_stream(caller_stream)
@@ -1270,9 +1265,11 @@ def render(generator, latents, noise, offset, duration, batch_size, out_size, ou
            truncation=1.0, bends=[], rewrites={}, randomize_noise=False, ffmpeg_preset="slow"):
     """Drop-in for reference render.render (render.py:14-29).  With torch.distributed initialised (one process per
     GPU) every rank renders a contiguous shard of the frames and streams them, batch by batch, to rank 0's ordered sink
-    (sharding.FrameStream)."""
-    return render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file,
-                        truncation, bends, rewrites, randomize_noise, ffmpeg_preset, None)
+    (sharding.FrameStream).  The reference's parameter list has no room for the options of the tail: the pipe format, a temporal fold
+    and a delivery size come from the environment (render_shard)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, None, None, None, fold=_fold_from_env(), resize=_resize_from_env(),
+                         grade=None, lens=None, feedback=None)
 
 
 def _drain_quietly(worker):
@@ -1410,136 +1407,31 @@ class _GatherStream:
         self.stream = None
 
 
-def render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                 bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
-    """``render`` with an optional ``_shard = (lo, hi, n_frames)``: set by generate() after sharding.scatter_frames, it says
-    that ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this rank's block of the frames.
-    ``pipe_pix_fmt``: "rgb24", "yuv420p", "mjpeg" or "mjpeg:<quality>" (PIPE_PIX_FMTS) or a deep format (DEEP_PIX_FMTS: 16-bit RGB / 10-bit
-    YUV made from the fp32 image; refused together with a temporal fold, which is 8-bit only); default $MAUA_PIPE_PIX_FMT, else rgb24 — what
-    crosses to the host, to rank 0 and into the sink.  ``render`` keeps the reference's parameter list, so it takes the format from the
-    environment variable.  This parameter list is pinned as well: a temporal fold comes from $MAUA_SUBFRAMES, $MAUA_SHUTTER and
-    $MAUA_SHUTTER_LIGHT (_fold_from_env; unset: none) — ``render_folded`` takes it as an argument —, a delivery size from
-    $MAUA_DELIVER_SIZE, $MAUA_DELIVER_FILTER and $MAUA_DELIVER_FIT (_resize_from_env; unset: none) — ``render_delivered`` takes both."""
-    resize = _resize_from_env()
-    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, _fold_from_env(),
-                         *(() if resize is None else (resize,)))
-
-
-def render_folded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None):
-    """``render_shard`` with an explicit ``fold`` (TemporalFold or None; the environment is not read): ``latents`` and every per-frame input
-    hold ``fold.subframes`` rows per delivered frame, each batch is folded N:1 on the device before anything else happens to it, the sink
-    runs at delivered frames / duration and the return value counts delivered frames.  ``batch_size`` and the frame count (of the job and
-    of every rank's block: ``_shard`` stays in rendered frames) must be multiples of N.  (A delivery size: $MAUA_DELIVER_SIZE, as
-    render_shard.)"""
-    resize = _resize_from_env()
-    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *(() if resize is None else (resize,)))
-
-
-def render_delivered(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                     bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None):
-    """``render_folded`` with an explicit ``resize`` (FrameResize or None; the environment is not read for either): every delivered frame
-    is resampled on the device to ``resize.size`` on the rank that rendered it — after the fold, before the colour conversion / the JPEG
-    encoder; at 16 bits on the deep formats —, and the sink, the stream's frame shape and both multi-rank transports see that size.  The
-    built-in 112-px crop of the 1920 / 1080 outputs is skipped: the source is the whole generated frame (2048 x 1024 for out_size 1920)."""
-    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *(() if resize is None else (resize,)))
-
-
-def render_graded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None):
-    """``render_delivered`` with a colour ``grade`` (audioreactive/grade.py's Grade, or None: render_delivered, call for call): the lanes keep
-    the fp32 image, every rendered frame is graded on the device by its row of the grade's table (grade_frames) — per sub-frame and before
-    the fold with a temporal fold, before the resampler with a delivery size —, then the 8-bit formats go on as maua_grade_to_u8's frames
-    through crop / fold / resize / yuv420p / mjpeg and the deep formats as the image graded in place through frames_to_deep.  The table
-    holds one row, or one row per entry of ``latents`` (with ``_shard``: this rank's block, Grade.slice); anything else is refused before
-    the first batch."""
-    extra = () if resize is None and grade is None else (resize,) if grade is None else (resize, grade)
-    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, *extra)
+FEEDBACK_ONE_RANK = ("a frame feedback is a recurrence over the frames: a shard's first frame needs the state its predecessor leaves behind, "
+                     "which only a render that starts at frame 0 on its own has ({where}).  Render a feedback on one rank (one process, one GPU)")
 
 
 def _grade_operands(grade, n_rendered, batch_size, dev):
-    """(rows, lut, per_frame) of a render's grade on ``dev``: the device row table — a one-row table repeated to a batch, so that every
-    launch finds a row per frame — and the padded LUT.  Refuses a table that has neither one row nor ``n_rendered``."""
+    """(rows, lut, per_frame) of a render's grade on ``dev``: the device row table (_batch_rows) and the padded LUT.  Refuses a table that
+    has neither one row nor ``n_rendered``."""
     if not (hasattr(grade, "rows") and hasattr(grade, "lut_table") and hasattr(grade, "n_rows")):
         raise TypeError(f"grade must be an audioreactive Grade, got {type(grade).__name__}")
-    if grade.n_rows not in (1, n_rendered):
-        raise ValueError(f"the grade's table has {grade.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
-    rows = grade.rows(dev)
-    per_frame = grade.n_rows != 1 or n_rendered == 1
-    if not per_frame:
-        rows = rows.expand(max(batch_size, 1), rows.shape[1]).contiguous()
-    return rows, grade.lut_table(dev), per_frame
-
-
-def render_lensed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
-                  lens=None):
-    """``render_graded`` with a ``lens`` (audioreactive/lens.py's Lens, or None: render_graded, call for call): the lanes keep the fp32
-    image and every rendered frame passes through lens_frames (bloom, sharpen, vignette; in place) — the whole generated frame (2048 x 1024
-    for out_size 1920), per sub-frame and before the fold, before the resampler —, then through the grade if there is one, then down the
-    existing chain: without a grade the 8-bit formats continue with frames_to_uint8 of the lensed image, the deep formats with the image
-    itself.  The table holds one row, or one row per entry of ``latents`` (with ``_shard``: this rank's block, Lens.slice); anything else
-    is refused before the first batch."""
-    if lens is None:
-        return render_graded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                             rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade)
-    return _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
+    per_frame = _per_frame_table("grade", grade.n_rows, n_rendered)
+    return _batch_rows(grade.rows(dev), per_frame, batch_size), grade.lut_table(dev), per_frame
 
 
 def _lens_operands(lens, n_rendered, batch_size, dev):
     """The LensOperands of a render's lens on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
     if not (hasattr(lens, "operands") and hasattr(lens, "n_rows") and hasattr(lens, "has_bloom")):
         raise TypeError(f"lens must be an audioreactive Lens, got {type(lens).__name__}")
-    if lens.n_rows not in (1, n_rendered):
-        raise ValueError(f"the lens's table has {lens.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
-    return LensOperands(lens, lens.n_rows != 1 or n_rendered == 1, batch_size, dev)
-
-
-def render_fed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-               bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
-               lens=None, feedback=None):
-    """``render_lensed`` with a ``feedback`` (audioreactive/feedback.py's Feedback, or None: render_lensed, call for call): the lanes keep
-    the fp32 image and every rendered frame passes through feedback_frames (the previous output fed back under it; in place) — per
-    sub-frame and before the fold —, then through the lens and the grade if there are any (the trail is glowed and graded with the picture
-    it belongs to; the state is the un-lensed image, so a bloom is not fed back into itself), then down the existing chain: without lens
-    and grade the 8-bit formats continue with frames_to_uint8 of the image, the deep formats with the image itself.  The table holds one
-    row, or one row per entry of ``latents``; anything else is refused before the first batch.
-
-    One rank only: a shard's first frame needs the state its predecessor leaves behind, so a job of more than one rank, or a ``_shard``
-    that does not start at frame 0, is refused with a ValueError before the sink is opened."""
-    if feedback is None:
-        return render_lensed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                             rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
-    return _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                          rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens, feedback=feedback)
-
-
-FEEDBACK_ONE_RANK = ("a frame feedback is a recurrence over the frames: a shard's first frame needs the state its predecessor leaves behind, "
-                     "which only a render that starts at frame 0 on its own has ({where}).  Render a feedback on one rank (one process, one GPU)")
+    return LensOperands(lens, _per_frame_table("lens", lens.n_rows, n_rendered), batch_size, dev)
 
 
 def _feedback_operands(feedback, n_rendered, batch_size, dev):
     """The FeedbackOperands of a render's feedback on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
     if not (hasattr(feedback, "operands") and hasattr(feedback, "n_rows") and hasattr(feedback, "border")):
         raise TypeError(f"feedback must be an audioreactive Feedback, got {type(feedback).__name__}")
-    if feedback.n_rows not in (1, n_rendered):
-        raise ValueError(f"the feedback's table has {feedback.n_rows} rows: it needs one row, or one per rendered frame ({n_rendered})")
-    return FeedbackOperands(feedback, feedback.n_rows != 1 or n_rendered == 1, batch_size, dev)
-
-
-def _lensed_u8(images, scratch):
-    """frames_to_uint8 of a lensed batch into a reusable buffer of ``scratch`` keyed by the input buffer."""
-    b, _, h, w = images.shape
-    key = ("lens-u8", images.data_ptr(), b, h, w)
-    u8 = scratch.get(key)
-    if u8 is None:
-        u8 = scratch[key] = th.empty((b, h, w, 3), dtype=th.uint8, device=images.device)
-    return frames_to_uint8(images, out=u8)
+    return FeedbackOperands(feedback, _per_frame_table("feedback", feedback.n_rows, n_rendered), batch_size, dev)
 
 
 def fold_shard_bounds(n_frames, subframes, rank, world):
@@ -1549,35 +1441,135 @@ def fold_shard_bounds(n_frames, subframes, rank, world):
     return subframes * lo, subframes * hi
 
 
-def _render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None, lens=None):
-    """What render_shard / render_folded / render_delivered / render_graded / render_lensed call: _render_frames without a feedback (this
-    parameter list is pinned; the feedback is _render_frames' last keyword)."""
-    return _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
-                          rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize, grade, lens)
+def _generated_hw(generator, out_size):
+    """(H, W) of the frames the generator produces for ``out_size``: 1920 / 1080 render 2048-px-wide / -high frames."""
+    side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
+    return (side, 2 * side) if out_size == 1920 else (2 * side, side) if out_size == 1080 else (side, side)
 
 
-def _render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
-                   bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold, resize=None, grade=None, lens=None,
-                   feedback=None):
-    """The body of render_shard / render_folded / render_delivered / render_graded / render_lensed / render_fed.  ``fold`` None or of one
-    sub-frame, ``resize`` None, ``grade`` None, ``lens`` None and ``feedback`` None: the plain render, call for call."""
-    width, height = _output_dims(out_size)
+def _stream_frame_shape(generator, out_size, pix_fmt="rgb24", resize=None):
+    """The shape of one frame as it travels from the device to the sink: [H, W, 3] of the generated frame (_generated_hw; 2048-px frames
+    are cropped and resized to 1920x1080 / 1080x1920 on the device first, crop_resize_for_delivery) or, with ``resize`` (FrameResize), of
+    its size whatever the generator's; [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p", [mjpeg_slot_bytes] for "mjpeg",
+    [deep_frame_bytes] for the deep formats."""
     if resize is not None:
-        check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
-        width, height = resize.size  # what the sink, the stream's frame shape and the transports see
-    subframes = _subframes(fold)
-    if batch_size % subframes:
-        raise ValueError(f"--batch {batch_size} is not a multiple of --subframes {subframes}: a batch must hold whole groups of sub-frames "
-                         f"(e.g. --batch {subframes * max(1, round(batch_size / subframes))})")
-    quality = _mjpeg_quality(pipe_pix_fmt) if _pipe_pix_fmt(pipe_pix_fmt) == "mjpeg" else None
-    pipe_pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
-    deep = pipe_pix_fmt in DEEP_PIX_FMTS
-    if deep and subframes > 1:
-        raise ValueError(f"--pipe_pix_fmt {pipe_pix_fmt} cannot be combined with --subframes {subframes}: the temporal fold is 8-bit only "
-                         f"(it averages the uint8 frames); render at --subframes 1 or with an 8-bit pipe format")
-    if deep and (width % 2 or height % 2):
-        raise ValueError(f"{pipe_pix_fmt} needs even dimensions, got {width}x{height}")
+        w, h = resize.size
+    else:
+        h, w = _generated_hw(generator, out_size)
+        box = _wide_output_box(out_size, h, w)
+        if box is not None:
+            w, h = box[4:]
+    if pix_fmt == "mjpeg":
+        return (mjpeg_slot_bytes(w, h),)
+    if pix_fmt in DEEP_PIX_FMTS:
+        return (deep_frame_bytes(pix_fmt, w, h),)
+    return (h * w * 3 // 2,) if pix_fmt == "yuv420p" else (h, w, 3)
+
+
+class _FrameTail:
+    """What happens to a batch between the generator and the delivery, decided once per render.  Constructed from the options alone —
+    every refusal that needs no device, the sink's size, the frame kind the lanes are asked for —, then ``load``-ed with the render's frame
+    count and position — the refusals and the operands of grade, lens and feedback on the device —, both before the sink is opened.
+    ``tail(first, batch)`` then runs the stages on the current (= producing) stream and returns the batch as it leaves the device:
+
+        feedback_frames -> lens_frames -> grade_frames, or the plain quantiser behind a feedback or lens without a grade
+        8-bit formats: _deliverable (fold_frames -> crop or resize_frames -> frames_to_yuv420p / frames_to_mjpeg)
+        deep formats:  frames_to_deep (the grade has worked in place on the fp32 image)
+
+    A stage is launched only for an option that is set (and, inside the stage, only for a lens or feedback that is not the identity).
+    ``scratch`` holds the stages' reusable buffers (_cached)."""
+
+    def __init__(self, generator, out_size, pipe_pix_fmt, batch_size, fold, resize, grade, lens, feedback):
+        self.width, self.height = _output_dims(out_size)
+        if resize is not None:
+            check_deliver_size(resize, _pipe_pix_fmt(pipe_pix_fmt))
+            self.width, self.height = resize.size  # what the sink, the stream's frame shape and the transports see
+        self.subframes = subframes = _subframes(fold)
+        if batch_size % subframes:
+            raise ValueError(f"--batch {batch_size} is not a multiple of --subframes {subframes}: a batch must hold whole groups of sub-frames "
+                             f"(e.g. --batch {subframes * max(1, round(batch_size / subframes))})")
+        self.pix_fmt = _pipe_pix_fmt(pipe_pix_fmt)
+        self.quality = _mjpeg_quality(pipe_pix_fmt) if self.pix_fmt == "mjpeg" else None
+        self.deep = self.pix_fmt in DEEP_PIX_FMTS
+        if self.deep and subframes > 1:
+            raise ValueError(f"--pipe_pix_fmt {self.pix_fmt} cannot be combined with --subframes {subframes}: the temporal fold is 8-bit only "
+                             f"(it averages the uint8 frames); render at --subframes 1 or with an 8-bit pipe format")
+        if self.deep and (self.width % 2 or self.height % 2):
+            raise ValueError(f"{self.pix_fmt} needs even dimensions, got {self.width}x{self.height}")
+        self.generator, self.out_size, self.batch_size = generator, out_size, batch_size
+        self.fold, self.resize, self.grade, self.lens, self.feedback = fold, resize, grade, lens, feedback
+        # the deep formats, the grade, the lens and the feedback work on the fp32 image: the lanes then run without their quantiser
+        self.frames = "f32" if self.deep or grade is not None or lens is not None or feedback is not None else "u8"
+        self.grade_rows = self.lens_ops = self.feedback_ops = None
+        self.scratch = {}
+
+    def load(self, n_rendered, first_frame, world):
+        """The per-frame tables of ``n_rendered`` frames on the generator's device (``dev``), for a render that starts at ``first_frame``
+        of a ``world``-rank job."""
+        if self.feedback is not None and (world > 1 or first_frame > 0):
+            raise ValueError(FEEDBACK_ONE_RANK.format(where=f"this shard starts at frame {first_frame} of a {world}-rank job"))
+        self.dev = dev = device_of(self.generator)
+        if self.grade is not None:
+            self.grade_rows, self.grade_lut, self.grade_per_frame = _grade_operands(self.grade, n_rendered, self.batch_size, dev)
+        if self.lens is not None:
+            self.lens_ops = _lens_operands(self.lens, n_rendered, self.batch_size, dev)
+            self.lens_ops.sized(*_generated_hw(self.generator, self.out_size))  # (a bloom too wide for this frame height is refused here)
+        if self.feedback is not None:
+            self.feedback_ops = _feedback_operands(self.feedback, n_rendered, self.batch_size, dev)
+            if not self.feedback.is_identity:
+                self.feedback_ops.sized(*_generated_hw(self.generator, self.out_size))
+                self.feedback_ops.allocate(*_generated_hw(self.generator, self.out_size))  # (on this stream, before the lanes start)
+
+    @property
+    def frame_shape(self):
+        return _stream_frame_shape(self.generator, self.out_size, self.pix_fmt, self.resize)
+
+    def __call__(self, first, images):
+        count, scratch = images.shape[0], self.scratch
+        if self.feedback_ops is not None:  # (first of all: the state is the un-lensed image, the trail is glowed and graded with its picture)
+            images = feedback_frames(images.contiguous(), self.feedback_ops, first, count, scratch)
+        if self.lens_ops is not None:  # (in front of the grade: the glow is graded with the picture it belongs to)
+            images = lens_frames(images.contiguous(), self.lens_ops, first, count, scratch)
+        if self.grade_rows is not None:
+            rows = self.grade_rows[first: first + count] if self.grade_per_frame else self.grade_rows[:count]
+            images = grade_frames(images.contiguous(), rows, self.grade_lut, scratch, out="f32" if self.deep else "u8")
+        elif self.frames == "f32" and not self.deep:  # (the quantiser every 8-bit render ends its forward with)
+            _, _, h, w = images.shape
+            images = frames_to_uint8(images, out=_scratch(scratch, ("lens-u8", images.data_ptr(), count, h, w), (count, h, w, 3), th.uint8, images.device))
+        if self.deep:
+            return frames_to_deep(images, self.out_size, self.pix_fmt, scratch, resize=self.resize)
+        # (2048-px frames leave the device as 1920x1080 already)
+        return _deliverable(images, self.out_size, self.pix_fmt, scratch, self.quality, self.fold, resize=self.resize)
+
+
+def render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, *, fold=None, resize=None,
+                  grade=None, lens=None, feedback=None):
+    """The body of every entry point below, and what generate() calls.  The reference's parameters, then ``_shard = (lo, hi, n_frames)``
+    — set by generate() after sharding.scatter_frames: ``latents`` / ``noise`` / ``truncation`` / bend modulations already hold only this
+    rank's block of the frames —, ``transport`` ("gather" | "host"; default $MAUA_FRAME_TRANSPORT, else gather) and ``pipe_pix_fmt``
+    (PIPE_PIX_FMTS, "mjpeg:<quality>" or DEEP_PIX_FMTS; default $MAUA_PIPE_PIX_FMT, else rgb24 — what crosses to the host, to rank 0 and
+    into the sink), then the options of the tail (_FrameTail; the environment is read for none of them):
+
+      fold      TemporalFold: ``latents`` and every per-frame input hold ``fold.subframes`` rows per delivered frame, each batch is folded
+                N:1 on the device, the sink runs at delivered frames / duration and the return value counts delivered frames.
+                ``batch_size`` and the frame count (of the job and of every rank's block: ``_shard`` stays in rendered frames) must be
+                multiples of N.  8-bit formats only
+      resize    FrameResize: every delivered frame is resampled on the rank that rendered it — after the fold, before the colour
+                conversion / the JPEG encoder; at 16 bits on the deep formats —, and the sink, the stream's frame shape and both
+                multi-rank transports see that size.  The built-in 112-px crop of the 1920 / 1080 outputs is skipped: the source is the
+                whole generated frame (2048 x 1024 for out_size 1920)
+      grade     ar.Grade: every rendered frame is graded by its row of the grade's table — per sub-frame and before the fold —, then the
+                8-bit formats go on as maua_grade_to_u8's frames, the deep formats as the image graded in place
+      lens      ar.Lens: every rendered frame — the whole generated frame — passes through lens_frames in front of the grade
+      feedback  ar.Feedback: every rendered frame passes through feedback_frames in front of the lens (the state is the un-lensed image,
+                so a bloom is not fed back into itself).  One rank only: a job of more than one rank, or a ``_shard`` that does not start
+                at frame 0, is refused before the sink is opened
+
+    The tables of grade, lens and feedback hold one row, or one row per entry of ``latents`` (with ``_shard``: this rank's block);
+    anything else is refused before the first batch."""
+    tail = _FrameTail(generator, out_size, pipe_pix_fmt, batch_size, fold, resize, grade, lens, feedback)
+    subframes = tail.subframes
     rank, world = sharding.rank_world()
     # multi-GPU frame transport: "gather" (default: RCCL gather of every round into rank 0's HBM) or "host" (per-rank D2H into shared memory)
     transport = transport or os.environ.get("MAUA_FRAME_TRANSPORT", "gather")
@@ -1594,24 +1586,12 @@ def _render_frames(generator, latents, noise, offset, duration, batch_size, out_
         raise ValueError(f"{n_frames} rendered frames (this rank's: {lo} .. {hi}) are not whole groups of {subframes} sub-frames")
     # what the sink and the transports count: delivered frames — n_frames and batch_size themselves without a fold
     n_out, batch_out = n_frames // subframes, batch_size // subframes
-    if feedback is not None and (world > 1 or lo > 0):  # (before the sink is opened: no file is created)
-        raise ValueError(FEEDBACK_ONE_RANK.format(where=f"this shard starts at frame {lo} of a {world}-rank job"))
-    dev = device_of(generator)
-    if grade is not None:  # (refused here, before the sink is opened and the first batch is rendered)
-        grade_rows, grade_lut, grade_per_frame = _grade_operands(grade, len(latents), batch_size, dev)
-    if lens is not None:  # (likewise)
-        lens_ops = _lens_operands(lens, len(latents), batch_size, dev)
-        lens_ops.sized(*_generated_hw(generator, out_size))  # (a bloom too wide for this frame height is refused here, not inside the first batch)
-    if feedback is not None:
-        feedback_ops = _feedback_operands(feedback, len(latents), batch_size, dev)
-        if not feedback.is_identity:
-            feedback_ops.sized(*_generated_hw(generator, out_size))
-            feedback_ops.allocate(*_generated_hw(generator, out_size))  # (on this stream, before the lanes start)
+    tail.load(len(latents), lo, world)  # (refusals included: before the sink is opened, no file is created)
     sink = worker = None
     with contextlib.ExitStack() as unwind:  # (callbacks run last in, first out)
         if rank == 0:
-            sink = FrameSink(output_file, width, height, n_out / duration, audio_file, offset, duration, ffmpeg_preset, pix_fmt=pipe_pix_fmt,
-                             quality=quality)
+            sink = FrameSink(output_file, tail.width, tail.height, n_out / duration, audio_file, offset, duration, ffmpeg_preset,
+                             pix_fmt=tail.pix_fmt, quality=tail.quality)
             unwind.callback(sink.close)  # the encoder process / output file must not outlive a failed render: closed last, and always
             worker = SinkWorker(sink)
             unwind.callback(_drain_quietly, worker)
@@ -1626,62 +1606,72 @@ def _render_frames(generator, latents, noise, offset, duration, batch_size, out_
         # 45-90 ms up front, as much as it saves on a 900-frame job; generate() has just run one, as the reference does.)
         with parked_heap():
             if not sharding.grouped():
-                delivery = _LocalRing(dev, batch_out, worker)
+                delivery = _LocalRing(tail.dev, batch_out, worker)
             else:
-                delivery = (_HostStore if transport == "host" else _GatherStream)(n_out, batch_out, dev, rank, worker)
+                delivery = (_HostStore if transport == "host" else _GatherStream)(n_out, batch_out, tail.dev, rank, worker)
             with contextlib.closing(delivery):
-                scratch = {}  # the reusable output buffers of the device-side crop / resize / conversion
-                # (lanes: synthesize's default, 3, on every path)
-                # (a deep format asks for the fp32 image; the keyword is passed on that path only)
-                # (a grade asks for it as well: it works on the fp32 image, and hands the 8-bit chain the frames the quantiser would have)
-                for first, u8 in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
-                                            frame_range=frame_range,
-                                            **({"frames": "f32"} if deep or grade is not None or lens is not None or feedback is not None
-                                               else {})):
-                    if feedback is not None:  # (first of all: the state is the un-lensed image, the trail is glowed and graded with its picture)
-                        u8 = feedback_frames(u8.contiguous(), feedback_ops, first, u8.shape[0], scratch)
-                    if lens is not None:  # (first the lens, then the grade: the glow is graded with the picture it belongs to)
-                        u8 = lens_frames(u8.contiguous(), lens_ops, first, u8.shape[0], scratch)
-                    if (lens is not None or feedback is not None) and grade is None and not deep:
-                        u8 = _lensed_u8(u8, scratch)  # (the quantiser every 8-bit render ends its forward with)
-                    if grade is not None:
-                        count = u8.shape[0]
-                        rows = grade_rows[first: first + count] if grade_per_frame else grade_rows[:count]
-                        u8 = grade_frames(u8.contiguous(), rows, grade_lut, scratch, out="f32" if deep else "u8")
-                    if resize is not None:  # (the keyword is passed on this path only: the plain render makes the calls it always made)
-                        delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch, resize=resize) if deep else
-                                      _deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold, resize=resize))
-                    elif deep:
-                        delivery.push(frames_to_deep(u8, out_size, pipe_pix_fmt, scratch))
-                    else:
-                        delivery.push(_deliverable(u8, out_size, pipe_pix_fmt, scratch, quality, fold))  # 2048-px frames leave the device as 1920x1080 already
-                delivery.finish(_stream_frame_shape(generator, out_size, pipe_pix_fmt, *(() if resize is None else (resize,))))
+                # (lanes: synthesize's default, 3, on every path.  The frame kind is named only where it is not the default: the rank
+                # tests stand in for synthesize with CPU functions of its original parameter list)
+                kind = {} if tail.frames == "u8" else {"frames": tail.frames}
+                for first, batch in synthesize(generator, latents, noise, batch_size, truncation, bends, rewrites, randomize_noise,
+                                               frame_range=frame_range, **kind):
+                    delivery.push(tail(first, batch))
+                delivery.finish(tail.frame_shape)
                 if worker is not None:
                     worker.close()  # every frame is written; re-raises a sink error on the launch thread
     return sink.count if sink is not None else 0
 
 
-def _generated_hw(generator, out_size):
-    """(H, W) of the frames the generator produces for ``out_size``: 1920 / 1080 render 2048-px-wide / -high frames."""
-    side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
-    return (side, 2 * side) if out_size == 1920 else (2 * side, side) if out_size == 1080 else (side, side)
+def render_shard(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                 bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None):
+    """``render`` with ``_shard``, ``transport`` and ``pipe_pix_fmt`` (render_frames).  Like ``render`` it has no parameter for a temporal
+    fold or a delivery size and takes them from the environment: $MAUA_SUBFRAMES, $MAUA_SHUTTER and $MAUA_SHUTTER_LIGHT (_fold_from_env;
+    unset: none), $MAUA_DELIVER_SIZE, $MAUA_DELIVER_FILTER and $MAUA_DELIVER_FIT (_resize_from_env; unset: none)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=_fold_from_env(),
+                         resize=_resize_from_env(), grade=None, lens=None, feedback=None)
 
 
-def _stream_frame_shape(generator, out_size, pix_fmt="rgb24", resize=None):
-    """[H, W, 3] of the frames the generator produces for ``out_size`` (1920 / 1080 render 2048-px-wide / -high frames
-    that the sink crops and resizes, render.py:98-105); [H * W * 3 // 2] for the planar ``pix_fmt`` "yuv420p", [mjpeg_slot_bytes] for
-    "mjpeg", [deep_frame_bytes] for the deep formats.  With ``resize`` (FrameResize) the frames travel at its size, whatever the generator's."""
-    side = int(getattr(generator, "size", 0)) or _output_dims(out_size)[0]
-    if resize is not None:
-        shape = (resize.size[1], resize.size[0], 3)
-    elif out_size == 1920:
-        shape = (1080, 1920, 3) if side == 1024 else (side, 2 * side, 3)  # 2048-px frames are resized on the device before they travel
-    elif out_size == 1080:
-        shape = (1920, 1080, 3) if side == 1024 else (2 * side, side, 3)
-    else:
-        shape = (side, side, 3)
-    if pix_fmt == "mjpeg":
-        return (mjpeg_slot_bytes(shape[1], shape[0]),)
-    if pix_fmt in DEEP_PIX_FMTS:
-        return (deep_frame_bytes(pix_fmt, shape[1], shape[0]),)
-    return (shape[0] * shape[1] * 3 // 2,) if pix_fmt == "yuv420p" else shape
+def render_folded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None):
+    """render_frames with an explicit ``fold`` (TemporalFold or None; the environment is not read for it) and the delivery size of the
+    environment ($MAUA_DELIVER_SIZE, as render_shard)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=fold, resize=_resize_from_env(),
+                         grade=None, lens=None, feedback=None)
+
+
+def render_delivered(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                     bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None):
+    """render_frames with ``fold`` and ``resize`` (FrameResize or None); the environment is read for neither, here and below."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=fold, resize=resize, grade=None,
+                         lens=None, feedback=None)
+
+
+def render_graded(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None):
+    """render_frames with ``fold``, ``resize`` and a colour ``grade`` (audioreactive/grade.py's Grade, or None)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=fold, resize=resize, grade=grade,
+                         lens=None, feedback=None)
+
+
+def render_lensed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+                  bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
+                  lens=None):
+    """render_frames with ``fold``, ``resize``, ``grade`` and a ``lens`` (audioreactive/lens.py's Lens, or None)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=fold, resize=resize, grade=grade,
+                         lens=lens, feedback=None)
+
+
+def render_fed(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation,
+               bends, rewrites, randomize_noise, ffmpeg_preset, _shard, transport=None, pipe_pix_fmt=None, fold=None, resize=None, grade=None,
+               lens=None, feedback=None):
+    """render_frames with every option as an ordinary parameter: ``fold``, ``resize``, ``grade``, ``lens`` and a ``feedback``
+    (audioreactive/feedback.py's Feedback, or None)."""
+    return render_frames(generator, latents, noise, offset, duration, batch_size, out_size, output_file, audio_file, truncation, bends,
+                         rewrites, randomize_noise, ffmpeg_preset, _shard, transport, pipe_pix_fmt, fold=fold, resize=resize, grade=grade,
+                         lens=lens, feedback=feedback)
+

@@ -318,9 +318,8 @@ def test_surface_and_dispatch_without_a_feedback(monkeypatch, built_lib):
     assert "feedback" not in inspect.signature(gav.generate).parameters
     lensed, fed = inspect.signature(render.render_lensed).parameters, inspect.signature(render.render_fed).parameters
     assert list(fed) == list(lensed) + ["feedback"] and fed["feedback"].default is None
-    frames = inspect.signature(render._render_frames).parameters
-    assert list(frames)[:-1] == list(inspect.signature(render._render_shard).parameters) and list(frames)[-1] == "feedback"
-    assert frames["feedback"].default is None
+    frames = inspect.signature(render.render_frames).parameters
+    assert list(frames) == list(fed) and frames["feedback"].default is None and frames["feedback"].kind is inspect.Parameter.KEYWORD_ONLY
     assert list(inspect.signature(render.feedback_frames).parameters) == ["images", "ops", "first", "count", "scratch"]
     P, I = c_void_p, c_int
     pinned = {"maua_feedback_f32": [P, P, P, I, I, I, I, P, I, I, I, P], "maua_feedback_plan": [I, I, I, P, I, P, P]}
@@ -330,17 +329,18 @@ def test_surface_and_dispatch_without_a_feedback(monkeypatch, built_lib):
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "maua_hip.h")).read()
     for name in pinned:
         assert f"int {name}(" in header
-    # without a feedback render_fed is render_lensed, call for call; with one the body gets it as its last keyword
+    # with or without a feedback render_fed is one call of the body, which gets every option by keyword (the other entries and the
+    # environment: tests/test_render_entries_host.py)
     seen = []
     args = ("G", "lat", [], 0, 1.0, 8, 512, None, None, 1.0, [], {}, False, "slow", None)
-    monkeypatch.setattr(render, "render_lensed", lambda *a, **kw: seen.append(("lensed", a, kw)) or 5)
-    monkeypatch.setattr(render, "_render_frames", lambda *a, **kw: seen.append(("frames", a, kw)) or 6)
-    assert render.render_fed(*args) == 5 and seen[-1] == ("lensed", args + (None,) * 6, {})
-    assert render.render_fed(*args, "host", "yuv420p", "F", "R", "GR", "L") == 5 and seen[-1] == ("lensed", args + ("host", "yuv420p", "F", "R", "GR", "L"), {})
-    assert render.render_fed(*args, lens="L", feedback="FB") == 6
-    assert seen[-1] == ("frames", args + (None, None, None, None, None, "L"), {"feedback": "FB"})
-    # the plain entry points reach the body without the keyword: the calls of a render without a feedback are the parent's
-    assert render._render_shard(*args, None, None, None) == 6 and seen[-1] == ("frames", args + (None,) * 6, {})
+    monkeypatch.setattr(render, "render_frames", lambda *a, **kw: seen.append((a, kw)) or 6)
+    none = dict(fold=None, resize=None, grade=None, lens=None, feedback=None)
+    assert render.render_fed(*args) == 6 and seen[-1] == (args + (None, None), none)
+    assert render.render_fed(*args, "host", "yuv420p", "F", "R", "GR", "L") == 6
+    assert seen[-1] == (args + ("host", "yuv420p"), dict(fold="F", resize="R", grade="GR", lens="L", feedback=None))
+    assert render.render_fed(*args, lens="L", feedback="FB") == 6 and seen[-1] == (args + (None, None), dict(none, lens="L", feedback="FB"))
+    for entry in (render.render_shard, render.render_folded, render.render_delivered, render.render_graded, render.render_lensed):
+        assert entry(*args) == 6 and seen[-1][1]["feedback"] is None  # the other entries reach the body without a feedback
 
 
 def test_a_feedback_is_refused_on_more_than_one_rank_before_the_sink_opens(monkeypatch, tmp_path, built_lib):

@@ -301,25 +301,13 @@ def test_pinned_signatures_and_the_new_surface(built_lib):
     delivered = list(inspect.signature(render.render_delivered).parameters)
     graded = inspect.signature(render.render_graded).parameters
     assert list(graded) == delivered + ["grade"] and graded["grade"].default is None
-    for fn in (render.render, render.render_shard, render.render_folded, render.render_delivered, gav._render, gav._render_delivered,
-               gav._scatter_from_rank0):
+    for fn in (render.render, render.render_shard, render.render_folded, render.render_delivered, gav._scatter_from_rank0):
         assert "grade" not in inspect.signature(fn).parameters
     assert list(inspect.signature(render.grade_frames).parameters) == ["images", "grade_rows", "lut", "scratch", "out"]
     assert list(inspect.signature(gav._scatter_from_rank0).parameters) == ["latents", "noise", "truncation", "bends", "rewrites", "n_frames", "subframes"]
     from maua_stylegan2_amd import _lib
 
     assert {"maua_grade_f32", "maua_grade_to_u8"} <= set(_lib.exported_symbols()) and _lib.ABI_VERSION == 8
-
-
-def test_dispatch_without_a_grade_is_render_delivereds(monkeypatch, built_lib):
-    from maua_stylegan2_amd import render
-
-    seen = []
-    monkeypatch.setattr(render, "_render_shard", lambda *a, **kw: seen.append((a, kw)) or 5)
-    args = ("G", "lat", [], 0, 1.0, 8, 512, None, None, 1.0, [], {}, False, "slow", None)
-    assert render.render_graded(*args) == 5 and seen[-1] == (args + (None, None, None), {})
-    assert render.render_graded(*args, resize="R") == 5 and seen[-1] == (args + (None, None, None, "R"), {})
-    assert render.render_graded(*args, "host", "yuv420p", "F", None, "GR") == 5 and seen[-1] == (args + ("host", "yuv420p", "F", None, "GR"), {})
 
 
 def test_grade_flags_parse_and_resolve(tmp_path, built_lib):

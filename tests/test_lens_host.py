@@ -393,10 +393,9 @@ def test_pinned_signatures_and_the_new_surface(built_lib):
     assert list(sig.parameters)[-1] == "args" and len(sig.parameters) == 31 and not {"lens", "lens_spec"} & set(sig.parameters)
     graded, lensed = inspect.signature(render.render_graded).parameters, inspect.signature(render.render_lensed).parameters
     assert list(lensed) == list(graded) + ["lens"] and lensed["lens"].default is None and lensed["grade"].default is None
-    shard = inspect.signature(render._render_shard).parameters
-    assert list(shard)[-3:] == ["resize", "grade", "lens"] and shard["lens"].default is None
-    for fn in (render.render, render.render_shard, render.render_folded, render.render_delivered, render.render_graded, gav._render, gav._render_delivered,
-               gav._scatter_from_rank0):
+    body = inspect.signature(render.render_frames).parameters
+    assert list(body)[-3:] == ["grade", "lens", "feedback"] and body["lens"].default is None
+    for fn in (render.render, render.render_shard, render.render_folded, render.render_delivered, render.render_graded, gav._scatter_from_rank0):
         assert "lens" not in inspect.signature(fn).parameters
     assert list(inspect.signature(render.lens_frames).parameters) == ["images", "lens_ops", "first", "count", "scratch"]
     P, I = c_void_p, c_int
@@ -440,19 +439,6 @@ def test_the_blur_plan_answers_without_a_device(built_lib):
     for bad in ((0, 4, 1), (4, 0, 1), (4, 4, -1), (4, 4, 65)):
         assert fn(*bad, 4096, plan) == -22
     assert fn(4, 4, 1, 4096, None) == -22
-
-
-def test_dispatch_without_a_lens_is_render_gradeds(monkeypatch, built_lib):
-    from maua_stylegan2_amd import render
-
-    seen = []
-    monkeypatch.setattr(render, "_render_shard", lambda *a, **kw: seen.append((a, kw)) or 5)
-    args = ("G", "lat", [], 0, 1.0, 8, 512, None, None, 1.0, [], {}, False, "slow", None)
-    assert render.render_lensed(*args) == 5 and seen[-1] == (args + (None, None, None), {})
-    assert render.render_lensed(*args, resize="R") == 5 and seen[-1] == (args + (None, None, None, "R"), {})
-    assert render.render_lensed(*args, "host", "yuv420p", "F", None, "GR") == 5 and seen[-1] == (args + ("host", "yuv420p", "F", None, "GR"), {})
-    assert render.render_lensed(*args, "host", "yuv420p", "F", None, "GR", "L") == 5 and seen[-1] == (args + ("host", "yuv420p", "F", None, "GR", "L"), {})
-    assert render.render_lensed(*args, lens="L") == 5 and seen[-1] == (args + (None, None, None, None, None, "L"), {})
 
 
 def test_the_glow_example_builds_a_valid_lens(monkeypatch, built_lib):

@@ -1,6 +1,7 @@
 """CPU: the Motion-JPEG pipe format without a device — the integer definition of the stream (tests/jpeg_ref.py, the oracle
 tests/test_mjpeg_gpu.py compares csrc/jpeg.hip against byte for byte) against an independent decoder and encoder (Pillow / libjpeg), its
 structure, the host-side entries of the C ABI, the AVI writer, the frame sink's mjpeg branch and the CLI."""
+import argparse
 import io
 import json
 import os
@@ -345,15 +346,14 @@ def test_cli_flag_quality_resolution_and_the_way_into_the_render_loop(monkeypatc
         render._mjpeg_quality("mjpeg")
     monkeypatch.delenv("MAUA_MJPEG_QUALITY")
 
-    calls = []
-    monkeypatch.setattr(render, "render", lambda **kw: calls.append(("render", kw)) or 7)
-    monkeypatch.setattr(render, "render_shard", lambda *a, **kw: calls.append(("render_shard", a, kw)) or 9)
-    base = ("G", "lat", ["nz"], "a.wav", 0.5, 2.0, 4, 1.0, [], {}, 512, "o.mp4", False, "slow")
-    assert gav._render(*base, None, "mjpeg", 85) == 9 and calls[-1][2] == {"pipe_pix_fmt": "mjpeg:85"} and calls[-1][1][-1] is None
-    assert gav._render(*base, (0, 3, 6), "mjpeg", 90) == 9 and calls[-1][2] == {"pipe_pix_fmt": "mjpeg:90"} and calls[-1][1][-1] == (0, 3, 6)
-    assert gav._render(*base, None, "mjpeg") == 9 and calls[-1][2] == {"pipe_pix_fmt": "mjpeg"}
-    assert gav._render(*base, None, "yuv420p", 85) == 9 and calls[-1][2] == {"pipe_pix_fmt": "yuv420p"}
-    assert gav._render(*base, None, "rgb24", 85) == 7 and calls[-1][0] == "render"  # the default path calls what it called before
+    # what generate() hands the body (every combination, and the positionals: tests/test_render_entries_host.py): the quality travels
+    # in the format's name, and only in mjpeg's
+    for name in ("MAUA_SUBFRAMES", "MAUA_DELIVER_SIZE"):
+        monkeypatch.delenv(name, raising=False)
+    for pix_fmt, quality, want in (("mjpeg", 85, "mjpeg:85"), ("mjpeg", 90, "mjpeg:90"), ("mjpeg", None, "mjpeg"), ("yuv420p", 85, "yuv420p"), ("rgb24", 85, None)):
+        namespace = argparse.Namespace(pipe_pix_fmt=pix_fmt, mjpeg_quality=quality)
+        assert gav._tail_options(namespace, None, None, None, None) == (want, None, None)
+        assert gav._pipe_format_of(namespace) == (want or "rgb24")
 
 
 def test_transport_frame_shape_is_the_flat_slot(built_lib):

@@ -209,32 +209,9 @@ def test_pinned_signatures_are_unchanged_and_render_delivered_extends_them(built
     delivered = inspect.signature(render.render_delivered).parameters
     assert list(delivered) == shard + ["fold", "resize"] and delivered["fold"].default is None and delivered["resize"].default is None
     assert list(inspect.signature(render.render).parameters)[-1] == "ffmpeg_preset" and len(inspect.signature(render.render).parameters) == 14
-    assert list(inspect.signature(gav._render).parameters)[-3:] == ["pipe_pix_fmt", "mjpeg_quality", "fold"]
-    for fn in (render.render, render.render_shard, render.render_folded, gav.generate, gav._render):
+    for fn in (render.render, render.render_shard, render.render_folded, gav.generate):
         assert not {"resize", "deliver_size", "deliver_filter", "deliver_fit"} & set(inspect.signature(fn).parameters)
     assert list(inspect.signature(render.resize_frames).parameters) == ["frames", "resize", "scratch"]
-
-
-def test_dispatch_without_a_delivery_size_is_call_for_call_todays(monkeypatch, built_lib):
-    from maua_stylegan2_amd import generate_audiovisual as gav
-    from maua_stylegan2_amd import render
-
-    for name in ("MAUA_DELIVER_SIZE", "MAUA_DELIVER_FILTER", "MAUA_DELIVER_FIT", "MAUA_SUBFRAMES"):
-        monkeypatch.delenv(name, raising=False)
-    seen = []
-    monkeypatch.setattr(render, "_render_shard", lambda *a, **kw: seen.append((a, kw)) or 5)
-    args = ("G", "lat", [], 0, 1.0, 8, 512, None, None, 1.0, [], {}, False, "slow", None)
-    assert render.render_shard(*args) == 5 and seen[-1] == (args + (None, None, None), {})
-    assert render.render_folded(*args, "host", "yuv420p") == 5 and seen[-1] == (args + ("host", "yuv420p", None), {})
-    assert render.render_delivered(*args) == 5 and seen[-1] == (args + (None, None, None), {})
-    resize = render.FrameResize("64x36")
-    assert render.render_delivered(*args, resize=resize) == 5 and seen[-1] == (args + (None, None, None, resize), {})
-    monkeypatch.setenv("MAUA_DELIVER_SIZE", "64x36")
-    monkeypatch.setenv("MAUA_DELIVER_FIT", "stretch")
-    for entry in (render.render_shard, render.render_folded):
-        assert entry(*args) == 5 and seen[-1][0][:-1] == args + (None, None, None) and seen[-1][0][-1].key() == (64, 36, "lanczos", "stretch")
-    assert render.render("G", "lat", [], 0, 1.0, 8, 512, None) == 5 and seen[-1][0][-1].key() == (64, 36, "lanczos", "stretch")
-    assert render.render_delivered(*args) == 5 and len(seen[-1][0]) == 18  # the explicit entry does not read the environment
 
 
 def test_four_wrong_twins_are_told_apart_by_the_gpu_case_list():

@@ -468,8 +468,9 @@ def _generate_worker(rank, world, port, out_dir):
 
         captured = {}
 
-        def fake_render_shard(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
-                              bends, rewrites, randomize_noise, ffmpeg_preset, shard):
+        def fake_render_frames(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
+                               bends, rewrites, randomize_noise, ffmpeg_preset, shard, *, pipe_pix_fmt, fold, resize, grade, lens, feedback):
+            assert (pipe_pix_fmt, fold, resize, grade, lens, feedback) == (None,) * 6  # a plain job: no option of the tail is set
             mark("render")
             captured.update(latents=latents.clone(), bend_noise=bends[0]["transform"].noise.clone(),
                             bend_mod=bends[1]["modulation"].clone(), rewrite_draw=rewrites["w"][0].draw.clone(), shard=shard)
@@ -479,7 +480,7 @@ def _generate_worker(rank, world, port, out_dir):
         gav.load_generator = fake_load_generator
         gav.render.prepare = fake_prepare
         gav._scatter_from_rank0 = logged_scatter
-        gav.render.render_shard = fake_render_shard
+        gav.render.render_frames = fake_render_frames
         np.save("selection.npy", np.arange(3 * 2 * 4, dtype=np.float32).reshape(3, 2, 4))
 
         def get_latents(selection, args):

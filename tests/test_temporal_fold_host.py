@@ -160,56 +160,7 @@ def test_pinned_signatures_hold_and_render_folded_exists(built_lib):
     assert list(inspect.signature(render.render).parameters)[-1] == "ffmpeg_preset"
     for fn in (render.render, gav.generate):
         assert not {"fold", "subframes", "shutter", "shutter_light"} & set(inspect.signature(fn).parameters)
-    params = inspect.signature(gav._render).parameters
-    assert list(params)[-3:] == ["pipe_pix_fmt", "mjpeg_quality", "fold"] and params["fold"].default is None
     assert list(inspect.signature(render.fold_frames).parameters) == ["u8", "fold", "scratch"]
-
-
-def test_render_dispatch_is_unchanged_without_a_fold(monkeypatch, built_lib):
-    from maua_stylegan2_amd import generate_audiovisual as gav
-    from maua_stylegan2_amd import render
-
-    calls = []
-    monkeypatch.setattr(render, "render", lambda **kw: calls.append(("render", kw)) or 7)
-    monkeypatch.setattr(render, "render_shard", lambda *a, **kw: calls.append(("render_shard", a, kw)) or 9)
-    monkeypatch.setattr(render, "render_folded", lambda *a, **kw: calls.append(("render_folded", a, kw)) or 11)
-    base = ("G", "lat", ["nz"], "a.wav", 0.5, 2.0, 4, 1.0, [], {}, 512, "o.mp4", False, "slow")
-    one = render.TemporalFold(1, "box", "linear")
-    for extra in ((), (None,), (one,)):
-        calls.clear()
-        assert gav._render(*base, None, None, None, *extra) == 7
-        assert gav._render(*base, (0, 3, 6), None, None, *extra) == 9
-        assert gav._render(*base, None, "yuv420p", None, *extra) == 9
-        assert [c[0] for c in calls] == ["render", "render_shard", "render_shard"]
-        assert set(calls[0][1]) == {"generator", "latents", "noise", "audio_file", "offset", "duration", "batch_size", "truncation", "bends",
-                                    "rewrites", "out_size", "output_file", "randomize_noise", "ffmpeg_preset"}
-        assert calls[1][2] == {} and calls[2][2] == {"pipe_pix_fmt": "yuv420p"}
-    fold = render.TemporalFold(4, "tent")
-    assert gav._render(*base, (0, 8, 16), "mjpeg", 80, fold) == 11
-    name, args, kwargs = calls[-1]
-    assert name == "render_folded" and kwargs == {"pipe_pix_fmt": "mjpeg:80", "fold": fold}
-    assert args == ("G", "lat", ["nz"], 0.5, 2.0, 4, 512, "o.mp4", "a.wav", 1.0, [], {}, False, "slow", (0, 8, 16))
-    assert gav._render(*base, None, None, None, fold) == 11 and calls[-1][2] == {"pipe_pix_fmt": None, "fold": fold}
-
-
-def test_render_shard_reads_the_fold_from_the_environment_only(monkeypatch, built_lib):
-    from maua_stylegan2_amd import render
-
-    seen = []
-    monkeypatch.setattr(render, "_render_shard", lambda *a: seen.append(a) or 5)
-    for name in ("MAUA_SUBFRAMES", "MAUA_SHUTTER", "MAUA_SHUTTER_LIGHT"):
-        monkeypatch.delenv(name, raising=False)
-    args = ("G", "lat", [], 0, 1.0, 8, 512, None, None, 1.0, [], {}, False, "slow", None)
-    assert render.render_shard(*args) == 5 and seen[-1] == args + (None, None, None)
-    assert render.render("G", "lat", [], 0, 1.0, 8, 512, None) == 5 and seen[-1][-1] is None
-    monkeypatch.setenv("MAUA_SUBFRAMES", "2")
-    monkeypatch.setenv("MAUA_SHUTTER", "3,1")
-    assert render.render_shard(*args, "host", "yuv420p") == 5
-    assert seen[-1][:-1] == args + ("host", "yuv420p") and seen[-1][-1].weights == (3, 1)
-    assert render.render("G", "lat", [], 0, 1.0, 8, 512, None) == 5 and seen[-1][-1].subframes == 2
-    fold = render.TemporalFold(4)
-    assert render.render_folded(*args, fold=fold) == 5 and seen[-1][-1] is fold
-    assert render.render_folded(*args) == 5 and seen[-1][-1] is None  # the explicit argument wins: the environment is not read
 
 
 def test_frame_counts_are_checked_before_anything_runs(built_lib):
@@ -247,7 +198,10 @@ def test_generate_renders_at_the_sub_frame_rate_and_delivers_at_fps(monkeypatch,
         seen.update(fps=args.fps, n_frames=args.n_frames, video_fps=args.video_fps, subframes=args.subframes)
         return torch.zeros(args.n_frames, 2, 4)
 
-    monkeypatch.setattr(gav, "_render", lambda *a: rendered.append(a) or len(a[1]))
+    for name in ("MAUA_PIPE_PIX_FMT", "MAUA_SUBFRAMES", "MAUA_DELIVER_SIZE"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(gav.render, "render_frames", lambda *a, **kw: rendered.append((a, kw)) or len(a[1]))
+    plain = dict(pipe_pix_fmt=None, fold=None, resize=None, grade=None, lens=None, feedback=None)
     common = dict(ckpt=None, audio_file="a.wav", get_latents=get_latents, get_noise=lambda **kw: None, fps=24, batch=8, out_size=512, G_res=512)
 
     def run(**extra):
@@ -258,15 +212,15 @@ def test_generate_renders_at_the_sub_frame_rate_and_delivers_at_fps(monkeypatch,
 
     run()
     assert seen == dict(fps=24, n_frames=50, video_fps=24, subframes=1) and smf[-1] == 24 / 30
-    assert len(rendered[-1]) == 17 and rendered[-1][4:7] == (0, 2.1, 8)  # exactly the arguments of a job that knows no fold
+    assert len(rendered[-1][0]) == 15 and rendered[-1][0][3:6] == (0, 2.1, 8) and rendered[-1][1] == plain  # no fold reaches the body
     run(subframes=1, shutter="tent", shutter_light="linear")
-    assert seen == dict(fps=24, n_frames=50, video_fps=24, subframes=1) and len(rendered[-1]) == 17
+    assert seen == dict(fps=24, n_frames=50, video_fps=24, subframes=1) and len(rendered[-1][0]) == 15 and rendered[-1][1] == plain
     args = run(subframes=4, shutter="tent", shutter_light="linear")
     assert seen == dict(fps=96, n_frames=200, video_fps=24, subframes=4) and smf[-1] == 96 / 30
     assert (args.fps, args.n_frames, args.video_fps, args.subframes) == (96, 200, 24, 4)
-    fold = rendered[-1][-1]
-    assert len(rendered[-1]) == 18 and (fold.subframes, fold.weights, fold.light) == (4, (1, 2, 2, 1), "linear")
-    assert len(rendered[-1][1]) == 200 and rendered[-1][5] == 2.1
+    fold = rendered[-1][1]["fold"]
+    assert rendered[-1][1] == dict(plain, fold=fold) and (fold.subframes, fold.weights, fold.light) == (4, (1, 2, 2, 1), "linear")
+    assert len(rendered[-1][0]) == 15 and len(rendered[-1][0][1]) == 200 and rendered[-1][0][4] == 2.1
 
 
 # ------------------------------------------------------------------------------------------------- sharding in units of delivered frames

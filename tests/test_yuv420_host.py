@@ -1,6 +1,7 @@
 """CPU: the planar YUV 4:2:0 pipe format without a device — the integer definition of the conversion (the oracle the GPU tests in
 tests/test_yuv420_gpu.py compare csrc/yuv420.hip against, bit for bit), the frame sink's yuv420p branch, the fallback file, the CLI flag
 and the way the format travels from generate() into the render loop."""
+import argparse
 import json
 import os
 import stat
@@ -211,16 +212,12 @@ def test_cli_flag_and_the_formats_way_into_the_render_loop(monkeypatch, built_li
         render._pipe_pix_fmt("nv12")
     monkeypatch.delenv("MAUA_PIPE_PIX_FMT")
 
-    calls = []
-    monkeypatch.setattr(render, "render", lambda **kw: calls.append(("render", kw)) or 7)
-    monkeypatch.setattr(render, "render_shard", lambda *a, **kw: calls.append(("render_shard", a, kw)) or 9)
-    base = ("G", "lat", ["nz"], "a.wav", 0.5, 2.0, 4, 1.0, [], {}, 512, "o.mp4", False, "slow")
-    assert gav._render(*base, None) == 7 and gav._render(*base, None, "rgb24") == 7  # the default path calls what it called before
-    assert [c[0] for c in calls] == ["render", "render"] and all("pipe_pix_fmt" not in c[1] for c in calls)
-    assert gav._render(*base, (0, 3, 6)) == 9 and calls[-1][2] == {}
-    assert gav._render(*base, None, "yuv420p") == 9 and calls[-1][2] == {"pipe_pix_fmt": "yuv420p"} and calls[-1][1][-1] is None
-    assert gav._render(*base, (0, 3, 6), "yuv420p") == 9 and calls[-1][2] == {"pipe_pix_fmt": "yuv420p"} and calls[-1][1][-1] == (0, 3, 6)
-    assert calls[-1][1][:8] == ("G", "lat", ["nz"], 0.5, 2.0, 4, 512, "o.mp4")
+    # what generate() hands the body (every combination, and the positionals: tests/test_render_entries_host.py): the flag's default is
+    # "not set" — the body then resolves the environment —, another format is passed on
+    for name in ("MAUA_SUBFRAMES", "MAUA_DELIVER_SIZE"):
+        monkeypatch.delenv(name, raising=False)
+    for namespace, want in ((argparse.Namespace(), None), (argparse.Namespace(pipe_pix_fmt="rgb24"), None), (argparse.Namespace(pipe_pix_fmt="yuv420p"), "yuv420p")):
+        assert gav._tail_options(namespace, None, None, None, None) == (want, None, None)
 
 
 def test_transport_frame_shape_is_flat_for_the_planar_format(built_lib):
