@@ -17,7 +17,9 @@ frame's width and height, so the rows are built per frame size (``rows`` / ``ope
 import math
 
 import numpy as np
-import torch as th
+
+from . import frame_table
+from .frame_table import FrameTable, collect, host64
 
 __all__ = ["Feedback", "FEEDBACK_ROW"]
 
@@ -29,13 +31,7 @@ _A, _TY, _GAIN, _TINT, _DRY, _LIMIT, _STILL = 0, 5, 6, 7, 10, 11, 12
 P_GAIN, P_DRY, P_ZOOM, P_ROTATE, P_TX, P_TY, P_TINT, P_LIMIT, P_COLS = 0, 1, 2, 3, 4, 5, 6, 9, 10
 
 
-def _host(value):
-    if isinstance(value, th.Tensor):
-        return value.detach().to("cpu", th.float64).numpy()
-    return np.asarray(value, np.float64)
-
-
-class Feedback:
+class Feedback(FrameTable):
     """Frame feedback: one parameter row per rendered frame, or one row for all of them.
 
     ``gain``, ``dry``, ``zoom``, ``rotate`` are scalars or per-frame sequences — [n_frames] or [n_frames, 1] —, ``translate`` a pair or
@@ -56,39 +52,12 @@ class Feedback:
     Refused: non-finite values, gain < 0, limit <= 0, zoom <= 0, sequences of different lengths, an unknown mode or border.  The device
     checks none of this."""
 
+    MASK = "neutral"  # (a neutral row — gain 0, dry 1 — is this class's identity)
+
     def __init__(self, n_frames=None, *, gain=0, dry=1, zoom=1, rotate=0, translate=(0, 0), tint=(1, 1, 1), limit=4.0, mode="add",
                  border="zero"):
-        if n_frames is not None and (isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 1):
-            raise ValueError(f"Feedback: n_frames must be a positive integer, got {n_frames!r}")
-        given = None if n_frames is None else int(n_frames)
-        lengths = {}
-
-        def arg(name, value, width=1):
-            """-> float64 [n or 1, width]"""
-            a = _host(value)
-            if not np.all(np.isfinite(a)):
-                raise ValueError(f"Feedback: {name} holds non-finite values")
-            if width == 1 and a.ndim == 0:
-                return a.reshape(1, 1)
-            if width > 1 and a.ndim == 1 and a.shape[0] == width:
-                return a.reshape(1, width)
-            if width > 1 and not (a.ndim == 2 and a.shape[1] == width):
-                raise ValueError(f"Feedback: {name} of shape {a.shape} is neither {width} values nor [n_frames, {width}]")
-            if a.ndim > 2 or a.ndim == 0 or (a.ndim == 2 and width == 1 and a.shape[1] != 1):
-                raise ValueError(f"Feedback: {name} of shape {a.shape} is neither a scalar nor [n_frames]")
-            lengths[name] = a.shape[0]
-            return a.reshape(a.shape[0], -1)
-
-        cols = [arg("gain", gain), arg("dry", dry), arg("zoom", zoom), arg("rotate", rotate), arg("translate", translate, 2),
-                arg("tint", tint, 3), arg("limit", limit)]
-        want = given
-        for name, n in lengths.items():
-            if want is None:
-                want = n
-            if n != want:
-                other = "n_frames" if given is not None else next(k for k, v in lengths.items() if v == want)
-                raise ValueError(f"Feedback: {name} has {n} entries, {other} says {want}")
-        n = want if lengths else 1  # (without a sequence one row serves every frame, whatever n_frames says)
+        n, cols = collect("Feedback", n_frames, [("gain", gain, 1, False), ("dry", dry, 1, False), ("zoom", zoom, 1, False), ("rotate", rotate, 1, False),
+                                                 ("translate", translate, 2, False), ("tint", tint, 3, False), ("limit", limit, 1, False)])
         table = np.concatenate([np.broadcast_to(c, (n, c.shape[1])) for c in cols], axis=1)
         self._init(table, mode, border)
 
@@ -120,7 +89,7 @@ class Feedback:
         """A feedback from a finished parameter table, float64 [n, 10]: gain, dry, zoom, rotate, translate x, y, tint r, g, b, limit per row
         (validated as the constructor does)."""
         self = cls.__new__(cls)
-        self._init(_host(table), mode, border)
+        self._init(host64(table), mode, border)
         return self
 
     @staticmethod
@@ -132,20 +101,8 @@ class Feedback:
             raise ValueError(f"Feedback.gain_for: a half-life of {half_life_seconds!r} s at {fps!r} fps")
         return 0.5 ** (1.0 / frames)
 
-    @property
-    def n_rows(self):
-        return self.table.shape[0]
-
-    def __len__(self):
-        return self.n_rows
-
-    @property
-    def is_identity(self):
-        """True when every row is neutral (gain 0, dry 1): the render then delivers the plain frames bit for bit and runs no kernel."""
-        return bool(self.neutral.all())
-
     def __repr__(self):
-        return (f"Feedback({self.n_rows} row{'s' if self.n_rows != 1 else ''}, mode={self.mode}, border={self.border}, "
+        return (f"Feedback({self._count()}, mode={self.mode}, border={self.border}, "
                 f"neutral={int(self.neutral.sum())})")
 
     def rows(self, h, w):
@@ -176,56 +133,25 @@ class Feedback:
             self._rows[key] = rows
         return self._rows[key]
 
-    def operands(self, device, h, w):
+    def operands(self, h, w):
         """(rows, mode index, border index) for frames of h x w.  The rows stay on the HOST (float32 [n, 16], contiguous): the entry reads
-        them while it plans its launches and hands each launch its row by value; ``device`` is accepted for symmetry with Lens.operands."""
-        del device
+        them while it plans its launches and hands each launch its row by value."""
         return self.rows(h, w), MODES.index(self.mode), BORDERS.index(self.border)
 
-    def slice(self, lo, hi):
-        """The feedback of the frames [lo, hi): a one-row feedback is its own slice.  (The recurrence starts from black at ``lo``.)"""
-        if self.n_rows == 1:
-            return self
-        if not 0 <= lo <= hi <= self.n_rows:
-            raise ValueError(f"Feedback.slice: [{lo}, {hi}) is not inside the {self.n_rows} rows")
-        if hi == lo:
-            raise ValueError("Feedback.slice: an empty slice")
-        return Feedback.from_tables(self.table[lo:hi], self.mode, self.border)
+    def tables(self):
+        """(table, mode, border): ``Feedback.from_tables(*x.tables())`` is x."""
+        return self.table, self.mode, self.border
+
+    def _block(self, lo, hi):
+        return Feedback.from_tables(self.table[lo:hi], self.mode, self.border)  # (the recurrence starts from black at ``lo``)
 
 
 SPEC_KEYS = ("gain", "dry", "zoom", "rotate", "translate", "tint", "limit", "mode", "border")
-_SPEC_WIDTH = {"translate": 2, "tint": 3}
 
 
 def parse_spec(text):
     """A static feedback as text, ``"gain=0.92,zoom=1.015,rotate=0.3,mode=max,border=mirror"`` (the --feedback flag), -> the keyword
     arguments of Feedback.  Keys: SPEC_KEYS; a value is a number, translate two and tint three numbers joined by ``:``
     (``translate=0.01:0``), mode and border a name."""
-    out = {}
-    for part in str(text).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        key, eq, value = part.partition("=")
-        key, value = key.strip(), value.strip()
-        if not eq or key not in SPEC_KEYS:
-            raise ValueError(f"--feedback {text!r}: {part!r} is not key=value with a key of {', '.join(SPEC_KEYS)}")
-        if key in out:
-            raise ValueError(f"--feedback {text!r}: {key} is given twice")
-        if key in ("mode", "border"):
-            names = MODES if key == "mode" else BORDERS
-            if value not in names:
-                raise ValueError(f"--feedback {text!r}: {key} is one of {', '.join(names)}, not {value!r}")
-            out[key] = value
-            continue
-        try:
-            nums = [float(v) for v in value.split(":")]
-        except ValueError:
-            raise ValueError(f"--feedback {text!r}: {value!r} is not a number") from None
-        width = _SPEC_WIDTH.get(key, 1)
-        if len(nums) != width:
-            raise ValueError(f"--feedback {text!r}: {key} takes " + (f"{width} numbers joined by ':'" if width > 1 else "one number"))
-        out[key] = nums if width > 1 else nums[0]
-    if not out:
-        raise ValueError(f"--feedback {text!r} names no parameter")
-    return out
+    counts = {k: ({"translate": 2, "tint": 3}.get(k, 1),) for k in SPEC_KEYS[:-2]}
+    return frame_table.parse_spec("--feedback", text, counts, {"mode": MODES, "border": BORDERS})

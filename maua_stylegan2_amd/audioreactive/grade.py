@@ -11,6 +11,9 @@ import math
 import numpy as np
 import torch as th
 
+from . import frame_table
+from .frame_table import FrameTable, collect, host64
+
 __all__ = ["Grade", "load_cube", "save_cube", "lut_from_function", "hue_matrix", "saturation_matrix", "GRADE_ROW"]
 
 GRADE_ROW = 24
@@ -39,13 +42,7 @@ def hue_matrix(degrees):
     return np.where((d == 0)[..., None, None], np.eye(3), m)
 
 
-def _host(value):
-    if isinstance(value, th.Tensor):
-        return value.detach().to("cpu", th.float64).numpy()
-    return np.asarray(value, np.float64)
-
-
-class Grade:
+class Grade(FrameTable):
     """A colour grade: one parameter row per rendered frame, or one row for all of them, and an optional 3-D LUT.
 
     Every argument is a scalar, a per-channel triple (R, G, B) where it says so, or a per-frame sequence — [n_frames], [n_frames, 1] or
@@ -69,58 +66,12 @@ class Grade:
 
     def __init__(self, n_frames=None, *, exposure=0, contrast=1, pivot=0.5, slope=1, offset=0, power=1, gamma=None, white_balance=None,
                  saturation=1, hue=0, matrix=None, bias=0, lut=None, lut_mix=1):
-        if n_frames is not None and (isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 1):
-            raise ValueError(f"Grade: n_frames must be a positive integer, got {n_frames!r}")
-        given = None if n_frames is None else int(n_frames)
-        lengths = {}
-
-        def arg(name, value, channels):
-            """-> float64 [n or 1, 3 or 1]"""
-            a = _host(value)
-            if not np.all(np.isfinite(a)):
-                raise ValueError(f"Grade: {name} holds non-finite values")
-            if a.ndim == 0:
-                return a.reshape(1, 1)
-            if a.ndim == 1 and channels and a.shape[0] == 3:
-                return a.reshape(1, 3)
-            if a.ndim == 2 and a.shape[1] not in ((1, 3) if channels else (1,)):
-                raise ValueError(f"Grade: {name} of shape {a.shape} is neither [n_frames]" + (", [3] nor [n_frames, 3]" if channels else " nor a scalar"))
-            if a.ndim > 2:
-                raise ValueError(f"Grade: {name} has {a.ndim} dimensions")
-            lengths[name] = a.shape[0]
-            return a.reshape(a.shape[0], -1)
-
-        exposure = arg("exposure", exposure, False)
-        contrast = arg("contrast", contrast, False)
-        pivot = arg("pivot", pivot, False)
-        slope = arg("slope", slope, True)
-        offset = arg("offset", offset, True)
-        power = arg("power", power, True)
-        gamma = None if gamma is None else arg("gamma", gamma, True)
-        wb = None if white_balance is None else arg("white_balance", white_balance, True)
-        saturation = arg("saturation", saturation, False)
-        hue = arg("hue", hue, False)
-        bias = arg("bias", bias, True)
-        mix = arg("lut_mix", lut_mix, False)
-        user = None
-        if matrix is not None:
-            user = _host(matrix)
-            if not np.all(np.isfinite(user)):
-                raise ValueError("Grade: matrix holds non-finite values")
-            if user.shape == (3, 3):
-                user = user[None]
-            elif user.ndim == 3 and user.shape[1:] == (3, 3):
-                lengths["matrix"] = user.shape[0]
-            else:
-                raise ValueError(f"Grade: matrix of shape {user.shape} is neither [3, 3] nor [n_frames, 3, 3]")
-        want = given
-        for name, n in lengths.items():
-            if want is None:
-                want = n
-            if n != want:
-                other = "n_frames" if given is not None else next(k for k, v in lengths.items() if v == want)
-                raise ValueError(f"Grade: {name} has {n} entries, {other} says {want}")
-        n = want if lengths else 1  # (without a sequence one row serves every frame, whatever n_frames says)
+        per_frame, per_channel = (1, False), (3, True)
+        n, (exposure, contrast, pivot, slope, offset, power, gamma, wb, saturation, hue, bias, mix, user) = collect("Grade", n_frames, [
+            ("exposure", exposure, *per_frame), ("contrast", contrast, *per_frame), ("pivot", pivot, *per_frame), ("slope", slope, *per_channel),
+            ("offset", offset, *per_channel), ("power", power, *per_channel), ("gamma", gamma, *per_channel),
+            ("white_balance", white_balance, *per_channel), ("saturation", saturation, *per_frame), ("hue", hue, *per_frame),
+            ("bias", bias, *per_channel), ("lut_mix", lut_mix, *per_frame), ("matrix", matrix, (3, 3), False)])
         if np.any(power <= 0) or (gamma is not None and np.any(gamma <= 0)):
             raise ValueError("Grade: power and gamma must be greater than 0")
         if np.any(mix < 0) or np.any(mix > 1):
@@ -157,7 +108,7 @@ class Grade:
     @classmethod
     def from_table(cls, table, lut=None):
         """A grade from a finished row table [n, 24] (validated as the constructor validates) and an optional LUT."""
-        table = np.array(_host(table), np.float32)
+        table = np.array(host64(table), np.float32)
         if table.ndim != 2 or table.shape[1] != GRADE_ROW or table.shape[0] < 1:
             raise ValueError(f"Grade.from_table: the table must be [n, {GRADE_ROW}], got {table.shape}")
         if not np.all(np.isfinite(table)):
@@ -170,24 +121,14 @@ class Grade:
         self._init(table, _check_lut(lut))
         return self
 
-    @property
-    def n_rows(self):
-        return self.table.shape[0]
-
-    def __len__(self):
-        return self.n_rows
-
-    @property
-    def is_identity(self):
-        """True when every row is the identity: the render then delivers the ungraded frames bit for bit."""
-        return bool(self.identity.all())
+    from_tables = from_table  # (the name Lens and Feedback give theirs: ``from_tables(*x.tables())`` is x for the three)
 
     @property
     def lut_n(self):
         return 0 if self.lut is None else self.lut.shape[0]
 
     def __repr__(self):
-        return f"Grade({self.n_rows} row{'s' if self.n_rows != 1 else ''}, lut={'none' if self.lut is None else self.lut_n}, identity={int(self.identity.sum())})"
+        return f"Grade({self._count()}, lut={'none' if self.lut is None else self.lut_n}, identity={int(self.identity.sum())})"
 
     def rows(self, device):
         """The row table as a float32 tensor [n, 24] on ``device`` (uploaded once per device)."""
@@ -209,14 +150,11 @@ class Grade:
             self._device[key] = th.from_numpy(padded).to(device)
         return self._device[key]
 
-    def slice(self, lo, hi):
-        """The grade of the frames [lo, hi): a one-row grade is its own slice."""
-        if self.n_rows == 1:
-            return self
-        if not 0 <= lo <= hi <= self.n_rows:
-            raise ValueError(f"Grade.slice: [{lo}, {hi}) is not inside the {self.n_rows} rows")
-        if hi == lo:
-            raise ValueError("Grade.slice: an empty slice")
+    def tables(self):
+        """(table, lut): ``Grade.from_table(*g.tables())`` is g."""
+        return self.table, self.lut
+
+    def _block(self, lo, hi):
         return Grade.from_table(self.table[lo:hi], self.lut)
 
     def with_lut(self, lut, lut_mix=1.0):
@@ -236,28 +174,7 @@ SPEC_KEYS = ("exposure", "contrast", "pivot", "slope", "offset", "power", "gamma
 def parse_spec(text):
     """A static grade as text, ``"exposure=0.3,saturation=1.2,gamma=0.9,hue=15"`` (the --grade flag), -> the keyword arguments of Grade.
     Keys: SPEC_KEYS; a value is a number, or three numbers joined by ``:`` for the per-channel ones (``slope=1.1:1:0.9``)."""
-    out = {}
-    for part in str(text).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        key, eq, value = part.partition("=")
-        key = key.strip()
-        if not eq or key not in SPEC_KEYS:
-            raise ValueError(f"--grade {text!r}: {part!r} is not key=value with a key of {', '.join(SPEC_KEYS)}")
-        if key in out:
-            raise ValueError(f"--grade {text!r}: {key} is given twice")
-        try:
-            nums = [float(v) for v in value.split(":")]
-        except ValueError:
-            raise ValueError(f"--grade {text!r}: {value.strip()!r} is not a number") from None
-        per_channel = key in ("slope", "offset", "power", "gamma", "bias")
-        if len(nums) not in ((1, 3) if per_channel else (1,)):
-            raise ValueError(f"--grade {text!r}: {key} takes one number" + (" or three joined by ':'" if per_channel else ""))
-        out[key] = nums[0] if len(nums) == 1 else nums
-    if not out:
-        raise ValueError(f"--grade {text!r} names no parameter")
-    return out
+    return frame_table.parse_spec("--grade", text, {k: (1, 3) if k in ("slope", "offset", "power", "gamma", "bias") else (1,) for k in SPEC_KEYS})
 
 
 def _check_lut(lut):
@@ -265,7 +182,7 @@ def _check_lut(lut):
         return None
     if isinstance(lut, (str, bytes)) or hasattr(lut, "__fspath__"):
         lut = load_cube(lut)
-    table = np.ascontiguousarray(_host(lut), np.float32)
+    table = np.ascontiguousarray(host64(lut), np.float32)
     if table.ndim != 4 or table.shape[3] != 3 or not (table.shape[0] == table.shape[1] == table.shape[2]) or not LUT_MIN <= table.shape[0] <= LUT_MAX:
         raise ValueError(f"Grade: a LUT is [N, N, N, 3] with {LUT_MIN} <= N <= {LUT_MAX}, got {table.shape}")
     if not np.all(np.isfinite(table)):

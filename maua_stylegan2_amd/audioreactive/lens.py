@@ -17,6 +17,9 @@ import math
 import numpy as np
 import torch as th
 
+from . import frame_table
+from .frame_table import FrameTable, collect, host64
+
 __all__ = ["Lens", "LENS_ROW"]
 
 LENS_ROW = 16
@@ -25,12 +28,6 @@ REDUCTIONS = (1, 2, 4, 8)
 SIGMA_PER_REDUCTION = 6.0
 MAX_RADIUS = 64
 MAX_SHARPEN_SIGMA = 8.0
-
-
-def _host(value):
-    if isinstance(value, th.Tensor):
-        return value.detach().to("cpu", th.float64).numpy()
-    return np.asarray(value, np.float64)
 
 
 def plan_reduction(sigma_max):
@@ -56,7 +53,7 @@ def gaussian_taps(sigmas, radius):
     return out.astype(np.float32)
 
 
-class Lens:
+class Lens(FrameTable):
     """Lens effects: one parameter row per rendered frame, or one row for all of them.
 
     Every argument is a scalar or a per-frame sequence — [n_frames] or [n_frames, 1]; the tint a triple (R, G, B) or [n_frames, 3]; torch
@@ -76,45 +73,11 @@ class Lens:
 
     def __init__(self, n_frames=None, *, bloom=0, bloom_size=0.02, bloom_threshold=0.7, bloom_knee=0.1, bloom_tint=(1, 1, 1), sharpen=0,
                  sharpen_radius=1.0, vignette=0, vignette_inner=0.5, vignette_outer=1.0):
-        if n_frames is not None and (isinstance(n_frames, bool) or int(n_frames) != n_frames or int(n_frames) < 1):
-            raise ValueError(f"Lens: n_frames must be a positive integer, got {n_frames!r}")
-        given = None if n_frames is None else int(n_frames)
-        lengths = {}
-
-        def arg(name, value, channels=False):
-            """-> float64 [n or 1, 3 or 1]"""
-            a = _host(value)
-            if not np.all(np.isfinite(a)):
-                raise ValueError(f"Lens: {name} holds non-finite values")
-            if a.ndim == 0 and not channels:
-                return a.reshape(1, 1)
-            if a.ndim == 1 and channels and a.shape[0] == 3:
-                return a.reshape(1, 3)
-            if channels and not (a.ndim == 2 and a.shape[1] == 3):
-                raise ValueError(f"Lens: {name} of shape {a.shape} is neither a triple nor [n_frames, 3]")
-            if a.ndim > 2 or (a.ndim == 2 and not channels and a.shape[1] != 1):
-                raise ValueError(f"Lens: {name} of shape {a.shape} is neither a scalar nor [n_frames]")
-            lengths[name] = a.shape[0]
-            return a.reshape(a.shape[0], -1)
-
-        bloom = arg("bloom", bloom)
-        size = arg("bloom_size", bloom_size)
-        threshold = arg("bloom_threshold", bloom_threshold)
-        knee = arg("bloom_knee", bloom_knee)
-        tint = arg("bloom_tint", bloom_tint, True)
-        sharpen = arg("sharpen", sharpen)
-        radius = arg("sharpen_radius", sharpen_radius)
-        vignette = arg("vignette", vignette)
-        inner = arg("vignette_inner", vignette_inner)
-        outer = arg("vignette_outer", vignette_outer)
-        want = given
-        for name, n in lengths.items():
-            if want is None:
-                want = n
-            if n != want:
-                other = "n_frames" if given is not None else next(k for k, v in lengths.items() if v == want)
-                raise ValueError(f"Lens: {name} has {n} entries, {other} says {want}")
-        n = want if lengths else 1  # (without a sequence one row serves every frame, whatever n_frames says)
+        n, (bloom, size, threshold, knee, tint, sharpen, radius, vignette, inner, outer) = collect("Lens", n_frames, [
+            ("bloom", bloom, 1, False), ("bloom_size", bloom_size, 1, False), ("bloom_threshold", bloom_threshold, 1, False),
+            ("bloom_knee", bloom_knee, 1, False), ("bloom_tint", bloom_tint, 3, False), ("sharpen", sharpen, 1, False),
+            ("sharpen_radius", sharpen_radius, 1, False), ("vignette", vignette, 1, False), ("vignette_inner", vignette_inner, 1, False),
+            ("vignette_outer", vignette_outer, 1, False)])
         if np.any(bloom < 0):
             raise ValueError("Lens: bloom must not be negative")
         if np.any(knee < 0):
@@ -166,8 +129,8 @@ class Lens:
         """A lens from a finished row table [n, 16] and its per-row bloom sizes and sharpen sigmas [n] (validated as the constructor does).
         ``plan_max``: the (bloom_size, sharpen sigma) maxima the plan rule uses when the table is a block of a longer one (``.plan_max`` of
         the whole table); None: this table's own."""
-        table = np.array(_host(table), np.float32)
-        size, sigma = np.array(_host(bloom_size), np.float64).reshape(-1), np.array(_host(sharpen_sigma), np.float64).reshape(-1)
+        table = np.array(host64(table), np.float32)
+        size, sigma = np.array(host64(bloom_size), np.float64).reshape(-1), np.array(host64(sharpen_sigma), np.float64).reshape(-1)
         if table.ndim != 2 or table.shape[1] != LENS_ROW or table.shape[0] < 1:
             raise ValueError(f"Lens.from_tables: the table must be [n, {LENS_ROW}], got {table.shape}")
         if size.shape != (table.shape[0],) or sigma.shape != (table.shape[0],):
@@ -183,18 +146,6 @@ class Lens:
         return self
 
     @property
-    def n_rows(self):
-        return self.table.shape[0]
-
-    def __len__(self):
-        return self.n_rows
-
-    @property
-    def is_identity(self):
-        """True when every row is the identity: the render then delivers the plain frames bit for bit."""
-        return bool(self.identity.all())
-
-    @property
     def has_bloom(self):
         return bool((self.table[:, _BLOOM:_BLOOM + 3] != 0).any())
 
@@ -203,7 +154,7 @@ class Lens:
         return bool((self.table[:, _SHARPEN] != 0).any())
 
     def __repr__(self):
-        return f"Lens({self.n_rows} row{'s' if self.n_rows != 1 else ''}, bloom={self.has_bloom}, sharpen={self.has_sharpen}, identity={int(self.identity.sum())})"
+        return f"Lens({self._count()}, bloom={self.has_bloom}, sharpen={self.has_sharpen}, identity={int(self.identity.sum())})"
 
     def plan(self, h, w):
         """(d, bloom radius, bloom taps [n, radius + 1], sharpen radius, sharpen taps) on the host for frames of h x w (the plan rule).  The
@@ -232,15 +183,12 @@ class Lens:
             self._device[key] = (up(self.table), d, rb, up(bt), rs, up(st))
         return self._device[key]
 
-    def slice(self, lo, hi):
-        """The lens of the frames [lo, hi), planned as this table is (``plan_max`` is kept): a one-row lens is its own slice."""
-        if self.n_rows == 1:
-            return self
-        if not 0 <= lo <= hi <= self.n_rows:
-            raise ValueError(f"Lens.slice: [{lo}, {hi}) is not inside the {self.n_rows} rows")
-        if hi == lo:
-            raise ValueError("Lens.slice: an empty slice")
-        return Lens.from_tables(self.table[lo:hi], self.bloom_size[lo:hi], self.sharpen_sigma[lo:hi], self.plan_max)
+    def tables(self):
+        """(table, bloom_size, sharpen_sigma, plan_max): ``Lens.from_tables(*x.tables())`` is x, planned as x is."""
+        return self.table, self.bloom_size, self.sharpen_sigma, self.plan_max
+
+    def _block(self, lo, hi):
+        return Lens.from_tables(self.table[lo:hi], self.bloom_size[lo:hi], self.sharpen_sigma[lo:hi], self.plan_max)  # (plans as this table does)
 
 
 SPEC_KEYS = ("bloom", "bloom_size", "bloom_threshold", "bloom_knee", "bloom_tint", "sharpen", "sharpen_radius", "vignette", "vignette_inner",
@@ -250,24 +198,4 @@ SPEC_KEYS = ("bloom", "bloom_size", "bloom_threshold", "bloom_knee", "bloom_tint
 def parse_spec(text):
     """A static lens as text, ``"bloom=0.8,bloom_size=0.03,sharpen=0.4,vignette=0.3"`` (the --lens flag), -> the keyword arguments of Lens.
     Keys: SPEC_KEYS; a value is a number, bloom_tint three numbers joined by ``:`` (``bloom_tint=1:0.8:0.6``)."""
-    out = {}
-    for part in str(text).split(","):
-        part = part.strip()
-        if not part:
-            continue
-        key, eq, value = part.partition("=")
-        key = key.strip()
-        if not eq or key not in SPEC_KEYS:
-            raise ValueError(f"--lens {text!r}: {part!r} is not key=value with a key of {', '.join(SPEC_KEYS)}")
-        if key in out:
-            raise ValueError(f"--lens {text!r}: {key} is given twice")
-        try:
-            nums = [float(v) for v in value.split(":")]
-        except ValueError:
-            raise ValueError(f"--lens {text!r}: {value.strip()!r} is not a number") from None
-        if len(nums) != (3 if key == "bloom_tint" else 1):
-            raise ValueError(f"--lens {text!r}: {key} takes " + ("three numbers joined by ':'" if key == "bloom_tint" else "one number"))
-        out[key] = nums if key == "bloom_tint" else nums[0]
-    if not out:
-        raise ValueError(f"--lens {text!r} names no parameter")
-    return out
+    return frame_table.parse_spec("--lens", text, {k: (3,) if k == "bloom_tint" else (1,) for k in SPEC_KEYS})

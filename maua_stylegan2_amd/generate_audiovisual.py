@@ -115,6 +115,10 @@ FEEDBACK_FLAGS = (
                         help='static frame feedback (trails), e.g. "gain=0.92,zoom=1.015,rotate=0.3,mode=max,border=mirror" (keys: '
                              + ", ".join(ar.feedback.SPEC_KEYS) + "); one rank only")),
 )
+# The frame effects (audioreactive/frame_table.py), in the order of their flags: (name, class, flags).  ``args.<name>`` and
+# ``args.<name>_spec`` hold an effect (_effect_of), ``ar.<name>.parse_spec`` reads its static flag.  The parser, the keys main() keeps out
+# of generate()'s settings and the per-job "is it set on rank 0" broadcasts are derived from this table: a new effect is a row here
+EFFECTS = (("grade", ar.Grade, GRADE_FLAGS), ("lens", ar.Lens, LENS_FLAGS), ("feedback", ar.Feedback, FEEDBACK_FLAGS))
 
 
 def _install_aliases():
@@ -362,10 +366,10 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
             args = initialize(args)
     # (generate() keeps the reference's parameter list: a colour grade arrives in the namespace — ``args.grade`` set by the plugin's
     # initialize, by its OVERRIDE or by the caller, and the --grade / --grade_lut flags —; resolved on rank 0, after initialize)
-    grade = _grade_of(args) if rank == 0 else None
-    lens = _lens_of(args) if rank == 0 else None  # (``args.lens`` / --lens, the same way)
-    feedback = _feedback_of(args) if rank == 0 else None  # (``args.feedback`` / --feedback, the same way)
-    if grouped and world > 1 and sharding.broadcast_object(feedback is not None if rank == 0 else None):
+    # (``args.lens`` / --lens and ``args.feedback`` / --feedback the same way)
+    effects = dict(grade=_grade_of(args), lens=_lens_of(args), feedback=_feedback_of(args)) if rank == 0 else dict.fromkeys(n for n, _, _ in EFFECTS)
+    on_rank0 = lambda name: sharding.broadcast_object(effects[name] is not None if rank == 0 else None)  # noqa: E731
+    if grouped and world > 1 and on_rank0("feedback"):
         # (every rank raises, before the scatter: a shard's first frame needs its predecessor's state — render.render_frames)
         raise ValueError(render.FEEDBACK_ONE_RANK.format(where=f"this is a {world}-rank job"))
 
@@ -411,10 +415,9 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
             latents, noise, truncation = _scatter_from_rank0(latents, noise, truncation, bends, rewrites, n_frames)
         lo, hi = render.fold_shard_bounds(n_frames, subframes, rank, world)
         shard = (lo, hi, n_frames)
-        if sharding.broadcast_object(grade is not None if rank == 0 else None):  # (a job without a grade adds this one object, nothing else)
-            grade = _broadcast_grade(grade, lo, hi)
-        if sharding.broadcast_object(lens is not None if rank == 0 else None):  # (likewise: a job without a lens adds this one object)
-            lens = _broadcast_lens(lens, lo, hi)
+        for name in ("grade", "lens"):  # (a feedback is not sharded: refused above)
+            if on_rank0(name):  # (a job without this effect adds this one object, nothing else)
+                effects[name] = _broadcast_effect(name, effects[name], lo, hi)
 
     # (reference :191-192.)  The job's one collection — 45-70 ms on this heap.  Full on purpose where it runs: young-generation collections
     # (tried in round 5) leave the preprocessing's cyclic garbage, device tensors among it, alive, and a render that has to LOAD its generator
@@ -445,10 +448,10 @@ def generate(ckpt, audio_file, initialize=None, get_latents=None, get_noise=None
     try:
         # generate() keeps the reference's parameter list: the pipe format, the fold and the delivery size arrive in the namespace
         # (the flags, a plugin's OVERRIDE, a caller's own ``args``) or, for some jobs, through the environment (_tail_options)
-        pix_fmt, fold, resize = _tail_options(args, fold, grade, lens, feedback)
+        pix_fmt, fold, resize = _tail_options(args, fold, **effects)
         written = render.render_frames(generator, latents, noise, offset, duration, batch, out_size, output_file, audio_file, truncation,
                                        bends, rewrites, randomize_noise, ffmpeg_preset, shard, pipe_pix_fmt=pix_fmt, fold=fold, resize=resize,
-                                       grade=grade, lens=lens, feedback=feedback)
+                                       **effects)
     finally:
         if grouped and hasattr(generator, "random_noise"):
             generator.noise_seed = None  # the generator is cached across jobs
@@ -476,106 +479,72 @@ def _resize_of(args):
     return render.FrameResize(size, getattr(args, "deliver_filter", None) or "lanczos", getattr(args, "deliver_fit", None) or "crop")
 
 
-def _grade_of(args):
-    """The colour grade a namespace asks for, or None.  ``args.grade``: an ar.Grade, a callable ``grade(args) -> ar.Grade`` (evaluated here:
-    after initialize, so it may use what initialize computed), or a --grade string; ``grade_spec`` / ``grade_lut`` / ``grade_lut_mix``: the
-    CLI flags.  Without a plugin grade the flags build a one-row grade; with one, --grade_lut is attached to it when it has no LUT of its
-    own, and anything that would need two grades composed (a --grade string next to a plugin grade, two LUTs) is refused."""
-    grade = getattr(args, "grade", None)
-    spec, lut, mix = getattr(args, "grade_spec", None), getattr(args, "grade_lut", None), getattr(args, "grade_lut_mix", None)
-    mix = 1.0 if mix is None else mix
-    if isinstance(grade, str):
-        grade = ar.Grade(**ar.grade.parse_spec(grade))
-    elif grade is not None and not isinstance(grade, ar.Grade):
-        if not callable(grade):
-            raise TypeError(f"args.grade must be an ar.Grade or a callable grade(args) -> ar.Grade, got {type(grade).__name__}")
-        grade = grade(args)
-        if grade is not None and not isinstance(grade, ar.Grade):
-            raise TypeError(f"args.grade(args) must return an ar.Grade, got {type(grade).__name__}")
-    if grade is None:
-        if not spec and not lut:
-            return None
-        return ar.Grade(**(ar.grade.parse_spec(spec) if spec else {}), lut=lut, lut_mix=mix)
+def _effect_of(args, name, **flag_kwargs):
+    """The frame effect ``name`` (EFFECTS) a namespace asks for, or None.  ``args.<name>``: an instance of the effect's class, a callable
+    ``<name>(args)`` that returns one or None (evaluated here: after initialize, so it may use what initialize computed), or a string
+    as the flag takes it; ``args.<name>_spec``: the CLI flag, which builds a one-row effect (with ``flag_kwargs``: what further flags add
+    to it).  The flag next to an effect of the namespace's own is refused: two effects do not compose into one row."""
+    cls = next(c for n, c, _ in EFFECTS if n == name)
+    kind, parse = f"ar.{cls.__name__}", getattr(ar, name).parse_spec
+    effect, spec = getattr(args, name, None), getattr(args, f"{name}_spec", None)
+    if isinstance(effect, str):
+        effect = cls(**parse(effect))
+    elif effect is not None and not isinstance(effect, cls):
+        if not callable(effect):
+            raise TypeError(f"args.{name} must be an {kind} or a callable {name}(args) -> {kind}, got {type(effect).__name__}")
+        effect = effect(args)
+        if effect is not None and not isinstance(effect, cls):
+            raise TypeError(f"args.{name}(args) must return an {kind}, got {type(effect).__name__}")
+    if effect is None:
+        return cls(**parse(spec), **flag_kwargs) if spec else None
     if spec:
-        raise ValueError("--grade cannot be combined with the plugin's grade (two grades do not compose into one row): set it in the plugin")
+        raise ValueError(f"--{name} cannot be combined with the plugin's {name} (two of them do not compose into one row): set it in the plugin")
+    return effect
+
+
+def _grade_of(args):
+    """The colour grade a namespace asks for, or None (_effect_of), and on top of it ``grade_lut`` / ``grade_lut_mix``, the LUT flags: they
+    alone build a one-row grade, and --grade_lut is attached to a grade that has no LUT of its own; two LUTs are refused."""
+    lut, mix = getattr(args, "grade_lut", None), getattr(args, "grade_lut_mix", None)
+    mix = 1.0 if mix is None else mix
+    grade = _effect_of(args, "grade", lut_mix=mix)
     if lut:
-        if grade.lut is not None:
+        if grade is not None and grade.lut is not None:  # (the plugin's: a grade built from --grade has none yet)
             raise ValueError("--grade_lut cannot be combined with a plugin grade that has a LUT of its own")
-        grade = grade.with_lut(lut, mix)
+        grade = (ar.Grade(lut_mix=mix) if grade is None else grade).with_lut(lut, mix)
     return grade
 
 
-def _broadcast_grade(grade, lo, hi):
-    """One process per GPU: rank 0's grade reaches every rank — the row table is broadcast and cut to this rank's frames [lo, hi) (a one-row
-    table is kept as it is), the LUT is broadcast whole."""
-    rank, _ = sharding.rank_world()
-    table, lut = sharding.broadcast_object((grade.table, grade.lut) if rank == 0 else None)
-    if table.shape[0] != 1:
-        if hi > table.shape[0]:
-            raise RuntimeError(f"the grade's table has {table.shape[0]} rows, this rank renders the frames {lo} .. {hi}")
-        if hi == lo:
-            return ar.Grade.from_table(table[:1], lut)  # (a rank without frames: never applied)
-        table = table[lo:hi]
-    return ar.Grade.from_table(table, lut)
-
-
 def _lens_of(args):
-    """The lens a namespace asks for, or None.  ``args.lens``: an ar.Lens, a callable ``lens(args) -> ar.Lens`` (evaluated here: after
-    initialize), or a --lens string; ``lens_spec``: the CLI flag, which builds a one-row lens.  A --lens string next to a plugin's lens is
-    refused: two lenses do not compose into one row."""
-    lens = getattr(args, "lens", None)
-    spec = getattr(args, "lens_spec", None)
-    if isinstance(lens, str):
-        lens = ar.Lens(**ar.lens.parse_spec(lens))
-    elif lens is not None and not isinstance(lens, ar.Lens):
-        if not callable(lens):
-            raise TypeError(f"args.lens must be an ar.Lens or a callable lens(args) -> ar.Lens, got {type(lens).__name__}")
-        lens = lens(args)
-        if lens is not None and not isinstance(lens, ar.Lens):
-            raise TypeError(f"args.lens(args) must return an ar.Lens, got {type(lens).__name__}")
-    if lens is None:
-        return ar.Lens(**ar.lens.parse_spec(spec)) if spec else None
-    if spec:
-        raise ValueError("--lens cannot be combined with the plugin's lens (two lenses do not compose into one row): set it in the plugin")
-    return lens
+    """The lens a namespace asks for, or None: ``args.lens`` / --lens (_effect_of)."""
+    return _effect_of(args, "lens")
 
 
 def _feedback_of(args):
-    """The frame feedback a namespace asks for, or None.  ``args.feedback``: an ar.Feedback, a callable ``feedback(args) -> ar.Feedback``
-    (evaluated here: after initialize), or a --feedback string; ``feedback_spec``: the CLI flag, which builds a one-row feedback.  A
-    --feedback string next to a plugin's feedback is refused: two recurrences do not compose into one row."""
-    feedback = getattr(args, "feedback", None)
-    spec = getattr(args, "feedback_spec", None)
-    if isinstance(feedback, str):
-        feedback = ar.Feedback(**ar.feedback.parse_spec(feedback))
-    elif feedback is not None and not isinstance(feedback, ar.Feedback):
-        if not callable(feedback):
-            raise TypeError(f"args.feedback must be an ar.Feedback or a callable feedback(args) -> ar.Feedback, got {type(feedback).__name__}")
-        feedback = feedback(args)
-        if feedback is not None and not isinstance(feedback, ar.Feedback):
-            raise TypeError(f"args.feedback(args) must return an ar.Feedback, got {type(feedback).__name__}")
-    if feedback is None:
-        return ar.Feedback(**ar.feedback.parse_spec(spec)) if spec else None
-    if spec:
-        raise ValueError("--feedback cannot be combined with the plugin's feedback (two recurrences do not compose into one row): set it "
-                         "in the plugin")
-    return feedback
+    """The frame feedback a namespace asks for, or None: ``args.feedback`` / --feedback (_effect_of)."""
+    return _effect_of(args, "feedback")
+
+
+def _broadcast_effect(name, effect, lo, hi):
+    """One process per GPU: rank 0's grade or lens reaches every rank — its ``tables()`` are broadcast whole (with them what belongs to the
+    whole table: the LUT, the lens's ``plan_max``, so that every rank derives the reduction, the radii and the taps of a frame that the
+    one-rank job derives), the effect is rebuilt and cut to this rank's frames [lo, hi); a one-row table is kept as it is."""
+    rank, _ = sharding.rank_world()
+    cls = next(c for n, c, _ in EFFECTS if n == name)
+    whole = cls.from_tables(*sharding.broadcast_object(effect.tables() if rank == 0 else None))
+    if whole.n_rows == 1:
+        return whole
+    if hi > whole.n_rows:
+        raise RuntimeError(f"the {name}'s table has {whole.n_rows} rows, this rank renders the frames {lo} .. {hi}")
+    return whole.slice(lo, hi) if hi > lo else whole.slice(0, 1)  # (a rank without frames: one row, never applied)
+
+
+def _broadcast_grade(grade, lo, hi):
+    return _broadcast_effect("grade", grade, lo, hi)
 
 
 def _broadcast_lens(lens, lo, hi):
-    """One process per GPU: rank 0's lens reaches every rank — the row table and the per-row sizes are broadcast and cut to this rank's
-    frames [lo, hi) (a one-row table is kept as it is), together with the whole table's ``plan_max``: every rank derives the reduction,
-    the radii and the taps of a frame that the one-rank job derives, also when bloom_size or sharpen_radius is modulated.  (A helper of
-    its own, like _broadcast_grade.)"""
-    rank, _ = sharding.rank_world()
-    table, size, sigma, plan_max = sharding.broadcast_object((lens.table, lens.bloom_size, lens.sharpen_sigma, lens.plan_max) if rank == 0 else None)
-    if table.shape[0] != 1:
-        if hi > table.shape[0]:
-            raise RuntimeError(f"the lens's table has {table.shape[0]} rows, this rank renders the frames {lo} .. {hi}")
-        if hi == lo:
-            return ar.Lens.from_tables(table[:1], size[:1], sigma[:1], plan_max)  # (a rank without frames: never applied)
-        table, size, sigma = table[lo:hi], size[lo:hi], sigma[lo:hi]
-    return ar.Lens.from_tables(table, size, sigma, plan_max)
+    return _broadcast_effect("lens", lens, lo, hi)
 
 
 def _pipe_format_of(args):
@@ -619,7 +588,7 @@ def load_plugin(audioreactive_file):
 
 def build_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + GRADE_FLAGS + LENS_FLAGS + FEEDBACK_FLAGS:
+    for flag, kwargs in CLI_FLAGS + DELIVERY_FLAGS + sum((flags for _, _, flags in EFFECTS), ()):
         parser.add_argument(flag, **kwargs)
     return parser
 
@@ -649,11 +618,13 @@ def main(argv=None):
         settings[key] = value
         setattr(args, key, value)
     ckpt, audio_file = settings.pop("ckpt", None), settings.pop("audio_file", None)
-    settings.pop("pipe_pix_fmt", None)  # (stays in ``args``, where generate() reads it: not one of its parameters)
-    settings.pop("mjpeg_quality", None)
-    for key in ("subframes", "shutter", "shutter_light", "deliver_size", "deliver_filter", "deliver_fit", "grade", "grade_spec", "grade_lut",
-                "grade_lut_mix", "lens", "lens_spec", "feedback", "feedback_spec"):
+    # (what stays in ``args``, where generate() reads it, and is not one of its parameters: the pipe format, the fold, the delivery size
+    # and, per effect, ``args.<name>`` and the destinations of its flags)
+    for key in ("pipe_pix_fmt", "mjpeg_quality", "subframes", "shutter", "shutter_light") + tuple(f.lstrip("-") for f, _ in DELIVERY_FLAGS):
         settings.pop(key, None)
+    for name, _, flags in EFFECTS:
+        for key in (name,) + tuple(kwargs.get("dest", flag.lstrip("-")) for flag, kwargs in flags):
+            settings.pop(key, None)
     try:
         generate(ckpt=ckpt, audio_file=audio_file, **callbacks, **settings, args=args)
     finally:

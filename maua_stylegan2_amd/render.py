@@ -65,6 +65,9 @@ import numpy as np
 import torch as th
 
 from . import _lib, avi, sharding
+from .audioreactive.feedback import Feedback
+from .audioreactive.grade import Grade
+from .audioreactive.lens import Lens
 from .audioreactive.noise import NoiseSynth
 
 th.set_grad_enabled(False)
@@ -544,21 +547,57 @@ def _batch_rows(table, per_frame, batch_size):
     return table.expand(max(batch_size, 1), table.shape[1]).contiguous()
 
 
-class LensOperands:
-    """A render's lens on one device (_lens_operands): the Lens, whether its table holds a row per rendered frame, and — per frame size:
-    the plan rule needs the height — the device tables (_batch_rows)."""
+class _TableOperands:
+    """A render's grade, lens or feedback (``KIND``: its audioreactive class) on one device: the effect — under its own name, ``.grade`` /
+    ``.lens`` / ``.feedback`` —, whether its table holds a row per rendered frame (_per_frame_table: a table that has neither one row nor
+    ``n_rendered`` is refused), the tables per frame size (``sized``: a subclass builds them in ``_tables``) and the rows of a batch
+    (``window``)."""
 
-    def __init__(self, lens, per_frame, batch_size, dev):
-        self.lens, self.per_frame, self.batch_size, self.dev = lens, per_frame, max(batch_size, 1), dev
+    KIND = None
+
+    def __init__(self, effect, n_rendered, batch_size, dev):
+        self.name = self.KIND.__name__.lower()
+        if not isinstance(effect, self.KIND):
+            raise TypeError(f"{self.name} must be an audioreactive {self.KIND.__name__}, got {type(effect).__name__}")
+        setattr(self, self.name, effect)
+        self.per_frame, self.batch_size, self.dev = _per_frame_table(self.name, effect.n_rows, n_rendered), batch_size, dev
         self._sized = {}
 
     def sized(self, h, w):
-        """(rows, d, bloom radius, bloom taps, sharpen radius, sharpen taps) for frames of h x w."""
+        """The tables for frames of h x w (``_tables``), built once per size."""
         if (h, w) not in self._sized:
-            rows, d, rb, bt, rs, st = self.lens.operands(self.dev, h, w)
-            rows, bt, st = (_batch_rows(t, self.per_frame, self.batch_size) for t in (rows, bt, st))
-            self._sized[(h, w)] = (rows, d, rb, bt, rs, st)
+            self._sized[(h, w)] = self._tables(h, w)
         return self._sized[(h, w)]
+
+    def window(self, table, first, count):
+        """The rows of the batch that starts at rendered frame ``first``: [first, first + count) of a per-frame table, else the first
+        ``count`` of the one row repeated to a batch (_batch_rows)."""
+        lo = first if self.per_frame else 0
+        if lo < 0 or lo + count > table.shape[0]:
+            raise RuntimeError(f"the frames {lo} .. {lo + count} are not inside the {table.shape[0]} rows of the {self.name}")
+        return table[lo: lo + count]
+
+
+class GradeOperands(_TableOperands):
+    """A render's grade on one device: ``rows`` (the device row table, _batch_rows) and ``lut`` (the padded LUT, or None)."""
+
+    KIND = Grade
+
+    def __init__(self, grade, n_rendered, batch_size, dev):
+        super().__init__(grade, n_rendered, batch_size, dev)
+        self.rows, self.lut = _batch_rows(grade.rows(dev), self.per_frame, batch_size), grade.lut_table(dev)
+
+
+class LensOperands(_TableOperands):
+    """A render's lens on one device; per frame size — the plan rule needs the height — the device tables (_batch_rows)."""
+
+    KIND = Lens
+
+    def _tables(self, h, w):
+        """(rows, d, bloom radius, bloom taps, sharpen radius, sharpen taps) for frames of h x w."""
+        rows, d, rb, bt, rs, st = self.lens.operands(self.dev, h, w)
+        rows, bt, st = (_batch_rows(t, self.per_frame, self.batch_size) for t in (rows, bt, st))
+        return rows, d, rb, bt, rs, st
 
 
 def lens_frames(images, lens_ops, first, count, scratch):
@@ -578,10 +617,7 @@ def lens_frames(images, lens_ops, first, count, scratch):
         return images
     dev = images.device
     rows, d, rb, btaps, rs, staps = lens_ops.sized(h, w)
-    lo = first if lens_ops.per_frame else 0
-    if lo < 0 or lo + b > rows.shape[0]:
-        raise RuntimeError(f"lens_frames: the frames {lo} .. {lo + b} are not inside the {rows.shape[0]} rows of the lens")
-    rows, btaps, staps = rows[lo: lo + b], btaps[lo: lo + b], staps[lo: lo + b]
+    rows, btaps, staps = (lens_ops.window(t, first, b) for t in (rows, btaps, staps))
     lib = _lib.load()
     st = _lib.stream_ptr(dev)
     bloom = soft = None
@@ -603,25 +639,22 @@ def lens_frames(images, lens_ops, first, count, scratch):
     return images
 
 
-class FeedbackOperands:
-    """A render's feedback on one device (_feedback_operands): the Feedback, whether its table holds a row per rendered frame, and what
-    outlives a batch — the persistent ``state`` [3, H, W] (the last output frame; allocated by the render before the lanes start, NOT a lane buffer:
-    a lane's image is overwritten by that lane's next replay while the following batch, on another lane, still has to read it), whether it
-    holds a frame yet, and the event recorded behind the last batch's feedback (feedback_frames chains the lanes' streams on it)."""
+class FeedbackOperands(_TableOperands):
+    """A render's feedback on one device, and what outlives a batch — the persistent ``state`` [3, H, W] (the last output frame; allocated
+    by the render before the lanes start, NOT a lane buffer: a lane's image is overwritten by that lane's next replay while the following
+    batch, on another lane, still has to read it), whether it holds a frame yet, and the event recorded behind the last batch's feedback
+    (feedback_frames chains the lanes' streams on it)."""
 
-    def __init__(self, feedback, per_frame, batch_size, dev):
-        self.feedback, self.per_frame, self.batch_size, self.dev = feedback, per_frame, max(batch_size, 1), dev
-        self.state = None
-        self.state_valid = False
-        self.done = None
-        self._sized = {}
+    KIND = Feedback
 
-    def sized(self, h, w):
+    def __init__(self, feedback, n_rendered, batch_size, dev):
+        super().__init__(feedback, n_rendered, batch_size, dev)
+        self.state, self.state_valid, self.done = None, False, None
+
+    def _tables(self, h, w):
         """(rows — float32 [n, 16] on the host, a one-row table repeated to a batch —, mode, border) for frames of h x w."""
-        if (h, w) not in self._sized:
-            rows, mode, border = self.feedback.operands(self.dev, h, w)
-            self._sized[(h, w)] = (np.ascontiguousarray(_batch_rows(rows, self.per_frame, self.batch_size), np.float32), mode, border)
-        return self._sized[(h, w)]
+        rows, mode, border = self.feedback.operands(h, w)
+        return np.ascontiguousarray(_batch_rows(rows, self.per_frame, self.batch_size), np.float32), mode, border
 
     def allocate(self, h, w):
         """The state buffer for frames of h x w, on the current stream (the render's own, which the lanes' streams wait for when they
@@ -630,6 +663,11 @@ class FeedbackOperands:
         if self.state is None or tuple(self.state.shape) != (3, h, w):
             self.state, self.state_valid = th.empty((3, h, w), dtype=th.float32, device=self.dev), False
         return self.state
+
+
+# (the names the lens and feedback operands were built by before they were classes: tests and tools call them, with these arguments.
+# The tail names the classes themselves, looked up when it is loaded)
+_lens_operands, _feedback_operands = LensOperands, FeedbackOperands
 
 
 def feedback_frames(images, ops, first, count, scratch):
@@ -656,10 +694,7 @@ def feedback_frames(images, ops, first, count, scratch):
         return images
     dev = images.device
     rows, mode, border = ops.sized(h, w)
-    lo = first if ops.per_frame else 0
-    if lo < 0 or lo + b > rows.shape[0]:
-        raise RuntimeError(f"feedback_frames: the frames {lo} .. {lo + b} are not inside the {rows.shape[0]} rows of the feedback")
-    rows = rows[lo: lo + b]
+    rows = ops.window(rows, first, b)
     ops.allocate(h, w)  # (the render has done so on its own stream before the lanes started)
     lib = _lib.load()
     with th.cuda.device(dev):
@@ -1411,29 +1446,6 @@ FEEDBACK_ONE_RANK = ("a frame feedback is a recurrence over the frames: a shard'
                      "which only a render that starts at frame 0 on its own has ({where}).  Render a feedback on one rank (one process, one GPU)")
 
 
-def _grade_operands(grade, n_rendered, batch_size, dev):
-    """(rows, lut, per_frame) of a render's grade on ``dev``: the device row table (_batch_rows) and the padded LUT.  Refuses a table that
-    has neither one row nor ``n_rendered``."""
-    if not (hasattr(grade, "rows") and hasattr(grade, "lut_table") and hasattr(grade, "n_rows")):
-        raise TypeError(f"grade must be an audioreactive Grade, got {type(grade).__name__}")
-    per_frame = _per_frame_table("grade", grade.n_rows, n_rendered)
-    return _batch_rows(grade.rows(dev), per_frame, batch_size), grade.lut_table(dev), per_frame
-
-
-def _lens_operands(lens, n_rendered, batch_size, dev):
-    """The LensOperands of a render's lens on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
-    if not (hasattr(lens, "operands") and hasattr(lens, "n_rows") and hasattr(lens, "has_bloom")):
-        raise TypeError(f"lens must be an audioreactive Lens, got {type(lens).__name__}")
-    return LensOperands(lens, _per_frame_table("lens", lens.n_rows, n_rendered), batch_size, dev)
-
-
-def _feedback_operands(feedback, n_rendered, batch_size, dev):
-    """The FeedbackOperands of a render's feedback on ``dev``.  Refuses a table that has neither one row nor ``n_rendered``."""
-    if not (hasattr(feedback, "operands") and hasattr(feedback, "n_rows") and hasattr(feedback, "border")):
-        raise TypeError(f"feedback must be an audioreactive Feedback, got {type(feedback).__name__}")
-    return FeedbackOperands(feedback, _per_frame_table("feedback", feedback.n_rows, n_rendered), batch_size, dev)
-
-
 def fold_shard_bounds(n_frames, subframes, rank, world):
     """[lo, hi) of a rank's block in RENDERED frames when every delivered frame is folded from ``subframes`` of them: the job is sharded in
     units of delivered frames (sharding.shard_bounds of n_frames / N), so that no group straddles two ranks."""
@@ -1500,7 +1512,7 @@ class _FrameTail:
         self.fold, self.resize, self.grade, self.lens, self.feedback = fold, resize, grade, lens, feedback
         # the deep formats, the grade, the lens and the feedback work on the fp32 image: the lanes then run without their quantiser
         self.frames = "f32" if self.deep or grade is not None or lens is not None or feedback is not None else "u8"
-        self.grade_rows = self.lens_ops = self.feedback_ops = None
+        self.grade_ops = self.lens_ops = self.feedback_ops = None
         self.scratch = {}
 
     def load(self, n_rendered, first_frame, world):
@@ -1510,12 +1522,12 @@ class _FrameTail:
             raise ValueError(FEEDBACK_ONE_RANK.format(where=f"this shard starts at frame {first_frame} of a {world}-rank job"))
         self.dev = dev = device_of(self.generator)
         if self.grade is not None:
-            self.grade_rows, self.grade_lut, self.grade_per_frame = _grade_operands(self.grade, n_rendered, self.batch_size, dev)
+            self.grade_ops = GradeOperands(self.grade, n_rendered, self.batch_size, dev)
         if self.lens is not None:
-            self.lens_ops = _lens_operands(self.lens, n_rendered, self.batch_size, dev)
+            self.lens_ops = LensOperands(self.lens, n_rendered, self.batch_size, dev)
             self.lens_ops.sized(*_generated_hw(self.generator, self.out_size))  # (a bloom too wide for this frame height is refused here)
         if self.feedback is not None:
-            self.feedback_ops = _feedback_operands(self.feedback, n_rendered, self.batch_size, dev)
+            self.feedback_ops = FeedbackOperands(self.feedback, n_rendered, self.batch_size, dev)
             if not self.feedback.is_identity:
                 self.feedback_ops.sized(*_generated_hw(self.generator, self.out_size))
                 self.feedback_ops.allocate(*_generated_hw(self.generator, self.out_size))  # (on this stream, before the lanes start)
@@ -1530,9 +1542,9 @@ class _FrameTail:
             images = feedback_frames(images.contiguous(), self.feedback_ops, first, count, scratch)
         if self.lens_ops is not None:  # (in front of the grade: the glow is graded with the picture it belongs to)
             images = lens_frames(images.contiguous(), self.lens_ops, first, count, scratch)
-        if self.grade_rows is not None:
-            rows = self.grade_rows[first: first + count] if self.grade_per_frame else self.grade_rows[:count]
-            images = grade_frames(images.contiguous(), rows, self.grade_lut, scratch, out="f32" if self.deep else "u8")
+        if self.grade_ops is not None:
+            rows = self.grade_ops.window(self.grade_ops.rows, first, count)
+            images = grade_frames(images.contiguous(), rows, self.grade_ops.lut, scratch, out="f32" if self.deep else "u8")
         elif self.frames == "f32" and not self.deep:  # (the quantiser every 8-bit render ends its forward with)
             _, _, h, w = images.shape
             images = frames_to_uint8(images, out=_scratch(scratch, ("lens-u8", images.data_ptr(), count, h, w), (count, h, w, 3), th.uint8, images.device))

@@ -197,9 +197,9 @@ def test_feedback_builds_rows_matrices_and_still_flags(built_lib):
     fb = ar.Feedback(gain=gain, dry=[1, 0.5, 1, 1, 1], zoom=zoom, rotate=rot, translate=tr, tint=(1, 0.5, 0.25), limit=2.0, mode="max", border="wrap")
     assert fb.n_rows == len(fb) == n and not fb.is_identity and list(fb.neutral) == [False, False, True, False, False]
     assert "5 rows" in repr(fb) and "max" in repr(fb) and "wrap" in repr(fb)
-    rows, mode, border = fb.operands("cpu", h, w)
+    rows, mode, border = fb.operands(h, w)
     assert rows.dtype == np.float32 and rows.shape == (n, 16) and rows.flags.c_contiguous and (mode, border) == (1, 3)
-    assert fb.operands("cpu", h, w)[0] is rows and fb.rows(h, w) is rows
+    assert fb.operands(h, w)[0] is rows and fb.rows(h, w) is rows
     for i in range(n):
         want = fr.inverse_matrix(zoom[i], rot[i], tr[i], h, w)
         assert np.array_equal(rows[i, :6], np.asarray(want, F64).astype(F32)), i
@@ -303,9 +303,31 @@ def test_the_feedback_flag_parses_and_resolves(built_lib):
     for bad in (3, lambda a: 3):
         with pytest.raises(TypeError, match="ar.Feedback"):
             gav._feedback_of(argparse.Namespace(feedback=bad))
-    # main() keeps the new keys out of generate()'s settings
-    src = inspect.getsource(gav.main)
-    assert '"feedback", "feedback_spec"' in src
+
+
+def test_main_keeps_the_effect_keys_out_of_generates_settings(monkeypatch, tmp_path, built_lib):
+    """main() hands generate() its own parameters as keywords; the fold, the delivery and every effect's keys stay in ``args``."""
+    from maua_stylegan2_amd import generate_audiovisual as gav
+
+    seen, parameters = [], set(inspect.signature(gav.generate).parameters)
+    monkeypatch.setattr(gav, "generate", lambda **kw: seen.append(kw))
+    monkeypatch.setattr(gav, "load_plugin", lambda path: ({name: None for name in gav.CALLBACK_NAMES}, {"feedback": "gain=0.5", "lens": None}))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    gav.main(["--ckpt", "c.pt", "--audio_file", "a.wav", "--output_dir", str(tmp_path), "--grade", "hue=3", "--grade_lut", "k.cube", "--lens", "bloom=1",
+              "--feedback", "gain=0.9", "--subframes", "2", "--deliver_size", "80x40", "--pipe_pix_fmt", "yuv420p"])
+    (kw,) = seen
+    kept = ("grade", "grade_spec", "grade_lut", "grade_lut_mix", "lens", "lens_spec", "feedback", "feedback_spec", "subframes", "shutter",
+            "shutter_light", "deliver_size", "deliver_filter", "deliver_fit", "pipe_pix_fmt", "mjpeg_quality")
+    assert not set(kept) & set(kw) and set(kw) <= parameters
+    args = kw["args"]
+    assert (kw["ckpt"], kw["audio_file"], kw["batch"]) == ("c.pt", "a.wav", 8)
+    assert all(hasattr(args, key) for key in kept if key != "grade")  # (``args.grade`` exists only where a plugin sets it)
+    assert (args.grade_spec, args.grade_lut, args.grade_lut_mix, args.lens_spec, args.feedback_spec) == ("hue=3", "k.cube", 1.0, "bloom=1", "gain=0.9")
+    assert args.feedback == "gain=0.5" and args.lens is None and (args.subframes, args.deliver_size) == (2, "80x40")
+    # ... and a plugin's OVERRIDE that sets ``grade`` reaches ``args``, not generate()
+    monkeypatch.setattr(gav, "load_plugin", lambda path: ({name: None for name in gav.CALLBACK_NAMES}, {"grade": "hue=3"}))
+    gav.main(["--ckpt", "c.pt", "--audio_file", "a.wav", "--output_dir", str(tmp_path)])
+    assert "grade" not in seen[-1] and seen[-1]["args"].grade == "hue=3"
 
 
 def test_surface_and_dispatch_without_a_feedback(monkeypatch, built_lib):

@@ -362,10 +362,11 @@ def test_render_graded_refuses_a_table_of_the_wrong_length_without_a_device():
     from maua_stylegan2_amd import render
 
     with pytest.raises(ValueError, match="5 rows.*one per rendered frame \\(7\\)"):
-        render._grade_operands(ar.Grade(exposure=np.zeros(5)), 7, 2, torch.device("cpu"))
+        render.GradeOperands(ar.Grade(exposure=np.zeros(5)), 7, 2, torch.device("cpu"))
     with pytest.raises(TypeError, match="Grade"):
-        render._grade_operands("exposure=1", 7, 2, torch.device("cpu"))
-    rows, lut, per_frame = render._grade_operands(ar.Grade(exposure=1), 7, 4, torch.device("cpu"))
+        render.GradeOperands("exposure=1", 7, 2, torch.device("cpu"))
+    ops = render.GradeOperands(ar.Grade(exposure=1), 7, 4, torch.device("cpu"))
+    rows, lut, per_frame = ops.rows, ops.lut, ops.per_frame
     assert tuple(rows.shape) == (4, 24) and rows.is_contiguous() and lut is None and not per_frame and bool((rows[:, 0] == 2).all())
-    rows, _, per_frame = render._grade_operands(ar.Grade(exposure=np.zeros(7)), 7, 4, torch.device("cpu"))
-    assert tuple(rows.shape) == (7, 24) and per_frame
+    ops = render.GradeOperands(ar.Grade(exposure=np.zeros(7)), 7, 4, torch.device("cpu"))
+    assert tuple(ops.rows.shape) == (7, 24) and ops.per_frame

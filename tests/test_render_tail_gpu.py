@@ -38,15 +38,18 @@ def job(gpu):
     return dict(g=g, lat=lat, noise=noise, feedback=feedback, lens=lens, grade=grade, resize=render.FrameResize(DELIVER, "bicubic", "pad"))
 
 
-def _by_hand(job, deliver):
-    """The stages called one after the other on every fp32 batch of the lanes; ``deliver(graded batch maker, scratch)`` ends the chain."""
+def _by_hand(job, deliver, effects=None):
+    """The stages called one after the other on every fp32 batch of the lanes; ``deliver(graded batch maker, scratch)`` ends the chain.
+    ``effects``: per-frame feedback, lens and grade in place of the job's."""
     from maua_stylegan2_amd import render
 
     dev = render.device_of(job["g"])
-    feedback_ops = render._feedback_operands(job["feedback"], N_FRAMES, BATCH, dev)
-    lens_ops = render._lens_operands(job["lens"], N_FRAMES, BATCH, dev)
-    rows, lut, per_frame = render._grade_operands(job["grade"], N_FRAMES, BATCH, dev)
-    assert per_frame and feedback_ops.per_frame and lens_ops.per_frame
+    effects = effects or job
+    feedback_ops = render._feedback_operands(effects["feedback"], N_FRAMES, BATCH, dev)
+    lens_ops = render._lens_operands(effects["lens"], N_FRAMES, BATCH, dev)
+    grade_ops = render.GradeOperands(effects["grade"], N_FRAMES, BATCH, dev)
+    rows, lut = grade_ops.rows, grade_ops.lut
+    assert grade_ops.per_frame and feedback_ops.per_frame and lens_ops.per_frame and rows.shape[0] == N_FRAMES
     scratch, out = {}, []
     for first, images in render.synthesize(job["g"], job["lat"], job["noise"], BATCH, frames="f32"):
         images, count = images.clone(), images.shape[0]
@@ -57,13 +60,14 @@ def _by_hand(job, deliver):
     return np.concatenate(out)
 
 
-def _render(job, out, **kw):
+def _render(job, out, effects=None, **kw):
     from maua_stylegan2_amd import render
 
+    effects = effects or job
     with pytest.MonkeyPatch.context() as mp:
         _stand_ins(mp)
         return render.render_fed(job["g"], job["lat"], job["noise"], 0, N_FRAMES / 30, BATCH, SIZE, out, *TAIL, resize=job["resize"],
-                                 grade=job["grade"], lens=job["lens"], feedback=job["feedback"], **kw)
+                                 grade=effects["grade"], lens=effects["lens"], feedback=effects["feedback"], **kw)
 
 
 def test_all_five_options_in_one_rgb24_render(gpu, job, tmp_path):
@@ -89,4 +93,28 @@ def test_feedback_lens_grade_and_delivery_size_in_one_yuv420p10le_render(gpu, jo
     assert _render(job, out, pipe_pix_fmt=fmt) == N_FRAMES
     got = np.fromfile(out + "." + fmt, dtype=np.uint8).reshape(N_FRAMES, -1)
     assert want.shape == got.shape == (N_FRAMES, render.deep_frame_bytes(fmt, *DELIVER)) and np.array_equal(got, want), int((got != want).sum())
+    assert len({f.tobytes() for f in got}) == len(got)
+
+
+def test_one_row_tables_are_row_0_repeated_to_every_batch(gpu, job, tmp_path):
+    """The three effects as ONE-ROW tables (row 0 of the job's per-frame tables): the render repeats the row to a batch and hands every
+    batch — the second starts at ``first = 4`` — its first ``count`` rows.  Compared with the chain by hand on PER-FRAME tables that hold
+    row 0 eight times, which picks its rows the other way: [first, first + count)."""
+    import maua_stylegan2_amd.audioreactive as ar
+    from maua_stylegan2_amd import render
+
+    def rebuilt(effect, pick):  # (the effect's per-row tables through ``pick``; what belongs to the whole table — mode, border — kept)
+        tables = effect.tables()
+        return type(effect).from_tables(*(pick(t) if isinstance(t, np.ndarray) and t.shape[:1] == (N_FRAMES,) else t for t in tables[:3]))
+
+    names = ("feedback", "lens", "grade")
+    one = {k: rebuilt(job[k], lambda t: t[:1]) for k in names}
+    repeated = {k: rebuilt(job[k], lambda t: np.repeat(t[:1], N_FRAMES, axis=0)) for k in names}
+    assert all(one[k].n_rows == 1 and repeated[k].n_rows == N_FRAMES and not one[k].is_identity for k in names)
+    assert isinstance(one["lens"], ar.Lens) and one["lens"].plan_max == repeated["lens"].plan_max
+    want = _by_hand(job, lambda graded, scratch: render.resize_frames(graded("u8"), job["resize"], scratch), repeated)
+    out = str(tmp_path / "one.mp4")
+    assert _render(job, out, one) == N_FRAMES
+    got = np.fromfile(out + ".rgb24", dtype=np.uint8).reshape(N_FRAMES, DELIVER[1], DELIVER[0], 3)
+    assert want.shape == got.shape and np.array_equal(got, want), int((got != want).sum())
     assert len({f.tobytes() for f in got}) == len(got)

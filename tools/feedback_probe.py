@@ -50,7 +50,7 @@ def step_kernels(args):
     result, counter = {}, {"k": 0}
 
     def measure(name, moved, feedback, note=""):
-        rows, mode, border = feedback.operands(dev, size, size)
+        rows, mode, border = feedback.operands(size, size)
         rows = np.ascontiguousarray(np.broadcast_to(rows, (batch, 16)) if rows.shape[0] == 1 else rows)
         plan = (ctypes.c_int * 8)()
         _lib.check(lib.maua_feedback_plan(batch, size, size, rows.ctypes.data, 16, imgs[0].data_ptr(), ctypes.addressof(plan)), "maua_feedback_plan")
