@@ -1024,7 +1024,14 @@ class Generator(nn.Module):
 
         def noise_for(i, h, w):
             if src is not None:
-                return None  # slot i of the frame source
+                # slot i of the frame source.  It is bound to maps of the shape of the generator's noise buffer (FrameSource.bind) and no
+                # kernel looks at that shape again: a bend that reshapes the maps of a generator built for another output size would read
+                # the slots, and write the frames, out of bounds where the eager path raises (_checked_noise)
+                hw = tuple(getattr(self.noises, f"noise_{i}").shape[-2:])
+                if hw != (int(h), int(w)):
+                    raise RuntimeError(f"noise slot {i} holds {hw[0]} x {hw[1]} maps (the generator's noise buffers), the layer's map is "
+                                       f"{int(h)} x {int(w)}: build the generator with the output_size its bends produce")
+                return None
             nz = noise[i]
             if nz is None:  # randomize_noise=True: fresh N(0,1) per call (:262-265)
                 nz = bufs(f"rand_noise_{i}", (batch, 1, h, w)).normal_()
@@ -1071,6 +1078,8 @@ class Generator(nn.Module):
             ``image``: offered to the layer's own launches, else a pass of its own.  Returns the layer's map."""
             nonlocal image, posted, u8_written
             h, w = (4, 4) if x is None else x.shape[2:]
+            if is_last and frames_u8 is not None and tuple(frames_u8.shape) != (batch, h, w, 3):
+                raise RuntimeError(f"frames buffer {tuple(frames_u8.shape)} for frames [{batch}, {h}, {w}, 3]")
             rgb_buf = bufs(rgb_name, (batch, 3, h, w))
             wants_rgb = self.min_rgb_size <= current_size
             # fold ToRGB into the conv epilogue where the layer qualifies (<= 64 channels) and nothing needs the feature

@@ -160,6 +160,89 @@ def test_captured_pad_and_translate_at_1080_equal_eager(gpu):
     assert graphed.std() > 5 and not np.array_equal(graphed[0], graphed[BS])
 
 
+def test_captured_pad_and_translate_at_1080_equal_eager_range_and_oracle(gpu):
+    """The portrait twin of the 1920 test: ``ar.Pad((0, 0, 2, 2))`` on layer 0, the per-frame scroll on the 32 x 16 map of layer id 4,
+    64 x 32 frames.  Three lanes == the eager path == a render of a frame range that starts inside a batch, byte for byte; the second
+    batch against the oracle: the tapped fp32 image inside 1e-3, the frames within one grey level."""
+    import maua_stylegan2_amd.audioreactive as ar
+    from maua_stylegan2_amd import render
+    from oracle import stylegan2_oracle as so
+
+    lat, noise, pads, plane, hw, shift, canvas = inputs(1080, N)
+    assert pads == (0, 0, 2, 2) and hw == (32, 16)
+    sd = unsaturated_checkpoint(1080, lat, noise, oracle_bends(pads, plane, hw, shift[:2], canvas), seed=36)
+    g = wide_seeding.build_wide(SIZE, 1080, sd, gpu)
+    g.tap_float_image = True
+
+    def bends():
+        return [{"layer": 0, "transform": ar.Pad(pads, noise=plane.clone())},
+                {"layer": 4, "modulation": shift.clone(), "transform": lambda m: ar.Translate(m, hw[0], hw[1], canvas)}]
+
+    graphed, eager, images, taps, replays = render_both_ways(g, lat, noise, bends, N, LANES, (2 * SIZE, SIZE))
+    assert sorted(taps) == [0, 1, 2] and replays == [0, BS, 2 * BS]
+    assert all(tuple(lane.u8.shape) == (BS, 2 * SIZE, SIZE, 3) for lane in taps.values())
+    assert np.array_equal(graphed, eager)
+    assert graphed.std() > 5 and not np.array_equal(graphed[0], graphed[BS])
+
+    # a frame range that starts inside a batch of the full render: two captured batches (frames 3 .. 10) and an eager tail (11 .. 12)
+    lo, hi = 3, 13
+    ranged = np.zeros((hi - lo, 2 * SIZE, SIZE, 3), np.uint8)
+    firsts = []
+    for first, u8 in render.synthesize(g, lat, noise, BS, bends=bends(), use_graph=True, lanes=LANES, frame_range=(lo, hi)):
+        firsts.append(first)
+        ranged[first - lo: first - lo + u8.shape[0]] = u8.cpu().numpy()
+    assert firsts == [lo, lo + BS, lo + 2 * BS]
+    assert np.array_equal(ranged, graphed[lo:hi])
+
+    lo, hi = BS, 2 * BS
+    noise_o = [None if nz is None else nz[lo:hi] for nz in noise]
+    want = wide_seeding.oracle_forward(sd, lat[lo:hi], noise_o, oracle_bends(pads, plane, hw, shift[lo:hi], canvas))
+    plain = wide_seeding.oracle_forward(sd, lat[lo:hi], noise_o, oracle_bends(pads, None, hw, None, None))
+    assert tuple(want.shape) == (BS, 3, 2 * SIZE, SIZE) and tuple(images[lo].shape) == tuple(want.shape)
+    err = float((images[lo] - want).abs().max())
+    moved = float((want - plain).abs().mean())
+    print(f"[pad + translate at 64 x 32, frames {lo}..{hi - 1}] image std {float(want.std()):.3f}, max |hip - oracle| = {err:.3e} (float, "
+          f"full frames), clamped values {100 * seeding.clamped_fraction(want):.1f} %, noise plane + scroll move the image by {moved:.3f} on average")
+    assert moved > 0, "the bends must change the frames for this test to mean anything"
+    assert seeding.clamped_fraction(want) < 0.25
+    assert err < 1e-3, err
+    assert np.array_equal(so.frames_to_uint8(images[lo]), graphed[lo:hi]), "frames != cast of the tapped float image"
+    diff = np.abs(graphed[lo:hi].astype(np.int16) - so.frames_to_uint8(want).astype(np.int16))
+    assert diff.max() <= 1
+
+
+def test_capture_refuses_a_widening_bend_on_a_generator_built_square(gpu):
+    """A captured forward reads its noise through slots bound to maps of the generator's noise buffers' shape and sizes the uint8 frames
+    from them: with a layer-0 ``ar.Pad`` on a generator built WITHOUT ``output_size`` both would be half of what the layers read and
+    write.  The capture raises at conv1, before any layer runs, as the eager forward does on the checkpoint's square buffers."""
+    import maua_stylegan2_amd.audioreactive as ar
+    from maua_stylegan2_amd.models.stylegan2 import Generator
+
+    size, batch = 16, 2
+    g = Generator(size, 512, 8, channel_multiplier=2, constant_input=True)
+    g.load_state_dict(seeding.seeded_state_dict(size, seed=37), strict=True)
+    g = g.to(gpu).eval()
+    lat = seeding.seeded_latents(batch, g.n_latent, seed=38).to(gpu)
+    bends = [{"layer": 0, "transform": ar.Pad((2, 2, 0, 0))}]
+    with pytest.raises(RuntimeError, match="does not match feature map"):
+        g(styles=lat, noise=None, randomize_noise=False, input_is_latent=True, transform_dict_list=bends)
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for frames_u8 in (False, True):
+            with pytest.raises(RuntimeError, match="noise slot 0 holds 4 x 4 maps"):
+                g.capture_graph(batch, bends=bends, frames_u8=frames_u8)
+    stream.synchronize()
+    # the same generator without the bend still captures and replays
+    with torch.cuda.stream(stream):
+        lane = g.capture_graph(batch, frames_u8=True)
+        lane.bind(lat, [None] * g.num_layers)
+        lane.replay(0)
+        stream.synchronize()
+    assert tuple(lane.u8.shape) == (batch, size, size, 3) and float(lane.u8.float().std()) > 1
+    lane.release()
+
+
 def test_generate_with_the_wide_plugin_renders_1920_on_the_lanes(gpu, tmp_path, monkeypatch):
     """``generate(out_size=1920)`` with examples/wide.py on stand-in audio features: the layer-0 bend is captured (the full batch comes
     from a graph lane) and every delivered frame has the shape ``render`` itself names for that output size."""

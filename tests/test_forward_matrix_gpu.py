@@ -7,7 +7,11 @@ every intermediate image and the final image lie inside the per-element bounds 4
 exempt; (3) the captured form of the forward, bound to the
 case's 2 x batch frames and replayed at offsets 0 and batch, equals the eager forward bit for bit and records the same route.  The uint8
 cases compare the frames of a forward captured with ``frames_u8`` with floor((clamp(fp64) + 1) 127.5): exact wherever the reference decides
-the level, one level elsewhere."""
+the level, one level elsewhere.
+
+The non-square cases (``orient`` "wide" / "tall") run the same assertions on generators built for 1920 / 1080 output behind the replicate
+``ar.Pad`` on layer id 0 that widens the constant to 4 x 8 / 8 x 4: every layer then works on a 2:1 / 1:2 map and takes a route no square
+generator takes (tests/test_forward_routes_host.py lists them), and the last layer's epilogue writes 2:1 / 1:2 frames."""
 import contextlib
 
 import pytest
@@ -57,7 +61,8 @@ class Recorder:
                               lambda: run(self, x, s, s_off, d, noise, bufs, tag, rgb=rgb, src=src, slot=slot, prescaled=prescaled, post_off=post_off))
 
         def const_conv(self, s, s_off, d, noise, bufs, rgb, src, batch):
-            return rec._layer(self.conv1, "conv1", (4, 4), rgb, src, False, None, lambda: const_run(self, s, s_off, d, noise, bufs, rgb, src, batch))
+            return rec._layer(self.conv1, "conv1", tuple(self.input.input.shape[2:]), rgb, src, False, None,
+                              lambda: const_run(self, s, s_off, d, noise, bufs, rgb, src, batch))
 
         def torgb_run(self, x, s, s_off, skip, out):
             if s is not None and rec.forwards:  # (s None: the plane sum behind a layer that left partial sums — part of that layer's path)
@@ -115,8 +120,10 @@ def _build(case, gpu):
     from maua_stylegan2_amd.models.stylegan2 import Generator
 
     inp = fr.inputs(case)
-    g = Generator(case.size, 512, 8, channel_multiplier=case.cm, constant_input=case.constant_input, min_rgb_size=case.min_rgb_size)
-    g.load_state_dict(inp["sd"], strict=True)
+    g = Generator(case.size, 512, 8, channel_multiplier=case.cm, constant_input=case.constant_input, min_rgb_size=case.min_rgb_size,
+                  output_size=case.output_size)
+    g.load_state_dict(inp["sd"], strict=True)  # (a non-square case: the 2:1 noise buffers are part of the state dict)
+    assert [tuple(getattr(g.noises, f"noise_{i}").shape[-2:]) for i in range(g.num_layers)] == fr.noise_shapes(case)
     g = g.to(gpu).eval()
     for attr, value in case.gen:
         setattr(g, attr, value)
@@ -167,7 +174,8 @@ def test_forward_route_and_fp64_parity(gpu, case):
         for n, want in enumerate(ref["images"]):
             if want is not None and case.min_rgb_size <= 4 * 2 ** n:
                 buf = g._bufs[(b, "rgb1" if n == 0 else f"rgbs.{n - 1}", 0)]
-                worst.append(fr.check(f"image after {4 * 2 ** n}^2", buf, want, bnd["images"][n]))
+                side = f"{4 * 2 ** n}^2" if case.orient == "square" else f"{want.shape[2]} x {want.shape[3]}"
+                worst.append(fr.check(f"image after {side}", buf, want, bnd["images"][n]))
         if ref["image"] is None:
             assert image is None
         else:
@@ -176,7 +184,7 @@ def test_forward_route_and_fp64_parity(gpu, case):
         for frac, msg in worst:
             print(f"[{case.name}] {msg}")
         top = max(worst)
-        print(f"[{case.name}] worst: {top[1]}; without G (4 x the fp32 CPU forward's own error) that is {top[0] * fr.winograd_gain():.2f} of the bound")
+        print(f"[{case.name}] worst: {top[1]}; without G (4 x the fp32 CPU forward's own error) that is {top[0] * fr.winograd_gain(case.orient):.2f} of the bound")
         assert all(frac <= 1.0 for frac, _ in worst), [msg for frac, msg in worst if frac > 1.0]
         # (3) the captured form
         if not case.capturable:
@@ -205,6 +213,7 @@ def test_forward_route_and_fp64_parity(gpu, case):
                     continue
                 last = want_graph[f"convs.{g.num_layers - 2}"]
                 frames = lane.u8.cpu()
+                assert tuple(frames.shape) == (b,) + tuple(ref["image"].shape[2:]) + (3,)  # (rows x columns of the padded generator)
                 cast = lambda img: ((img.clamp(-1, 1) + 1) * 127.5).permute(0, 2, 3, 1).to(torch.uint8).cpu()  # noqa: E731
                 assert int((frames.int() - cast(eager).int()).abs().max()) <= 1  # (the eager forward has no uint8 form: another instance)
                 if last.u8 == "layer" and not case.u8:

@@ -8,8 +8,11 @@ conv_ref.case_operands at the layer's spatial shape, in units of u M (conv_ref.r
     sequential    the DIRECT form with one float32 accumulator per output over (tap, channel), term after term (this file)
     once_rounded  conv_ref._direct_conv: the float32 product x * s, the convolution summed in float64, ONE rounding of the result
 
-    G[mode]              = max over the layers of  emulated / sequential      <- what the bound uses (floored at 1)
+    G_all_cases[mode]    = max over the layers of  emulated / sequential      <- floored at 1; recorded, used by nothing
     G_once_rounded[mode] = max over the layers of  emulated / once_rounded    <- recorded, used by nothing
+    G_by_orientation[o]  = the same (<- what the bound uses) over the layers of the cases of orientation o (square, wide = 2:1 maps, tall = 1:2) alone: a case's bound takes
+                           the largest entry of its own orientation, so that the layer shapes of the non-square generators (the 16 x 32
+                           map of the 2-D Winograd kernels among them) do not widen the bounds of forwards that never run them
 
 Why the first.  The bound is 4 G E with E measured from a float32 CPU forward, whose convolutions accumulate in float32: E contains the
 accumulation rounding of a direct form already, and G has to add only what the transforms amplify.  conv_ref._direct_conv contains no
@@ -77,35 +80,44 @@ def main():
     ap.add_argument("--cout", type=int, default=64)
     ap.add_argument("--write", action="store_true")
     args = ap.parse_args()
-    shapes = {}
+    shapes, orients = {}, {}
     for case in forward_ref.CASES:
         with forward_ref.switched(case):
             g = forward_ref.case_skeleton(case)
-            for tag, layer, _, h in forward_ref.layer_shapes(g):
-                mode = layer.conv.conv_mode(h, h)
+            for tag, layer, _, (h, w) in forward_ref.layer_shapes(g, case.orient):
+                mode = layer.conv.conv_mode(h, w)
                 if mode >= 2:
                     c = layer.conv
-                    shapes.setdefault((mode, min(c.in_channel, args.cin), min(c.out_channel, args.cout), h), []).append(
-                        f"{case.size}/cm{case.cm} {tag} {c.in_channel}->{c.out_channel}")
+                    orient = "" if case.orient == "square" else case.orient + " "
+                    key = (mode, min(c.in_channel, args.cin), min(c.out_channel, args.cout), h, w)
+                    shapes.setdefault(key, []).append(f"{orient}{case.size}/cm{case.cm} {tag} {c.in_channel}->{c.out_channel}")
+                    orients.setdefault(key, set()).add(case.orient)
     gain, once_rounded, rows = {"0": 1.0, "1": 1.0}, {"0": 1.0, "1": 1.0}, []
-    for (mode, cin, cout, h), where in sorted(shapes.items()):
-        emulated, sequential, once = layer_ratios(mode, cin, cout, h, h)
-        rows.append(dict(mode=mode, cin=cin, cout=cout, h=h, emulated=round(emulated, 3), sequential=round(sequential, 3), once_rounded=round(once, 3),
+    by_orient = {o: {"0": 1.0, "1": 1.0} for o in forward_ref.ORIENTATIONS}
+    for (mode, cin, cout, h, w), where in sorted(shapes.items()):
+        emulated, sequential, once = layer_ratios(mode, cin, cout, h, w)
+        rows.append(dict(mode=mode, cin=cin, cout=cout, h=h, w=w, emulated=round(emulated, 3), sequential=round(sequential, 3), once_rounded=round(once, 3),
                          layers=sorted(set(where))))
         gain[str(mode)] = max(gain.get(str(mode), 1.0), emulated / sequential)
+        for o in orients[(mode, cin, cout, h, w)]:
+            by_orient[o][str(mode)] = max(by_orient[o].get(str(mode), 1.0), emulated / sequential)
         once_rounded[str(mode)] = max(once_rounded.get(str(mode), 1.0), emulated / once)
-        print(f"mode {mode}  {cin:3d} -> {cout:3d} @ {h:4d}^2   emulated {emulated:6.2f}   sequential direct {sequential:5.2f}   once-rounded direct {once:5.2f} u M"
+        print(f"mode {mode}  {cin:3d} -> {cout:3d} @ {h:4d} x {w:4d}   emulated {emulated:6.2f}   sequential direct {sequential:5.2f}   once-rounded direct {once:5.2f} u M"
               f"   ratios {emulated / sequential:5.2f} / {emulated / once:5.2f}   {', '.join(sorted(set(where))[:3])}")
     ceil2 = lambda table: {k: round(float(np.ceil(v * 100) / 100), 2) for k, v in sorted(table.items())}  # noqa: E731
     gain, once_rounded = ceil2(gain), ceil2(once_rounded)
+    by_orient = {o: ceil2(table) for o, table in by_orient.items()}
     print("G per mode (emulated / sequential fp32 direct form):", gain, " G =", max(gain.values()))
+    for o, table in by_orient.items():
+        print(f"  over the {o} cases' layers:", table, " G =", max(table.values()))
     print("recorded only, emulated / once-rounded direct form (conv_ref._direct_conv):", once_rounded)
     if args.write:
         out = dict(command=f"python tools/forward_tolerance.py --cin {args.cin} --cout {args.cout} --write",
-                   note="units of u M; cin and cout cut at the layer's own spatial shape; G = emulated fp32 rounding of the mode / rounding of the "
-                        "direct form accumulated term after term in fp32, same operands, floored at 1 — the whole-forward bound uses its largest "
-                        "entry; G_once_rounded = the ratio to conv_ref._direct_conv (fp64 sum rounded once), used by nothing",
-                   G=gain, G_once_rounded=once_rounded, layers=rows)
+                   note="units of u M; cin and cout cut at the layer's own spatial shape; G_all_cases = emulated fp32 rounding of the mode / rounding of the "
+                        "direct form accumulated term after term in fp32, same operands, floored at 1, over the layers of every case (recorded, used by nothing); G_by_orientation = the same over the "
+                        "layers of the square / wide (2:1) / tall (1:2) cases alone — the whole-forward bound of a case uses the largest "
+                        "entry of its orientation; G_once_rounded = the ratio to conv_ref._direct_conv (fp64 sum rounded once), used by nothing",
+                   G_all_cases=gain, G_by_orientation=by_orient, G_once_rounded=once_rounded, layers=rows)
         with open(forward_ref.TOLERANCE_JSON, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
